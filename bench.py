@@ -1,7 +1,14 @@
 """MPPI solve benchmark (BASELINE.json metric: trajectory-steps/sec (K x H per solve) + wall-clock per solve).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload humanoid_ca|cartpole|humanoid_mlp|quad_mlp|cartpole_fa|quad_fa]
+                    [--full] [--dump-outputs DIR]
 
+A plain run sets up, ramps the clock, warms up, times the K steps and prints the result line (the rollout's roofline
+figures come from device-clock stamps inside the timed region).  --full adds the measurements that take runs of their
+own: the rocprofv3 kernel-trace and PMC traffic child passes, the HIP-event pass over plain solves and the CPU
+baseline (each can be left out again with its --no-... option).  --dump-outputs DIR writes the controls the last
+timed step left (DIR/U.npy, DIR/u0.npy, streams also DIR/x0.npy; float32): the warmup and timed steps start from a
+fixed state, so two runs with the same arguments write the same arrays.
 One step = one batched MPPI solve per rank (noise -> rollout -> cost -> softmin -> reduce -> update -> shift),
 replayed from a captured hipGraph with inputs resident in HBM, then (N > 1) an RCCL all-gather of the reduced
 control sequences U* and u0 (overlapped with the next step's solve; all gathers complete inside the timed region).  Stream workloads chain 256 solves (with the on-device env step) per step.
@@ -253,7 +260,8 @@ def pmc_traffic(args, kernel_substr: str) -> dict | None:
         out = os.path.join(d, "pmc")
         cmd = [prof, "-i", inp, "-d", out, "-o", "pmc", "--output-format", "csv", "--", sys.executable,
                os.path.abspath(__file__), "--workload", args.workload, "--precision", args.precision, "--steps",
-               "3", "--warmup", "1", "--no-cpu-baseline", "--no-traffic", "--no-kernel-trace", "--launch", args.launch, "--ramp-ms", "0",
+               "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-traffic", "--no-kernel-trace", "--launch", args.launch,
+               "--ramp-ms", "0",
                "--stream-solves",
                "4" if args.stream_solves or "stream" in args.workload else "0", "--solves", str(args.solves),
                "--global-solves", str(args.global_solves)]
@@ -353,13 +361,25 @@ def main():
     ap.add_argument("--weak", action="store_true",
                     help="weak scaling: the whole config #4 (64 solves) on every rank, no data-path collective "
                          "(= --solves 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC passes for roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the rocprofv3 kernel-trace and PMC traffic "
+                         "child passes (kernel_ms, roofline.traffic), the HIP-event pass over plain solves "
+                         "(plain_solve_kernel_ms) and the CPU baseline (cpu_baseline); off by default, and each part can "
+                         "be left out again with its --no-... option")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the controls the last timed step left, as a caller of the step "
+                         "receives them: DIR/U.npy [solves, nu, H] and DIR/u0.npy [solves, nu] (every rank's rows at "
+                         "N > 1, from the gather), stream workloads also DIR/x0.npy (the state the stream reached); "
+                         "float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-traffic", action="store_true",
+                    help="with --full: skip the rocprofv3 PMC passes for roofline.traffic")
     ap.add_argument("--stream-solves", type=int, default=0, help="override the stream length (stream workloads)")
     ap.add_argument("--no-kernel-trace", action="store_true",
-                    help="skip the rocprofv3 kernel-trace pass that times the graph path's kernels (kernel_ms)")
+                    help="with --full: skip the rocprofv3 kernel-trace pass that times the graph path's kernels "
+                         "(kernel_ms)")
     ap.add_argument("--no-plain-pass", action="store_true",
-                    help="skip the HIP-event pass over plain solves before the timed region")
+                    help="with --full: skip the HIP-event pass over plain solves before the timed region")
     ap.add_argument("--ramp-ms", type=float, default=150.0,
                     help="untimed GPU work (the same steps) before the warmup steps, so the timed region runs at "
                          "steady-state clocks: after an idle host phase the GPU clock ramps over ~20 ms of load "
@@ -376,6 +396,8 @@ def main():
         args.precision = DEFAULT_PRECISION.get(args.workload, "bf16")
     if args.weak and not args.solves:
         args.solves = 64
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_traffic = args.no_kernel_trace = args.no_plain_pass = True
 
     # --gpus N is the number of ranks: without a launcher start N ranks under torch.distributed.run (before any GPU
     # call in this process), under one it must agree with WORLD_SIZE
@@ -445,6 +467,7 @@ def main():
     # B solves per rank; the global list is rows 0..G-1 of the x0 table (config #4: 64 rows over 8 ranks).
     rows = np.arange(start, stop) % spec["x0_all"].shape[0]
     x0 = torch.from_numpy(np.ascontiguousarray(spec["x0_all"][rows], np.float32)).to(dev)
+    x0_init = x0.clone()
     # nominal sequences U [B, nu, H] (resident in HBM, updated in place) and u0 [B, nu]: views of one flat buffer,
     # so each step's controls leave the rank with one snapshot copy and ONE all-gather
     from mppi_hip.distributed import control_buffers
@@ -490,6 +513,8 @@ def main():
     if mirror:
         eng.set_U(U[:B].cpu().numpy(), B)
 
+    last = [None]  # the gather handle of the newest gathered step (--dump-outputs reads its result)
+
     def step(i, gathered=True):
         if launch == "graph":
             eng.graph_launch(sync=False)
@@ -498,13 +523,13 @@ def main():
             eng.solve_device(B, x0.data_ptr(), Us.data_ptr(), None, seed=rank << 40, u0_ptr=u0s.data_ptr(),
                              shift=True, resident_U=True, env_step=env_step, seed_counter=True, chain=True)
             if gathered:
-                gather.commit()
+                last[0] = gather.commit()
             return
         else:
             eng.solve_device(B, x0.data_ptr(), U.data_ptr(), None, seed=rank << 40, u0_ptr=u0.data_ptr(), shift=True,
                              env_step=env_step, seed_counter=True, chain=True)
         if gather is not None and gathered:
-            gather.submit(U, u0)
+            last[0] = gather.submit(U, u0)
 
     # clock ramp: the same steps, untimed, for at least --ramp-ms of wall time, then the W warmup steps.  Each rank
     # times its own ramp, so the ramp steps run without the control gather: a collective per ramp step would pair
@@ -515,6 +540,16 @@ def main():
             step(-1, gathered=False)
             n_ramp += 1
         torch.cuda.synchronize(dev)
+    # a fixed start for the warmup and timed steps: the ramp (and the plain-solve pass) ran a number of solves that
+    # differs from run to run, and every solve moves U, the noise key counter and a stream's x0.  Back to the initial
+    # states, zero controls and key 0, so the same arguments give the same steps, output for output (--dump-outputs).
+    # The reset drops the prefetched noise, so the first step after it generates its own again (a warmup step).
+    torch.cuda.synchronize(dev)
+    x0.copy_(x0_init)
+    flat_ctrl.zero_()
+    if mirror:
+        eng.set_U(U[:B].cpu().numpy(), B)
+    eng.set_seed_counter(0)
     for i in range(args.warmup):
         step(i)
     if gather is not None:
@@ -547,6 +582,23 @@ def main():
     f16_l1 = bool(f16_on) and "<l1=f16" in routed
     f16_l2x1 = (f16_all or f16_l1) and routed.endswith(",l2=1>")
     f16_ran = f16_all or f16_l1
+
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # what the last timed step handed its caller: the updated (shifted) U and the applied controls u0 -- this
+        # rank's own at N = 1, every rank's from that step's gather otherwise (each rank's rows up to its shard's
+        # size: the rows behind a short shard are padding) -- and, for a stream, the state its env steps reached
+        if gather is not None:
+            U_all, u0_all = gather.result(last[0])
+            bounds = [shard_bounds(G, r, world) for r in range(world)]
+            keep = np.concatenate([r * Bmax + np.arange(stop_r - start_r) for r, (start_r, stop_r, _) in enumerate(bounds)])
+            outs = {"U": U_all.cpu().numpy()[keep], "u0": u0_all.cpu().numpy()[keep]}
+        else:
+            outs = {"U": U[:B].cpu().numpy(), "u0": u0[:B].cpu().numpy()}
+        if env_step:
+            outs["x0"] = x0.cpu().numpy()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
     if rank == 0:
         solves_per_step = max(n_stream, 1)

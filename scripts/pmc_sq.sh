@@ -10,7 +10,7 @@ mkdir -p gpurun_out
 passes=${PMC_PASSES:-"SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY;SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_UNALIGNED_STALL"}
 echo "$passes" | tr ';' '\n' | sed 's/^/pmc: /' > "$out.txt"
 timeout -k 10 300 rocprofv3 -i "$out.txt" -d "$out" -o pmc --output-format csv -- \
-  python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-traffic --no-kernel-trace "$@" > "$out.log" 2>&1
+  python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-traffic --no-kernel-trace "$@" > "$out.log" 2>&1
 rc=$?
 echo "== pmc $name rc=$rc"
 python3 - "$out" <<'PY'

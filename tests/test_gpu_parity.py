@@ -1272,7 +1272,7 @@ def test_seed_counter_resume_chained_and_graph(M, mode):
 # ------------------------------------------------------------------------------------------ bench launch path
 
 @pytest.mark.parametrize("ranks", [2, 3])
-def test_bench_two_ranks_complete(M, ranks):
+def test_bench_two_ranks_complete(M, ranks, tmp_path):
     """bench.py --gpus 2 (ranks under torch.distributed.run, here two gloo ranks sharing device 0; the driver's
     scaling runs use RCCL, one rank per GPU): every rank runs the clock ramp, warmup and timed steps with the
     pipelined control gather, and rank 0 prints one JSON line with n_gpus = 2.  Guards the ramp against collectives:
@@ -1286,7 +1286,8 @@ def test_bench_two_ranks_complete(M, ranks):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", str(ranks), "--steps", "4",
-                        "--warmup", "2", "--ramp-ms", "60", "--no-cpu-baseline", "--no-traffic", "--no-kernel-trace"],
+                        "--warmup", "2", "--ramp-ms", "60", "--no-cpu-baseline", "--no-traffic", "--no-kernel-trace",
+                        "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=150, env=env, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1295,6 +1296,14 @@ def test_bench_two_ranks_complete(M, ranks):
     # -- shard_bounds: 22 / 22 / 20 (rank 0 reports its own 22), the gather sized for 22
     assert line["scaling"] == "strong" and line["config"]["solves_per_gpu"] == -(-64 // ranks)
     assert line["config"]["global_solves"] == 64
+    # --dump-outputs at N > 1: the last timed step's gathered controls, the 64 solves' rows in order (the padding
+    # rows behind the short last shard dropped), every one a solve's result
+    Ud, u0d = np.load(tmp_path / "U.npy"), np.load(tmp_path / "u0.npy")
+    assert Ud.dtype == u0d.dtype == np.float32 and Ud.shape == (64, 21, 64) and u0d.shape == (64, 21)
+    assert np.isfinite(Ud).all() and np.isfinite(u0d).all()
+    assert (np.abs(Ud).max(axis=(1, 2)) > 0).all() and (np.abs(u0d).max(axis=1) > 0).all()
+    # 64 different states (and a noise seed per rank): no two solves share a row
+    assert len(np.unique(Ud.reshape(64, -1), axis=0)) == 64
 
 
 def _perturbed_fa(nx, nu, D, layers, seed, num_heads=4):
@@ -1454,11 +1463,13 @@ def test_resident_U_mirror_chain(M):
 @pytest.mark.parametrize("extra", [["--workload", "humanoid_ca_stream"], ["--steps", "10"],
                                    ["--weak", "--steps", "10"],
                                    ["--workload", "cartpole", "--steps", "20"]])
-def test_bench_line_default_steps(M, extra):
+def test_bench_line_default_steps(M, extra, tmp_path):
     """bench.py at its default step count (50) for the receding-horizon stream (config #5: 256 solves per step, 12800
     stamped rollout launches, past round 2's 8192 clock slots), config #4's whole 64-state batch on one GPU (the
     default: config #4's 64 states split over the ranks, strong scaling; --weak: 64 per GPU, weak scaling), and the
-    analytic cartpole, whose line must report the fp32 it runs."""
+    analytic cartpole, whose line must report the fp32 it runs.  A plain run (no --full) carries none of the
+    measurements that take runs of their own, and --dump-outputs writes the last timed step's controls: for the
+    cartpole, bitwise what warmup + steps chained solves from the fixed start (logged x0, U = 0, noise key 0) give."""
     import json
     import os
     import subprocess
@@ -1467,12 +1478,44 @@ def test_bench_line_default_steps(M, extra):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
+    out = tmp_path / "out"
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--warmup", "1", "--ramp-ms", "30",
-                        "--no-cpu-baseline", "--no-traffic", "--no-kernel-trace", "--no-plain-pass"] + extra,
+                        "--no-cpu-baseline", "--no-traffic", "--no-kernel-trace", "--no-plain-pass",
+                        "--dump-outputs", str(out)] + extra,
                        capture_output=True, text=True, timeout=110, env=env, cwd=repo)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["value"] > 0 and line["roofline"]["launches"] > 0
+    steps = int(extra[extra.index("--steps") + 1]) if "--steps" in extra else 50
+    assert line["steps"] == steps and line["ms_per_step"] > 0
+    assert line["kernel_ms"] is None and line["plain_solve_kernel_ms"] is None and line["cpu_baseline"] is None
+    assert line["roofline"]["traffic"] is None
+    stream = "humanoid_ca_stream" in extra
+    nu, H, nx = (1, 50, 4) if "cartpole" in extra else (21, 128 if stream else 64, 55)
+    B = line["config"]["solves_per_gpu"] // (256 if stream else 1)
+    dumped = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(dumped) == (["U.npy", "u0.npy", "x0.npy"] if stream else ["U.npy", "u0.npy"])
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dumped.values())
+    assert dumped["U.npy"].shape == (B, nu, H) and dumped["u0.npy"].shape == (B, nu)
+    assert np.abs(dumped["U.npy"]).max() > 0
+    if stream:
+        assert dumped["x0.npy"].shape == (B, nx)
+    if "cartpole" in extra:
+        import torch
+        from mppi_hip.distributed import control_buffers
+        eng = _engine(M, "cartpole_py", K=4096, H=50, precision=0, max_batch=1)
+        eng.load_dynamics(1).set_cost("cartpole")
+        dev = torch.device("cuda")
+        tx = torch.tensor([[0.0, np.pi, 0.0, 0.0]], dtype=torch.float32, device=dev)
+        _, tU, tu0 = control_buffers(1, 1, 50, device=dev)
+        eng.set_stream(torch.cuda.current_stream().cuda_stream)
+        for _ in range(1 + steps):
+            eng.solve_device(1, tx.data_ptr(), tU.data_ptr(), None, seed=0, u0_ptr=tu0.data_ptr(), shift=True,
+                             seed_counter=True, chain=True)
+        torch.cuda.synchronize()
+        eng.close()
+        np.testing.assert_array_equal(dumped["U.npy"], tU.cpu().numpy())
+        np.testing.assert_array_equal(dumped["u0.npy"], tu0.cpu().numpy())
     if "cartpole" in extra:
         assert line["dtype"] == "fp32"
     if extra == ["--steps", "10"]:

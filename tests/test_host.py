@@ -122,20 +122,20 @@ def test_controller_passes_real_env_context_every_call():
 
 
 def test_humanoid_body_ids_match_the_model_xml():
-    """HUMANOID_BODY_IDS are the MuJoCo body ids of src/humanoid.xml (world 0, then <body> elements depth-first)."""
-    import pytest
-    import xml.etree.ElementTree as ET
+    """HUMANOID_BODY_IDS are the MuJoCo body ids of src/humanoid.xml (world 0, then <body> elements depth-first);
+    the model's body tree (names and nesting) is stored as tests/golden/humanoid_bodies.json."""
+    import json
     from mppi_hip.controller import HUMANOID_BODY_IDS
-    path = "/root/reference/src/humanoid.xml"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present")
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "humanoid_bodies.json")) as f:
+        tree = json.load(f)
     names = ["world"]
 
-    def walk(e):
-        for b in e.findall("body"):
-            names.append(b.get("name"))
-            walk(b)
-    walk(ET.parse(path).getroot().find("worldbody"))
+    def walk(bodies):
+        for b in bodies:
+            names.append(b["name"])
+            walk(b["body"])
+    walk(tree["worldbody"])
+    assert len(names) == 18 and len(set(names)) == 18
     assert {n: names.index(n) for n in HUMANOID_BODY_IDS} == HUMANOID_BODY_IDS
 
 
