@@ -18,7 +18,6 @@
 // it used to be chosen).
 #include "fc_rollout.h"
 
-#include <cstdlib>
 
 namespace mppi {
 
@@ -328,32 +327,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   kclock_record(a, kc);
 }
 
-// MPPI_FC_PIPE=1 forces this kernel (read per launch, so a test can switch it).  It used to be chosen by itself for
-// batches that fill whole rounds of 2 blocks x 3 tiles per CU (48 solves of config #4: 423.6 vs 446.5 us for the M-split
-// kernel); the per-wave kernel (kernels_fc_wave.hip) is faster on every such batch (48 solves: 330 us; 24: 190 vs 212
-// us; scripts/gpu_sweep_wave.sh), so it is now an A/B arm only.
-static int fc_pipe_mode() {
-  const char* e = std::getenv("MPPI_FC_PIPE");
-  return e ? std::atoi(e) : -1;
-}
-
-bool fc_pipe_wanted(const SolveArgs& a) {
-  (void)a;
-  return fc_pipe_mode() == 1;
-}
-
-hipError_t launch_fc_pipe(const SolveArgs& a, FcArgs fa, hipStream_t stream) {
+// MPPI_FC_PIPE=1 forces this kernel (fc_route.h).  It used to be chosen by itself for batches that fill whole rounds of
+// 2 blocks x 3 tiles per CU (48 solves of config #4: 423.6 vs 446.5 us for the M-split kernel); the per-wave kernel
+// (kernels_fc_wave.hip) is faster on every such batch (48 solves: 330 us; 24: 190 vs 212 us;
+// scripts/gpu_sweep_wave.sh), so it is now an A/B arm only.
+hipError_t launch_fc_pipe(const SolveArgs& a, const FcArgs& fa, const FcRoute&, hipStream_t stream) {
   const int tiles = a.B * (a.Kp >> 4);
   const int grid = (tiles + 2) / 3;
-  auto go = [&](auto kern, int bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
-  if (a.cost_kind == MPPI_COST_HUMANOID_V1) return go(fc_pipe_kernel<MPPI_COST_HUMANOID_V1>, PipeLay<MPPI_COST_HUMANOID_V1>::BYTES);
-  return go(fc_pipe_kernel<MPPI_COST_HUMANOID_V3>, PipeLay<MPPI_COST_HUMANOID_V3>::BYTES);
+  return by_humanoid_cost(a.cost_kind, [&](auto cost) {
+    constexpr int C = decltype(cost)::value;
+    return fc_launch(fc_pipe_kernel<C>, grid, 256, PipeLay<C>::BYTES, stream, a, fa);
+  });
 }
 
 }  // namespace mppi

@@ -3,9 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
+#include <type_traits>
 
 #include "costs.h"
+#include "fc_route.h"
 #include "mppi_internal.h"
 
 namespace mppi {
@@ -39,33 +40,6 @@ struct Arch<kArchMLP> {  // MLPStatePredictor(nx, nu, 128, hidden_layers=2), lea
   static constexpr int QP = 64;
   static constexpr int REG_MASK = kMlpRegMask;
 };
-
-struct FcArgs {
-  const char* img;  // packed image in global memory
-  int img_bytes, lds_bytes;
-  int w_off[4], b_off[4];
-  int lnb_off, ln_n;  // beta' of the folded LayerNorm (mppi_nets.cpp)
-  int qp, qv;  // state slots: x[0, qp) -> [0, qp); x[qp, qp+qv) -> [32, 32+qv)
-  int groups_per_block;
-  int g_off;  // FcNet::g_off (the per-wave CA kernel's Gram fragments), -1: none
-  int wave;   // FcNet::wave
-  int w32_off;  // FcNet::w32_off
-  int w32_bd;   // FcNet::w32_bd
-  int w0bd_off, gbd_off;  // FcNet::w0bd_off, gbd_off
-  int w32x3_off, w32x3_l1lo_off;  // FcNet::w32x3_off, w32x3_l1lo_off
-  int wmx3_off, wmx3_lo_off;      // FcNet::wmx3_off, wmx3_lo_off
-  int wm32x3_off, wm32x3_lo_off;  // FcNet::wm32x3_off, wm32x3_lo_off
-  int x3_l1;                      // FcNet::x3_l1 (the probe's decision for this net)
-  int w32f16_off;                 // FcNet::w32f16_off (fc_wave32_x3p_kernel's fp16 form image)
-  int wmf16_off, wmf16_x_off;     // FcNet::wmf16_off, wmf16_x_off (fc_rollout_kernel_x3d's fp16 form)
-  int wmf16_0_off;                // FcNet::wmf16_0_off
-  int wmf16_0b_off;               // FcNet::wmf16_0b_off
-  int x3_f16;                     // FcNet::x3_f16 (the probe's decision on the fp16 form)
-  int x3_route;                   // FcNet::x3_route (the probe's direct launches: 1 fc_wave32_x3p_kernel, 2 _x3h)
-};
-
-// kernels_fc_x3h.hip: whether the few-tiles shards' fp16-form kernel runs this net (the engine's probe checks it too)
-bool fc_x3h_wanted(const SolveArgs& a, const FcArgs& fa);
 
 // ------------------------------------------------------------------------------------------------ precision traits
 
@@ -147,18 +121,7 @@ struct BX3 {
 // beyond kX3TwoTermMaxH.  Any other layer with two products, or layer 1 without W1_lo, exceeds 1e-4 already at H = 64
 // on model_cross, and so does every layer of the MLP, which keeps three.  It takes 64 of the per-wave kernels' 306
 // MFMAs per wave-step (M-split: 32 of 168) and layer 0's lo conversions.  MPPI_X3_L1_TERMS=3 / =2 (read per launch)
-// forces three / two products without a probe (A/B and tests).
-constexpr int kX3TwoTermMaxH = 64;
-constexpr float kX3ProbeTol = 7.5e-5f;  // 3/4 of the fp32-accurate bar (costs rtol 1e-4 against the fp32 oracle);
-                                        // model_cross.pth on config #4's logged states: 4.95e-5 (CPU emulation)
-inline int x3_l1_env() {
-  const char* e = std::getenv("MPPI_X3_L1_TERMS");
-  return e && (e[0] == '2' || e[0] == '3') ? e[0] - '0' : 0;
-}
-inline int x3_l1_terms(int H, int decided) {
-  if (const int f = x3_l1_env()) return f;
-  return H <= kX3TwoTermMaxH && decided == 2 ? 2 : 3;
-}
+// forces three / two products without a probe (A/B and tests).  (fc_route.h: x3_l1_terms, kX3TwoTermMaxH, kX3ProbeTol)
 // The fp16 form of the split CA (L1T == 1 in the per-wave kernels, F16 in fc_rollout_kernel_x3d): layer 1 as ONE fp16
 // MFMA product per (tile, k-step), fp16 W1 against the fp16 ReLU'd layer-0 output, and the last layer as two (fp16 W hi
 // + lo against fp16 activations); the per-wave kernels (fc_wave32_x3p_kernel, fc_wave32_x3_kernel) take layer 0 and the
@@ -171,31 +134,13 @@ inline int x3_l1_terms(int H, int decided) {
 // W1 lo stream from L2, no hi / lo splits in VALU; x3d: 48 instead of 68.  A CHECKED property of the net like the
 // two-product form: x3_probe runs fc_wave32_x3p_kernel's fp16 form against three products and keeps it only within
 // kX3ProbeTol, never beyond kX3TwoTermMaxH.  MPPI_X3_F16=0 / =1 (read per launch) forces it off / on without a probe.
-inline int x3_f16_env() {
-  const char* e = std::getenv("MPPI_X3_F16");
-  return e && (e[0] == '0' || e[0] == '1') ? (e[0] == '1' ? 1 : -1) : 0;
-}
-inline bool x3_f16_on(int H, int decided, int img_off) {
-  if (img_off < 0) return false;
-  if (const int f = x3_f16_env()) return f > 0;
-  return H <= kX3TwoTermMaxH && decided >= 1;
-}
 // ... with the last layer as ONE fp16 product (fp16 W against the fp16 activations): OPT-IN only, MPPI_X3_F16_L2=1 (read
 // per launch).  124 MFMAs per wave-step instead of 140, rollout -6 % (profiles/r06_ab_f16_l2x1.log), but not
 // fp32-accurate on every logged state: CPU emulation "f16x2w,f16x1,f16x1" 4.8e-5 from the fp32 oracle over config
 // #4's 64 states, while on the GPU one of 34 logged states (H = 64) ended 1.04e-4 from the three-product costs
 // (profiles/r06_gpu_tests_f16_l2x1.log) -- the dynamics error is common to all samples of a solve (the CA's action
 // encoder never reaches its output), so one state's error is the whole solve's.  The probe does not pick it.
-inline bool x3_f16_l2x1(int decided) {
-  const char* e = std::getenv("MPPI_X3_F16_L2");
-  return (e && e[0] == '1') || decided == 2;
-}
-// The split CA rollout's form at launch: 0 = fp16 with the one-product last layer, 1 = fp16, 2 = bf16 with the
-// two-product layer 1, 3 = bf16 three products (the kernels' L1T template argument)
-inline int x3_form(int H, int l1_decided, int f16_decided, int f16_img) {
-  if (x3_f16_on(H, f16_decided, f16_img)) return x3_f16_l2x1(f16_decided) ? 0 : 1;
-  return x3_l1_terms(H, l1_decided);
-}
+// (fc_route.h: x3_f16_on, x3_f16_l2x1, x3_form)
 __device__ __forceinline__ unsigned pk_bf16_x3(float a, float b) {  // one v_cvt_pk_bf16_f32 (RNE)
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
@@ -411,5 +356,39 @@ struct Lay {
   static constexpr int CP = ST + kSplit * 16 * 8;
   static constexpr int BYTES = (CP + kSplit * 16 * 4 + 15) / 16 * 16;
 };
+
+// ------------------------------------------------------------------------------------------------ launch helpers
+
+// One rollout launch.  > 64 KiB of dynamic LDS must be opted into per kernel (gfx950 has 160 KiB per CU); set on every
+// launch, since the attribute holds per device and a process may drive several.
+template <class Kern, class Net>
+inline hipError_t fc_launch(Kern kern, int grid, int block, size_t lds, hipStream_t stream, const SolveArgs& a,
+                            const Net& net) {
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, a, net);
+  return hipGetLastError();
+}
+// f(std::integral_constant<int, COST>{}) for the solve's cost: every cost (the MLP kernels) ...
+template <class F>
+inline hipError_t by_cost(int cost_kind, F&& f) {
+  switch (cost_kind) {
+    case MPPI_COST_HUMANOID_V3: return f(std::integral_constant<int, MPPI_COST_HUMANOID_V3>{});
+    case MPPI_COST_HUMANOID_V1: return f(std::integral_constant<int, MPPI_COST_HUMANOID_V1>{});
+    case MPPI_COST_QUAD_JL: return f(std::integral_constant<int, MPPI_COST_QUAD_JL>{});
+    case MPPI_COST_QUAD_EST: return f(std::integral_constant<int, MPPI_COST_QUAD_EST>{});
+    case MPPI_COST_CARTPOLE_EST: return f(std::integral_constant<int, MPPI_COST_CARTPOLE_EST>{});
+    case MPPI_COST_CARTPOLE: return f(std::integral_constant<int, MPPI_COST_CARTPOLE>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+// ... or the humanoid's two (the CA kernels are built for the humanoid, qpos 28; launch_fc_route checks the cost)
+template <class F>
+inline hipError_t by_humanoid_cost(int cost_kind, F&& f) {
+  if (cost_kind == MPPI_COST_HUMANOID_V1) return f(std::integral_constant<int, MPPI_COST_HUMANOID_V1>{});
+  return f(std::integral_constant<int, MPPI_COST_HUMANOID_V3>{});
+}
 
 }  // namespace mppi

@@ -108,7 +108,7 @@ __device__ __forceinline__ void fc_rollout_body(const SolveArgs& a, const FcArgs
   const int groups_per_solve = a.Kp >> 4;
   const int total_groups = a.B * groups_per_solve;
   // a group past the end still runs the loop (barriers are block-wide) on a clamped copy and writes nothing.  NS = 2:
-  // launch_t requires groups_per_solve % 2 == 0, so both tiles are live and belong to solve b.
+  // launch_msplit_t requires groups_per_solve % 2 == 0, so both tiles are live and belong to solve b.
   const bool live = grp < total_groups;
   const int gc = live ? grp : total_groups - 1;
   const int b = gc / groups_per_solve;
@@ -711,115 +711,78 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   extern __shared__ __attribute__((aligned(16))) char lds[];
   fc_rollout_body<ARCH, MPPI_PREC_BF16X3, COST, true, 2, L1T>(a, net, lds);
 }
-int fc_x3_tiles();  // MPPI_X3_TILES=1/2: split-bf16 sample tiles per wave (read per launch; default 2); kernels_fc.hip
 
-bool fc_f32_stream();  // MPPI_F32_STREAM=1: the streamed fp32 kernel (A/B); kernels_fc.hip
-#ifdef MPPI_AB_ARMS  // the A/B-only library (csrc/ab/, MPPI_AB_ARMS=1 build.py); not in the shipped libmppi_hip.so
-int fc_wide();         // MPPI_FC_WIDE=0/1: bf16 with two sample tiles per wave (fc_rollout_kernel_wide); kernels_fc.hip
-// the wide kernel's launch (its own translation unit and codegen flags, build.py PER_FILE_FLAGS); ab/kernels_fc_wide.hip
-hipError_t launch_fc_wide(int arch, int cost, const SolveArgs& a, FcArgs fa, int img_lds, hipStream_t stream);
-#endif
+// ------------------------------------------------------------------------------------------------ launch
+// Which kernel runs is fc_route's decision (fc_route.h); every launcher below takes the route, validates what it
+// must, sizes the grid and launches.
 
-template <int ARCH, int PREC, int COST>
-static hipError_t launch_t(const SolveArgs& a, FcArgs fa, int img_lds, hipStream_t stream) {
-  using L = Lay<ARCH, PREC, COST>;
-  const int total_groups = a.B * (a.Kp >> 4);
-  if constexpr (PREC == MPPI_PREC_BF16X3) {  // 4 waves per block, one wave per SIMD; 1 or 2 sample tiles per wave
-    fa.groups_per_block = 1;
-    const bool wide = fc_x3_tiles() == 2 && (a.Kp >> 4) % 2 == 0;
-    const bool two = ARCH == kArchCA && x3_l1_terms(a.H, fa.x3_l1) == 2;  // (the MLP keeps three products: fc_common.h)
-    auto kern = wide ? (two ? fc_rollout_kernel_x3w<ARCH, COST, 2> : fc_rollout_kernel_x3w<ARCH, COST, 3>)
-                     : (two ? fc_rollout_kernel_x3<ARCH, COST, 2> : fc_rollout_kernel_x3<ARCH, COST, 3>);
-    const int lds = (wide ? 2 : 1) * L::BYTES;
-    note_kernel(wide ? (two ? "fc_rollout_kernel_x3w<l1=2>" : "fc_rollout_kernel_x3w<l1=3>")
-                     : (two ? "fc_rollout_kernel_x3<l1=2>" : "fc_rollout_kernel_x3<l1=3>"));
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(wide ? total_groups / 2 : total_groups), dim3(64 * kSplit), lds, stream, a, fa);
-    return hipGetLastError();
-  }
-  const bool f32_regs = PREC == MPPI_PREC_FP32 && !fc_f32_stream();
-  // bf16 wide: two consecutive groups of one solve per wave, one 4-wave block per CU (kernels_fc_wide.hip); only when
-  // the halved grid still covers every CU (config #3's 128 groups keep one group per block)
-#ifdef MPPI_AB_ARMS
-  if (PREC == MPPI_PREC_BF16 && fc_wide() && (a.Kp >> 4) % 2 == 0 && total_groups >= 2 * 256)
-    return launch_fc_wide(ARCH, COST, a, fa, img_lds, stream);
-#endif
-  // bf16 and fp32-in-registers: one group per block (bf16: two blocks per CU, each with its own barriers; fp32: one
-  // wave per SIMD); the streamed fp32 path: two groups per block when that still spreads the groups over all CUs
-  const int gpb = (PREC == MPPI_PREC_FP32 && !f32_regs && total_groups >= 2 * 256 &&
-                   img_lds + 2 * L::BYTES <= 160 * 1024) ? 2 : 1;
-  fa.groups_per_block = gpb;
-  const int grid = (total_groups + gpb - 1) / gpb;
-  const size_t lds = (size_t)img_lds + (size_t)gpb * L::BYTES;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  auto kern = f32_regs ? fc_rollout_kernel_f32<ARCH, COST>
-                      : fc_rollout_kernel<ARCH, PREC == MPPI_PREC_BF16X3 ? MPPI_PREC_BF16 : PREC, COST>;
-  note_kernel(f32_regs ? "fc_rollout_kernel_f32" : (PREC == MPPI_PREC_FP32 ? "fc_rollout_kernel<fp32>" : "fc_rollout_kernel"));
-  // > 64 KiB of dynamic LDS must be opted into per kernel (gfx950 has 160 KiB per CU).
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kSplit * gpb), lds, stream, a, fa);
-  return hipGetLastError();
-}
-
+// The M-split kernels above for one (arch, cost): route.kernel = msplit / msplit_f32 / msplit_x3 / msplit_x3w.  One
+// group per block (bf16: two blocks per CU, each with its own barriers; fp32 in registers and split bf16: one wave per
+// SIMD, split bf16 with one or two sample tiles per wave); the streamed fp32 path: two groups per block when that
+// still spreads the groups over all CUs.
 template <int ARCH, int COST>
-static hipError_t launch_prec(const SolveArgs& a, const FcArgs& fa, int precision, hipStream_t s) {
-  if (precision == MPPI_PREC_BF16) return launch_t<ARCH, MPPI_PREC_BF16, COST>(a, fa, fa.lds_bytes, s);
-  if (precision == MPPI_PREC_BF16X3) return launch_t<ARCH, MPPI_PREC_BF16X3, COST>(a, fa, 0, s);
-  return launch_t<ARCH, MPPI_PREC_FP32, COST>(a, fa, 0, s);
-}
-
-template <int ARCH>
-static hipError_t launch_cost(const SolveArgs& a, const FcArgs& fa, int precision, hipStream_t s) {
-  switch (a.cost_kind) {
-    case MPPI_COST_HUMANOID_V3: return launch_prec<ARCH, MPPI_COST_HUMANOID_V3>(a, fa, precision, s);
-    case MPPI_COST_HUMANOID_V1: return launch_prec<ARCH, MPPI_COST_HUMANOID_V1>(a, fa, precision, s);
-    case MPPI_COST_QUAD_JL: return launch_prec<ARCH, MPPI_COST_QUAD_JL>(a, fa, precision, s);
-    case MPPI_COST_QUAD_EST: return launch_prec<ARCH, MPPI_COST_QUAD_EST>(a, fa, precision, s);
-    case MPPI_COST_CARTPOLE_EST: return launch_prec<ARCH, MPPI_COST_CARTPOLE_EST>(a, fa, precision, s);
-    case MPPI_COST_CARTPOLE: return launch_prec<ARCH, MPPI_COST_CARTPOLE>(a, fa, precision, s);
+static hipError_t launch_msplit_t(const SolveArgs& a, FcArgs fa, const FcRoute& r, hipStream_t stream) {
+  constexpr int kBlock = 64 * kSplit;
+  const int total_groups = a.B * (a.Kp >> 4);
+  fa.groups_per_block = 1;
+  switch (r.kernel) {
+    case FcKernel::msplit_x3: {
+      constexpr int lds = Lay<ARCH, MPPI_PREC_BF16X3, COST>::BYTES;
+      return r.form == 2 ? fc_launch(fc_rollout_kernel_x3<ARCH, COST, 2>, total_groups, kBlock, lds, stream, a, fa)
+                         : fc_launch(fc_rollout_kernel_x3<ARCH, COST, 3>, total_groups, kBlock, lds, stream, a, fa);
+    }
+    case FcKernel::msplit_x3w: {
+      constexpr int lds = 2 * Lay<ARCH, MPPI_PREC_BF16X3, COST>::BYTES;
+      if ((a.Kp >> 4) % 2 != 0) return hipErrorInvalidValue;  // both tiles of a wave in one solve
+      return r.form == 2 ? fc_launch(fc_rollout_kernel_x3w<ARCH, COST, 2>, total_groups / 2, kBlock, lds, stream, a, fa)
+                         : fc_launch(fc_rollout_kernel_x3w<ARCH, COST, 3>, total_groups / 2, kBlock, lds, stream, a, fa);
+    }
+    case FcKernel::msplit_f32:
+      return fc_launch(fc_rollout_kernel_f32<ARCH, COST>, total_groups, kBlock, Lay<ARCH, MPPI_PREC_FP32, COST>::BYTES,
+                       stream, a, fa);
+    case FcKernel::msplit: {
+      if (r.form == MPPI_PREC_FP32) {  // streamed fp32
+        constexpr int bytes = Lay<ARCH, MPPI_PREC_FP32, COST>::BYTES;
+        const int gpb = total_groups >= 2 * 256 && 2 * bytes <= 160 * 1024 ? 2 : 1;
+        fa.groups_per_block = gpb;
+        return fc_launch(fc_rollout_kernel<ARCH, MPPI_PREC_FP32, COST>, (total_groups + gpb - 1) / gpb, kBlock * gpb,
+                         (size_t)gpb * bytes, stream, a, fa);
+      }
+      return fc_launch(fc_rollout_kernel<ARCH, MPPI_PREC_BF16, COST>, total_groups, kBlock,
+                       (size_t)fa.lds_bytes + Lay<ARCH, MPPI_PREC_BF16, COST>::BYTES, stream, a, fa);
+    }
     default: return hipErrorInvalidValue;
   }
 }
+// kernels_fc.hip (MLP, every cost) / kernels_fc_ca.hip (CA, the humanoid's costs): each arch's instantiations in its own
+// translation unit, with its own codegen flags (build.py PER_FILE_FLAGS)
+hipError_t launch_fc_msplit_mlp(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
+hipError_t launch_fc_msplit_ca(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
 
-#ifdef MPPI_AB_ARMS  // ab/kernels_fc_pipe.hip: the layer-pipelined CA rollout (an A/B arm: MPPI_FC_PIPE=1 forces it)
-bool fc_pipe_wanted(const SolveArgs& a);
-hipError_t launch_fc_pipe(const SolveArgs& a, FcArgs fa, hipStream_t stream);
+#ifdef MPPI_AB_ARMS  // the A/B-only library (csrc/ab/, MPPI_AB_ARMS=1 build.py); not in the shipped libmppi_hip.so
+// ab/kernels_fc_wide.hip: bf16 with two sample tiles per wave (fc_rollout_kernel_wide above)
+hipError_t launch_fc_wide(int arch, const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
+// ab/kernels_fc_pipe.hip: the layer-pipelined CA rollout
+hipError_t launch_fc_pipe(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
 #endif
 
-// kernels_fc_wave.hip: the per-wave CA rollout (weights in LDS, every layer of NS sample tiles in one wave; batches
-// with >= 2 tile pairs per wave slot; MPPI_FC_WAVE=0/1/2 forces); fc_wave_ns: 0 = not this kernel, else NS
-int fc_wave_ns(const SolveArgs& a, const FcArgs& fa);
-hipError_t launch_fc_wave(const SolveArgs& a, const FcArgs& fa, int ns, hipStream_t stream);
-// ... and its MLP (hidden 128 x 2) counterpart (MPPI_FC_WAVE=0/1/2 forces it too)
-int fc_wave_mlp_ns(const SolveArgs& a, const FcArgs& fa);
-hipError_t launch_fc_wave_mlp(const SolveArgs& a, const FcArgs& fa, int ns, hipStream_t stream);
-// ... and the split-bf16 per-wave CA rollout (fc_wave32_x3_kernel; batches with >= 4 wave-tiles of 32 per CU;
-// MPPI_X3_WAVE=0 keeps the M-split split-bf16 kernels)
-bool fc_wave_x3_wanted(const SolveArgs& a, const FcArgs& fa);
-hipError_t launch_fc_wave_x3(const SolveArgs& a, const FcArgs& fa, hipStream_t stream);
-// kernels_fc_x3m.hip: the split per-wave MLP rollout (MPPI_X3M=0/1 forces it off / on; default by batch size)
-bool fc_wave_mlp_x3_wanted(const SolveArgs& a, const FcArgs& fa);
-hipError_t launch_fc_wave_mlp_x3(const SolveArgs& a, const FcArgs& fa, hipStream_t stream);
-// kernels_fc_x3mp.hip: the same at 32 samples per wave on 32x32x16 MFMAs (MPPI_X3M32=0/1; default by batch size)
-bool fc_wave32_mlp_x3_wanted(const SolveArgs& a, const FcArgs& fa);
-hipError_t launch_fc_wave32_mlp_x3(const SolveArgs& a, const FcArgs& fa, hipStream_t stream);
-hipError_t launch_fc_wave_x3p(const SolveArgs& a, const FcArgs& fa, hipStream_t stream);  // two waves per SIMD
+// kernels_fc_wave.hip: the bf16 per-wave rollouts (weights in LDS, every layer of NS sample tiles in one wave): the CA's
+// (route.kernel = wave with NS = route.ns, or wave32) and its MLP (hidden 128 x 2) counterpart
+hipError_t launch_fc_wave(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
+hipError_t launch_fc_wave_mlp(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
+// kernels_fc_x3.hip / kernels_fc_x3p.hip: the split-bf16 per-wave CA rollout at one / two waves per SIMD
+hipError_t launch_fc_wave_x3(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
+hipError_t launch_fc_wave_x3p(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
+// kernels_fc_x3m.hip / kernels_fc_x3mp.hip: the split per-wave MLP rollout at 16 / 32 samples per wave
+hipError_t launch_fc_wave_mlp_x3(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
+hipError_t launch_fc_wave32_mlp_x3(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
 // kernels_fc_x3d.hip: the split M-split CA rollout with two groups per block at two waves per SIMD (the few-tiles
-// shards; MPPI_X3D=0 keeps fc_rollout_kernel_x3w)
-bool fc_x3d_wanted(const SolveArgs& a, const FcArgs& fa);
-hipError_t launch_fc_x3d(const SolveArgs& a, const FcArgs& fa, hipStream_t stream);
-// kernels_fc_x3h.hip: its fp16 form at one group per block, two blocks per CU (MPPI_X3H=0 keeps x3d)
-bool fc_x3h_wanted(const SolveArgs& a, const FcArgs& fa);
-hipError_t launch_fc_x3h(const SolveArgs& a, const FcArgs& fa, hipStream_t stream);
+// shards); kernels_fc_x3h.hip: its fp16 form at one group per block, two blocks per CU
+hipError_t launch_fc_x3d(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
+hipError_t launch_fc_x3h(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream);
 
-// kernels_fc_ca.hip
-hipError_t launch_fc_ca(const SolveArgs& a, const FcArgs& fa, int precision, hipStream_t stream);
 #ifdef MPPI_STAMPS
-int fc_ca_stamps(unsigned long long* out, int reset);
+int fc_ca_stamps(unsigned long long* out, int reset);  // kernels_fc_ca.hip
 #endif
 
 }  // namespace mppi

@@ -3,7 +3,6 @@
 #include "fc_rollout.h"
 
 #include <atomic>
-#include <cstdlib>
 
 namespace mppi {
 
@@ -23,83 +22,47 @@ int current_device_cus() {
   return n;
 }
 
-bool fc_f32_stream() {
-  static const bool on = [] {
-    const char* e = std::getenv("MPPI_F32_STREAM");
-    return e && e[0] == '1';
-  }();
-  return on;
+hipError_t launch_fc_msplit_mlp(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream) {
+  return by_cost(a.cost_kind, [&](auto cost) {
+    return launch_msplit_t<kArchMLP, decltype(cost)::value>(a, fa, r, stream);
+  });
 }
-
-int fc_x3_tiles() {
-  const char* e = std::getenv("MPPI_X3_TILES");
-  return e ? std::atoi(e) : 2;
-}
-
-#ifdef MPPI_AB_ARMS
-int fc_wide() {
-  static const int on = [] {
-    const char* e = std::getenv("MPPI_FC_WIDE");
-    return e ? (e[0] == '1' ? 1 : 0) : 0;
-  }();
-  return on;
-}
-#endif
 
 hipError_t launch_fc_rollout(const SolveArgs& a, const FcNet& n, hipStream_t stream) {
-  if (n.arch == kArchGeneric) return launch_fc_generic(a, n, stream);  // any other fc-stack shape
-  FcArgs fa;
-  fa.img = reinterpret_cast<const char*>(n.d_img);
-  fa.img_bytes = n.img_bytes;
-  fa.lds_bytes = n.lds_bytes;
-  for (int i = 0; i < 4; ++i) {
-    fa.w_off[i] = n.w_off[i];
-    fa.b_off[i] = n.b_off[i];
-  }
-  fa.lnb_off = n.lnb_off;
-  fa.ln_n = n.ln_n;
-  fa.qp = n.qp;
-  fa.qv = n.qv;
-  fa.groups_per_block = 1;
-  fa.g_off = n.g_off;
-  fa.wave = n.wave;
-  fa.w32_off = n.w32_off;
-  fa.w32_bd = n.w32_bd;
-  fa.w0bd_off = n.w0bd_off;
-  fa.gbd_off = n.gbd_off;
-  fa.w32x3_off = n.w32x3_off;
-  fa.w32x3_l1lo_off = n.w32x3_l1lo_off;
-  fa.wmx3_off = n.wmx3_off;
-  fa.wmx3_lo_off = n.wmx3_lo_off;
-  fa.wm32x3_off = n.wm32x3_off;
-  fa.wm32x3_lo_off = n.wm32x3_lo_off;
-  fa.x3_l1 = n.x3_l1;
-  fa.w32f16_off = n.w32f16_off;
-  fa.wmf16_off = n.wmf16_off;
-  fa.wmf16_x_off = n.wmf16_x_off;
-  fa.wmf16_0_off = n.wmf16_0_off;
-  fa.wmf16_0b_off = n.wmf16_0b_off;
-  fa.x3_f16 = n.x3_f16;
-  fa.x3_route = n.x3_route;
-  if (n.arch == kArchCA) {
-    // the CA kernel is built for the humanoid (qpos 28) with its two costs
-    if (a.cost_kind != MPPI_COST_HUMANOID_V3 && a.cost_kind != MPPI_COST_HUMANOID_V1) return hipErrorInvalidValue;
-    return launch_fc_ca(a, fa, n.precision, stream);
-  }
-  if (n.arch == kArchMLP) {
-    if (n.precision == MPPI_PREC_BF16 && n.wave && fa.lds_bytes == 0) {  // large batches: the per-wave kernel
-      const int ns = fc_wave_mlp_ns(a, fa);
-      if (ns) return launch_fc_wave_mlp(a, fa, ns, stream);
-    }
-    if (n.precision == MPPI_PREC_BF16X3 && fc_wave32_mlp_x3_wanted(a, fa))  // the split per-wave kernels
-      return launch_fc_wave32_mlp_x3(a, fa, stream);
-    if (n.precision == MPPI_PREC_BF16X3 && fc_wave_mlp_x3_wanted(a, fa))
-      return launch_fc_wave_mlp_x3(a, fa, stream);
-    return launch_cost<kArchMLP>(a, fa, n.precision, stream);
-  }
-  return hipErrorInvalidValue;
+  if (n.arch != kArchCA && n.arch != kArchMLP && n.arch != kArchGeneric) return hipErrorInvalidValue;
+  const FcRoute r = fc_route(n.arch, n.precision, a, n.fa, n.x3_l1, n.x3_f16, current_device_cus(), fc_knobs_from_env());
+  return launch_fc_route(a, n, r, stream);
 }
 
+hipError_t launch_fc_route(const SolveArgs& a, const FcNet& n, const FcRoute& r, hipStream_t stream) {
+  note_kernel(fc_route_name(r));
+  if (r.kernel == FcKernel::generic) return n.arch == kArchGeneric ? launch_fc_generic(a, n, stream) : hipErrorInvalidValue;
+  const bool ca = n.arch == kArchCA, mlp = n.arch == kArchMLP;
+  // the CA kernels are built for the humanoid (qpos 28) with its two costs
+  if (ca && a.cost_kind != MPPI_COST_HUMANOID_V3 && a.cost_kind != MPPI_COST_HUMANOID_V1) return hipErrorInvalidValue;
+  const FcArgs& fa = n.fa;
+  if ((!ca && !mlp) || !fc_route_can_run(r.kernel, a, fa)) return hipErrorInvalidValue;
+  switch (r.kernel) {
+    case FcKernel::msplit:
+    case FcKernel::msplit_f32:
+    case FcKernel::msplit_x3:
+    case FcKernel::msplit_x3w: return ca ? launch_fc_msplit_ca(a, fa, r, stream) : launch_fc_msplit_mlp(a, fa, r, stream);
+    case FcKernel::wave:
+    case FcKernel::wave32: return ca ? launch_fc_wave(a, fa, r, stream) : hipErrorInvalidValue;
+    case FcKernel::wave_mlp: return mlp ? launch_fc_wave_mlp(a, fa, r, stream) : hipErrorInvalidValue;
+    case FcKernel::x3_wave32: return ca ? launch_fc_wave_x3(a, fa, r, stream) : hipErrorInvalidValue;
+    case FcKernel::x3p: return ca ? launch_fc_wave_x3p(a, fa, r, stream) : hipErrorInvalidValue;
+    case FcKernel::x3d: return ca ? launch_fc_x3d(a, fa, r, stream) : hipErrorInvalidValue;
+    case FcKernel::x3h: return ca ? launch_fc_x3h(a, fa, r, stream) : hipErrorInvalidValue;
+    case FcKernel::x3m: return mlp ? launch_fc_wave_mlp_x3(a, fa, r, stream) : hipErrorInvalidValue;
+    case FcKernel::x3mp: return mlp ? launch_fc_wave32_mlp_x3(a, fa, r, stream) : hipErrorInvalidValue;
+#ifdef MPPI_AB_ARMS
+    case FcKernel::pipe: return ca ? launch_fc_pipe(a, fa, r, stream) : hipErrorInvalidValue;
+    case FcKernel::wide: return launch_fc_wide(n.arch, a, fa, r, stream);
+#endif
+    default: return hipErrorInvalidValue;
+  }
+}
 
 #ifdef MPPI_STAMPS
 extern "C" int mppi_debug_stamps(unsigned long long* out, int reset) {  // both fc translation units' sums

@@ -23,8 +23,6 @@
 // tile's step over 4 SIMDs.
 #include "fc_rollout.h"
 
-#include <cstdlib>
-
 namespace mppi {
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -1284,120 +1282,49 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   kclock_record(a, kc);
 }
 
-// MPPI_FC_WAVE: 0 never, 1 / 2 always with NS = 1 / 2 sample tiles per wave, 3 the 32x32x16 variant (read per launch,
-// so a test can switch it); unset: by 16-sample tiles per CU, from a same-box sweep over config #4 batches (scripts/gpu_sweep_wave.sh,
-// DESIGN.md §4): NS = 2 from 12 tiles per CU (48 solves and up), NS = 1 from 6 (24, 32 solves), below that the
-// M-split kernel (16 solves: 153 us vs 185 us for NS = 1), which spreads one tile's step over 4 SIMDs
-static int fc_wave_mode() {
-  const char* e = std::getenv("MPPI_FC_WAVE");
-  return e ? std::atoi(e) : -1;
-}
-
-static int wave_device_cus() { return current_device_cus(); }
-
-int fc_wave_ns(const SolveArgs& a, const FcArgs& fa) {
-  // a wave owns 32 samples of one solve (NS = 2, 32x32): only for Kp a multiple of 32.  The env-step launch (Kp = 16,
-  // one sample) always takes the M-split kernel, also when MPPI_FC_WAVE forces these kernels.
-  if (fa.g_off < 0 || fa.ln_n != 256 || a.Kp < 32 || a.Kp % 32 != 0) return 0;
-  const int mode = fc_wave_mode();
-  if (mode == 0) return 0;
-  if (mode == 1 || mode == 2) return mode;
-  const bool w32 = fa.w32_off >= 0 && a.nu >= 20 && a.nu <= 22;  // the 32x32x16 variant (fc_wave32_kernel)
-  if (mode == 3) return w32 ? 3 : 2;
-  const int tiles = a.B * (a.Kp >> 4), cus = wave_device_cus();
-  // two tiles per wave: the 32x32x16 variant where it applies (two boxes, config #4 64 solves: 384.7-389.8 ->
-  // 365.9-370.5 us; 378.5/378.8 -> 371.1/366.5 us)
-  return tiles >= 12 * cus ? (w32 ? 3 : 2) : (tiles >= 6 * cus ? 1 : 0);
-}
-
-hipError_t launch_fc_wave(const SolveArgs& a, const FcArgs& fa, int ns, hipStream_t stream) {
-  if (a.Kp <= 0 || a.Kp % (ns == 3 ? 32 : 16 * ns) != 0) return hipErrorInvalidValue;  // whole wave-tiles only
-  if (ns == 3) {  // the 32x32x16 variant (32 samples per wave)
-    if (fa.w32_off < 0 || a.nu < 20 || a.nu > 22) return hipErrorInvalidValue;
-    const int wts = a.B * (a.Kp / 32);
-    int grid = (wts + WaveLay::WAVES - 1) / WaveLay::WAVES;
-    if (grid > wave_device_cus()) grid = wave_device_cus();
-    auto go32 = [&](auto kern, int bytes) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WaveLay::WAVES), bytes, stream, a, fa);
-      return hipGetLastError();
-    };
-    const int b1 = WaveLay::bytes<MPPI_COST_HUMANOID_V1>(), b3 = WaveLay::bytes<MPPI_COST_HUMANOID_V3>();
-    note_kernel("fc_wave32_kernel");
-    if (a.cost_kind == MPPI_COST_HUMANOID_V1)
-      return fa.w32_bd == 2   ? go32(fc_wave32_kernel<MPPI_COST_HUMANOID_V1, 2>, b1)
-             : fa.w32_bd == 1 ? go32(fc_wave32_kernel<MPPI_COST_HUMANOID_V1, 1>, b1)
-                              : go32(fc_wave32_kernel<MPPI_COST_HUMANOID_V1, 0>, b1);
-    return fa.w32_bd == 2   ? go32(fc_wave32_kernel<MPPI_COST_HUMANOID_V3, 2>, b3)
-           : fa.w32_bd == 1 ? go32(fc_wave32_kernel<MPPI_COST_HUMANOID_V3, 1>, b3)
-                            : go32(fc_wave32_kernel<MPPI_COST_HUMANOID_V3, 0>, b3);
-  }
+// Routed by fc_route (fc_route.h) by 16-sample tiles per CU, from a same-box sweep over config #4 batches
+// (scripts/gpu_sweep_wave.sh): NS = 2 from 12 tiles per CU (48 solves and up), NS = 1 from 6 (24, 32
+// solves), below that the M-split kernel (16 solves: 153 us vs 185 us for NS = 1), which spreads one tile's step over 4
+// SIMDs.  Two tiles per wave: the 32x32x16 variant where it applies (two boxes, config #4 64 solves: 384.7-389.8 ->
+// 365.9-370.5 us; 378.5/378.8 -> 371.1/366.5 us).
+hipError_t launch_fc_wave(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream) {
+  const bool w32 = r.kernel == FcKernel::wave32;  // the 32x32x16 variant (32 samples per wave)
+  const int ns = w32 ? 2 : r.ns;
+  if ((ns != 1 && ns != 2) || a.Kp <= 0 || a.Kp % (16 * ns) != 0) return hipErrorInvalidValue;  // whole wave-tiles only
   const int wts = a.B * (a.Kp / (16 * ns));
-  const int cus = wave_device_cus();
   int grid = (wts + WaveLay::WAVES - 1) / WaveLay::WAVES;
-  if (grid > cus) grid = cus;  // persistent: a wave takes wave-tiles wt, wt + 8 grid, ...
-  const bool bd = fa.w32_bd == 2 && fa.w0bd_off >= 0 && fa.gbd_off >= 0;  // the block-diagonal layer 0 (form 2)
-  auto go = [&](auto kern, int bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WaveLay::WAVES), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
-  constexpr int V1 = MPPI_COST_HUMANOID_V1, V3 = MPPI_COST_HUMANOID_V3;
-  static_assert(WaveLay::bytes<V3>() <= 160 * 1024 && WaveLay::bytes<V1>() <= 160 * 1024, "LDS per CU");
-  note_kernel(ns == 1 ? "fc_wave_kernel<ns=1>" : "fc_wave_kernel<ns=2>");
-  if (a.cost_kind == V1)
-    return bd ? (ns == 1 ? go(fc_wave_kernel<V1, 1, 2>, WaveLay::bytes<V1>()) : go(fc_wave_kernel<V1, 2, 2>, WaveLay::bytes<V1>()))
-              : (ns == 1 ? go(fc_wave_kernel<V1, 1, 0>, WaveLay::bytes<V1>()) : go(fc_wave_kernel<V1, 2, 0>, WaveLay::bytes<V1>()));
-  return bd ? (ns == 1 ? go(fc_wave_kernel<V3, 1, 2>, WaveLay::bytes<V3>()) : go(fc_wave_kernel<V3, 2, 2>, WaveLay::bytes<V3>()))
-            : (ns == 1 ? go(fc_wave_kernel<V3, 1, 0>, WaveLay::bytes<V3>()) : go(fc_wave_kernel<V3, 2, 0>, WaveLay::bytes<V3>()));
+  if (grid > current_device_cus()) grid = current_device_cus();  // persistent: a wave takes wave-tiles wt, wt + 8 grid, ...
+  constexpr int kBlock = 64 * WaveLay::WAVES;
+  return by_humanoid_cost(a.cost_kind, [&](auto cost) {
+    constexpr int C = decltype(cost)::value;
+    constexpr int bytes = WaveLay::bytes<C>();
+    static_assert(bytes <= 160 * 1024, "LDS per CU");
+    if (w32)
+      return fa.w32_bd == 2   ? fc_launch(fc_wave32_kernel<C, 2>, grid, kBlock, bytes, stream, a, fa)
+             : fa.w32_bd == 1 ? fc_launch(fc_wave32_kernel<C, 1>, grid, kBlock, bytes, stream, a, fa)
+                              : fc_launch(fc_wave32_kernel<C, 0>, grid, kBlock, bytes, stream, a, fa);
+    const bool bd = fa.w32_bd == 2 && fa.w0bd_off >= 0 && fa.gbd_off >= 0;  // the block-diagonal layer 0 (form 2)
+    return bd ? (ns == 1 ? fc_launch(fc_wave_kernel<C, 1, 2>, grid, kBlock, bytes, stream, a, fa)
+                         : fc_launch(fc_wave_kernel<C, 2, 2>, grid, kBlock, bytes, stream, a, fa))
+              : (ns == 1 ? fc_launch(fc_wave_kernel<C, 1, 0>, grid, kBlock, bytes, stream, a, fa)
+                         : fc_launch(fc_wave_kernel<C, 2, 0>, grid, kBlock, bytes, stream, a, fa));
+  });
 }
 
-}  // namespace mppi
-
-namespace mppi {
-
-// MLP: the same rule as the CA kernel (fc_wave_ns), to be confirmed by its own sweep
-int fc_wave_mlp_ns(const SolveArgs& a, const FcArgs& fa) {
-  if (!fa.wave || a.nx > kMlpBiasSlotHi || a.nu > 32 || a.Kp < 32 || a.Kp % 32 != 0) return 0;  // as fc_wave_ns
-  const int mode = fc_wave_mode();
-  if (mode == 0) return 0;
-  if (mode == 1 || mode == 2) return mode;
-  const int tiles = a.B * (a.Kp >> 4), cus = wave_device_cus();
-  return tiles >= 12 * cus ? 2 : (tiles >= 6 * cus ? 1 : 0);
-}
-
-hipError_t launch_fc_wave_mlp(const SolveArgs& a, const FcArgs& fa, int ns, hipStream_t stream) {
-  if (a.Kp <= 0 || a.Kp % (16 * ns) != 0) return hipErrorInvalidValue;  // whole wave-tiles only
+// MLP: routed by the same rule as the CA kernel, to be confirmed by its own sweep
+hipError_t launch_fc_wave_mlp(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream) {
+  const int ns = r.ns;
+  if ((ns != 1 && ns != 2) || a.Kp <= 0 || a.Kp % (16 * ns) != 0) return hipErrorInvalidValue;  // whole wave-tiles only
   const int wts = a.B * (a.Kp / (16 * ns));
   int grid = (wts + WaveMlpLay::WAVES - 1) / WaveMlpLay::WAVES;
-  if (grid > wave_device_cus()) grid = wave_device_cus();
-  auto go = [&](auto kern, int bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WaveMlpLay::WAVES), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
-  note_kernel(ns == 1 ? "fc_wave_mlp_kernel<ns=1>" : "fc_wave_mlp_kernel<ns=2>");
-#define MPPI_WAVE_MLP_COST(K)                                                                       \
-  case K:                                                                                           \
-    static_assert(WaveMlpLay::bytes<K>() <= 160 * 1024, "LDS per CU");                              \
-    return ns == 1 ? go(fc_wave_mlp_kernel<K, 1>, WaveMlpLay::bytes<K>())                           \
-                   : go(fc_wave_mlp_kernel<K, 2>, WaveMlpLay::bytes<K>());
-  switch (a.cost_kind) {
-    MPPI_WAVE_MLP_COST(MPPI_COST_HUMANOID_V3)
-    MPPI_WAVE_MLP_COST(MPPI_COST_HUMANOID_V1)
-    MPPI_WAVE_MLP_COST(MPPI_COST_QUAD_EST)
-    MPPI_WAVE_MLP_COST(MPPI_COST_QUAD_JL)
-    MPPI_WAVE_MLP_COST(MPPI_COST_CARTPOLE_EST)
-    MPPI_WAVE_MLP_COST(MPPI_COST_CARTPOLE)
-    default: return hipErrorInvalidValue;
-  }
-#undef MPPI_WAVE_MLP_COST
+  if (grid > current_device_cus()) grid = current_device_cus();
+  return by_cost(a.cost_kind, [&](auto cost) {
+    constexpr int C = decltype(cost)::value;
+    constexpr int bytes = WaveMlpLay::bytes<C>(), kBlock = 64 * WaveMlpLay::WAVES;
+    static_assert(bytes <= 160 * 1024, "LDS per CU");
+    return ns == 1 ? fc_launch(fc_wave_mlp_kernel<C, 1>, grid, kBlock, bytes, stream, a, fa)
+                   : fc_launch(fc_wave_mlp_kernel<C, 2>, grid, kBlock, bytes, stream, a, fa);
+  });
 }
 
 }  // namespace mppi

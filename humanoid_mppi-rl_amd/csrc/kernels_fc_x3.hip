@@ -3,7 +3,6 @@
 // AGPRs (build.py: no -amdgpu-mfma-vgpr-form here): a lone wave per SIMD has the whole 512-entry register file, and
 // with the accumulators in AccVGPRs the 256 ArchVGPRs hold the hi / lo activations and the fragments in flight
 // (config #4 at 64 solves, same box: 1501 -> 977 us per rollout; profiles/r04_ab_x3_agpr.log).
-#include <cstdlib>
 
 #include "x3_common.h"
 
@@ -357,60 +356,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   kclock_record(a, kc);
 }
 
-// MPPI_X3_PAIR (read per launch): unset = two waves per SIMD (kernels_fc_x3p.hip) once the wave-tiles exceed one per
-// SIMD, 0 = never, 1 = always.  At <= 4 tiles per CU the pair kernel would run them on half the CUs (8 per block).
-static bool x3_pair_on(int wts) {
-  const char* e = std::getenv("MPPI_X3_PAIR");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  return wts > WaveX3Lay::WAVES * x3_device_cus();
-}
-
-// MPPI_X3_WAVE (read per launch): 0 = split bf16 always on the M-split kernels, 2 = always on the per-wave kernels
-static int x3_wave_mode() {
-  const char* e = std::getenv("MPPI_X3_WAVE");
-  return e && e[0] == '0' ? 0 : (e && e[0] == '2' ? 2 : 1);
-}
-
-bool fc_wave_x3_wanted(const SolveArgs& a, const FcArgs& fa) {
-  // whole 32-sample wave-tiles, the humanoid controls, and enough of them for every CU's 4 waves
-  if (fa.w32x3_off < 0 || fa.ln_n != 256 || a.Kp < 32 || a.Kp % 32 != 0 || a.nu < 20 || a.nu > 22) return false;
-  const int mode = x3_wave_mode();
-  if (mode != 1) return mode == 2;
-  return a.B * (a.Kp / 32) >= WaveX3Lay::WAVES * x3_device_cus();
-}
-
-hipError_t launch_fc_wave_x3(const SolveArgs& a, const FcArgs& fa, hipStream_t stream) {
-  if (fa.w32x3_off < 0 || a.Kp <= 0 || a.Kp % 32 != 0 || a.nu < 20 || a.nu > 22) return hipErrorInvalidValue;
+// Routed by fc_route (fc_route.h) from 4 wave-tiles of 32 per CU; past that, two waves per SIMD (kernels_fc_x3p.hip):
+// at <= 4 tiles per CU the pair kernel would run them on half the CUs (8 per block).
+hipError_t launch_fc_wave_x3(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream) {
   const int wts = a.B * (a.Kp / 32);
   int grid = (wts + WaveX3Lay::WAVES - 1) / WaveX3Lay::WAVES;
-  if (grid > x3_device_cus()) grid = x3_device_cus();
-  auto go = [&](auto kern, int bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WaveX3Lay::WAVES), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
-  if (x3_pair_on(wts)) return launch_fc_wave_x3p(a, fa, stream);  // two waves per SIMD (kernels_fc_x3p.hip)
-  const int form = x3_form(a.H, fa.x3_l1, fa.x3_f16, fa.w32f16_off);
-  static const char* const names[4] = {
-      MPPI_X3_F16_L0 ? "fc_wave32_x3_kernel<f16,l2=1>" : "fc_wave32_x3_kernel<l1=f16,l2=1>",
-      MPPI_X3_F16_L0 ? "fc_wave32_x3_kernel<f16>" : "fc_wave32_x3_kernel<l1=f16>", "fc_wave32_x3_kernel<l1=2>",
-      "fc_wave32_x3_kernel<l1=3>"};
-  note_kernel(names[form]);
-  auto by_form = [&](auto cost) {
+  if (grid > current_device_cus()) grid = current_device_cus();
+  return by_humanoid_cost(a.cost_kind, [&](auto cost) {
     constexpr int C = decltype(cost)::value;
-    constexpr int bytes = WaveX3Lay::bytes<C>();
-    switch (form) {
-      case 0: return go(fc_wave32_x3_kernel<C, 0>, bytes);
-      case 1: return go(fc_wave32_x3_kernel<C, 1>, bytes);
-      case 2: return go(fc_wave32_x3_kernel<C, 2>, bytes);
-      default: return go(fc_wave32_x3_kernel<C, 3>, bytes);
+    constexpr int bytes = WaveX3Lay::bytes<C>(), kBlock = 64 * WaveX3Lay::WAVES;
+    switch (r.form) {
+      case 0: return fc_launch(fc_wave32_x3_kernel<C, 0>, grid, kBlock, bytes, stream, a, fa);
+      case 1: return fc_launch(fc_wave32_x3_kernel<C, 1>, grid, kBlock, bytes, stream, a, fa);
+      case 2: return fc_launch(fc_wave32_x3_kernel<C, 2>, grid, kBlock, bytes, stream, a, fa);
+      default: return fc_launch(fc_wave32_x3_kernel<C, 3>, grid, kBlock, bytes, stream, a, fa);
     }
-  };
-  if (a.cost_kind == MPPI_COST_HUMANOID_V1) return by_form(std::integral_constant<int, MPPI_COST_HUMANOID_V1>{});
-  return by_form(std::integral_constant<int, MPPI_COST_HUMANOID_V3>{});
+  });
 }
 
 }  // namespace mppi

@@ -409,42 +409,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-// MPPI_X3D (read per launch): unset = this kernel for the split CA with the two-product layer 1 below the per-wave
-// kernels' batch threshold; 0 = never (fc_rollout_kernel_x3w); 1 = always where it applies
-bool fc_x3d_wanted(const SolveArgs& a, const FcArgs& fa) {
-  if (fa.w_off[1] < 0 || fa.ln_n != 256 || a.Kp % 64 != 0) return false;
-  if (x3_l1_terms(a.H, fa.x3_l1) != 2 && !x3_f16_on(a.H, fa.x3_f16, fa.wmf16_off)) return false;
-  const char* e = std::getenv("MPPI_X3D");
-  return !(e && e[0] == '0');
-}
-
-hipError_t launch_fc_x3d(const SolveArgs& a, const FcArgs& fa, hipStream_t stream) {
+// Routed by fc_route (fc_route.h): the split CA with the two-product layer 1 or the fp16 form, below the per-wave
+// kernels' batch threshold.  No three-product form.
+hipError_t launch_fc_x3d(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream) {
   const int groups = a.B * (a.Kp >> 4);
-  if (a.Kp % 64 != 0 || groups < 1) return hipErrorInvalidValue;
+  if (groups < 1 || r.form < 0 || r.form > 2) return hipErrorInvalidValue;
   const int grid = (groups + 1) / 2;
-  auto go = [&](auto kern, int bytes) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
-  const int form = x3_form(a.H, fa.x3_l1, fa.x3_f16, fa.wmf16_off);
-  if (form == 3) return hipErrorInvalidValue;
-  static const char* const names[3] = {
-      MPPI_X3_F16_L0 ? "fc_rollout_kernel_x3d<f16,l2=1>" : "fc_rollout_kernel_x3d<l1=f16,l2=1>",
-      MPPI_X3_F16_L0 ? "fc_rollout_kernel_x3d<f16>" : "fc_rollout_kernel_x3d<l1=f16>", "fc_rollout_kernel_x3d<l1=2>"};
-  note_kernel(names[form]);
-  auto by_form = [&](auto cost) {
+  return by_humanoid_cost(a.cost_kind, [&](auto cost) {
     constexpr int C = decltype(cost)::value;
-    switch (form) {
-      case 0: return go(fc_rollout_kernel_x3d<C, true, true>, X3dLay<C>::BYTES);
-      case 1: return go(fc_rollout_kernel_x3d<C, true>, X3dLay<C>::BYTES);
-      default: return go(fc_rollout_kernel_x3d<C, false>, X3dLay<C>::BYTES);
+    constexpr int bytes = X3dLay<C>::BYTES;
+    switch (r.form) {
+      case 0: return fc_launch(fc_rollout_kernel_x3d<C, true, true>, grid, 512, bytes, stream, a, fa);
+      case 1: return fc_launch(fc_rollout_kernel_x3d<C, true>, grid, 512, bytes, stream, a, fa);
+      default: return fc_launch(fc_rollout_kernel_x3d<C, false>, grid, 512, bytes, stream, a, fa);
     }
-  };
-  if (a.cost_kind == MPPI_COST_HUMANOID_V1) return by_form(std::integral_constant<int, MPPI_COST_HUMANOID_V1>{});
-  return by_form(std::integral_constant<int, MPPI_COST_HUMANOID_V3>{});
+  });
 }
 
 }  // namespace mppi

@@ -15,9 +15,12 @@
 //   * only the LO planes of layers 0 and 2 (48 KiB) in LDS, per block, read by their own wave every step (12 fragments
 //     per wave-step instead of 24);
 //   * the layer-0 bias and beta' in LDS (registers are the limit at two waves per SIMD), an 8-step cost ring.
-// The arithmetic is x3d's fp16 form term for term and in the same order (layer 0: lo then hi per k-step; the last
-// layer: two chains, lo then hi), so the costs equal fc_rollout_kernel_x3d<f16>'s bitwise
-// (tests/test_gpu_fullsize.py test_split_x3d_kernel_matches_x3w_and_oracle).  Its own translation unit (build.py PER_FILE_FLAGS).
+// The arithmetic follows x3d's fp16 form (layer 0: lo then hi per k-step; the last layer: two chains, lo then hi) but
+// does NOT equal fc_rollout_kernel_x3d<f16>'s bitwise: the layer-0 bias enters as an fp16 hi / lo pair through the MFMA
+// (X3H_B0MMA) and the qvel k-step of layer 0 is one product (X3H_L0LO_QV), rounding differences that over 64 steps grow
+// to the size of the fp16 form's own error -- the costs agree within 8e-5, and both are within 1e-4 of the fp32 oracle
+// (tests/test_gpu_fullsize.py test_split_x3d_kernel_matches_x3w_and_oracle).  Its own translation unit (build.py
+// PER_FILE_FLAGS).
 #include "fc_rollout.h"
 
 namespace mppi {
@@ -34,10 +37,9 @@ namespace mppi {
 #ifndef X3H_DIAG
 #define X3H_DIAG 0
 #endif
-#ifndef X3H_B0MMA  // layer 0's bias through the MFMA chain (FcNet::wmf16_0b_off: b0 in the pad column kCaX3hBiasSlot
-                   // against a state slot of 1.0) instead of an accumulator initialised from LDS
-#define X3H_B0MMA 1
-#endif
+// X3H_B0MMA (default 1; fc_route.h, which gates the kernel on the image part it needs): layer 0's bias through the MFMA
+// chain (FcArgs::wmf16_0b_off: b0 in the pad column kCaX3hBiasSlot against a state slot of 1.0) instead of an
+// accumulator initialised from LDS
 #ifndef X3H_BEPRE  // beta' read from LDS before the statistic barrier (its latency under the barrier wait)
 #define X3H_BEPRE 1
 #endif
@@ -543,60 +545,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   fc_x3h_body<COST, L2X1, NS>(a, net, lds);
 }
 
-// MPPI_X3H (read per launch): unset = this kernel wherever fc_rollout_kernel_x3d would run the fp16 form; 0 = never
-// (x3d keeps it); 1 = the same (explicit)
-bool fc_x3h_wanted(const SolveArgs& a, const FcArgs& fa) {
-  if (!MPPI_X3_F16_L0 || fa.w_off[1] < 0 || fa.ln_n != 256 || a.Kp % 16 != 0 || fa.wmf16_0_off < 0) return false;
-  if (X3H_B0MMA && fa.wmf16_0b_off < 0) return false;
-  if (!x3_f16_on(a.H, fa.x3_f16, fa.wmf16_off)) return false;
-  const char* e = std::getenv("MPPI_X3H");
-  return !(e && e[0] == '0');
-}
-
-// tiles per wave: 1 (one group per block, two blocks per CU), or MPPI_X3H_NS=2/4 (read per launch) -- one block per CU
-// at one wave per SIMD, NS static chains per wave: measured slower than the dynamic interleave of two blocks per CU at
-// both shard sizes (same box: 8 solves 104.6 -> 126.5 us with NS = 2; 16 solves 205-206 us in two rounds of NS = 1 ->
-// 218 us in one round of NS = 4, 255 us with NS = 2; profiles/r06_ab_x3h.log), kept as A/B arms
-static int x3h_ns(const SolveArgs& a) {
-  const char* e = std::getenv("MPPI_X3H_NS");
-  int ns = e ? std::atoi(e) : 1;
-  if (ns != 1 && ns != 2 && ns != 4) ns = 1;
-  while (ns > 1 && (a.Kp >> 4) % ns != 0) ns >>= 1;  // a block's tiles belong to one solve
-  return ns;
-}
-
-hipError_t launch_fc_x3h(const SolveArgs& a, const FcArgs& fa, hipStream_t stream) {
-  const int groups = a.B * (a.Kp >> 4);
-  if (a.Kp % 16 != 0 || groups < 1 || fa.wmf16_0_off < 0 || fa.wmf16_x_off < 0 || fa.wmf16_off < 0 ||
-      (X3H_B0MMA && fa.wmf16_0b_off < 0))
+// Routed by fc_route (fc_route.h) wherever fc_rollout_kernel_x3d would run the fp16 form.  Tiles per wave (route.ns):
+// 1 (one group per block, two blocks per CU), or 2 / 4 (MPPI_X3H_NS) -- one block per CU at one wave per SIMD, NS static
+// chains per wave: measured slower than the dynamic interleave of two blocks per CU at both shard sizes (same box: 8
+// solves 104.6 -> 126.5 us with NS = 2; 16 solves 205-206 us in two rounds of NS = 1 -> 218 us in one round of NS = 4,
+// 255 us with NS = 2; profiles/r06_ab_x3h.log), kept as A/B arms
+hipError_t launch_fc_x3h(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream) {
+  const int groups = a.B * (a.Kp >> 4), ns = r.ns;
+  if (groups < 1 || fa.wmf16_x_off < 0 || (r.form != 0 && r.form != 1) || (ns != 1 && ns != 2 && ns != 4) ||
+      (a.Kp >> 4) % ns != 0)  // a block's tiles belong to one solve
     return hipErrorInvalidValue;
-  const bool l2x1 = x3_f16_l2x1(fa.x3_f16);
-  const int ns = x3h_ns(a);
-  static const char* const names[2][3] = {
-      {"fc_rollout_kernel_x3h<f16>", "fc_rollout_kernel_x3hw<f16,ns=2>", "fc_rollout_kernel_x3hw<f16,ns=4>"},
-      {"fc_rollout_kernel_x3h<f16,l2=1>", "fc_rollout_kernel_x3hw<f16,l2=1,ns=2>", "fc_rollout_kernel_x3hw<f16,l2=1,ns=4>"}};
-  note_kernel(names[l2x1][ns == 1 ? 0 : (ns == 2 ? 1 : 2)]);
-  auto go = [&](auto kern, int bytes) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(groups / ns), dim3(256), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
   auto by_ns = [&](auto cost, auto l2) {
     constexpr int C = decltype(cost)::value;
     constexpr bool L2 = decltype(l2)::value;
     switch (ns) {
-      case 2: return go(fc_rollout_kernel_x3hw<C, L2, 2>, X3hLay<C, 2>::BYTES);
-      case 4: return go(fc_rollout_kernel_x3hw<C, L2, 4>, X3hLay<C, 4>::BYTES);
-      default: return go(fc_rollout_kernel_x3h<C, L2>, X3hLay<C, 1>::BYTES);
+      case 2: return fc_launch(fc_rollout_kernel_x3hw<C, L2, 2>, groups / 2, 256, X3hLay<C, 2>::BYTES, stream, a, fa);
+      case 4: return fc_launch(fc_rollout_kernel_x3hw<C, L2, 4>, groups / 4, 256, X3hLay<C, 4>::BYTES, stream, a, fa);
+      default: return fc_launch(fc_rollout_kernel_x3h<C, L2>, groups, 256, X3hLay<C, 1>::BYTES, stream, a, fa);
     }
   };
-  auto by_form = [&](auto cost) {
-    return l2x1 ? by_ns(cost, std::true_type{}) : by_ns(cost, std::false_type{});
-  };
-  if (a.cost_kind == MPPI_COST_HUMANOID_V1) return by_form(std::integral_constant<int, MPPI_COST_HUMANOID_V1>{});
-  return by_form(std::integral_constant<int, MPPI_COST_HUMANOID_V3>{});
+  return by_humanoid_cost(a.cost_kind, [&](auto cost) {
+    return r.form == 0 ? by_ns(cost, std::true_type{}) : by_ns(cost, std::false_type{});
+  });
 }
 
 }  // namespace mppi

@@ -11,7 +11,6 @@
 //   * layer 0's bias rides in the MFMA (the b0 pair in pad state slots 62, 63, which hold 1.0: their lo parts are 0);
 //     b1, b2, b3 initialise the accumulators.
 //   * the running cost's state part through a one-step LDS ring (lane group 0 evaluates its 16 samples every step).
-#include <cstdlib>
 
 #include "x3_common.h"
 
@@ -28,7 +27,7 @@ struct WaveMlpX3Lay {
   static constexpr int B2 = B1 + 512;          // 128 f32
   static constexpr int B3 = B2 + 512;          // 64 f32
   static constexpr int RING = B3 + 256;
-  static constexpr int WAVES = 8;
+  static constexpr int WAVES = kWaveMlpX3Waves;
   template <int COST>
   static constexpr int ring_bytes() { return 16 * CostChunks<kArchMLP, COST>::HS * 4; }
   template <int COST>
@@ -298,45 +297,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   kclock_record(a, kc);
 }
 
-static int x3m_device_cus() { return x3_device_cus(); }
-
-// MPPI_X3M (read per launch): 0 = never, 1 = always (when the image carries it); unset = from one round of 8
-// 16-sample wave-tiles per CU (the M-split split kernel below that: it spreads a tile's step over 4 SIMDs)
-bool fc_wave_mlp_x3_wanted(const SolveArgs& a, const FcArgs& fa) {
-  if (fa.wmx3_off < 0 || a.Kp < 16 || a.Kp % 16 != 0 || a.nx > kMlpBiasSlotHi || a.nu > 32) return false;
-  const char* e = std::getenv("MPPI_X3M");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  return a.B * (a.Kp / 16) >= WaveMlpX3Lay::WAVES * x3m_device_cus();
-}
-
-hipError_t launch_fc_wave_mlp_x3(const SolveArgs& a, const FcArgs& fa, hipStream_t stream) {
-  if (fa.wmx3_off < 0 || a.Kp <= 0 || a.Kp % 16 != 0) return hipErrorInvalidValue;
+// Routed by fc_route (fc_route.h) from one round of 8 16-sample wave-tiles per CU (the M-split split kernel below
+// that: it spreads a tile's step over 4 SIMDs)
+hipError_t launch_fc_wave_mlp_x3(const SolveArgs& a, const FcArgs& fa, const FcRoute&, hipStream_t stream) {
   const int wts = a.B * (a.Kp / 16);
   int grid = (wts + WaveMlpX3Lay::WAVES - 1) / WaveMlpX3Lay::WAVES;
-  if (grid > x3m_device_cus()) grid = x3m_device_cus();
-  auto go = [&](auto kern, int bytes) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WaveMlpX3Lay::WAVES), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
-  note_kernel("fc_wave_mlp_x3_kernel");
-#define MPPI_WAVE_MLP_X3_COST(K)                                                                    \
-  case K:                                                                                           \
-    static_assert(WaveMlpX3Lay::bytes<K>() <= 160 * 1024, "LDS per CU");                            \
-    return go(fc_wave_mlp_x3_kernel<K>, WaveMlpX3Lay::bytes<K>());
-  switch (a.cost_kind) {
-    MPPI_WAVE_MLP_X3_COST(MPPI_COST_HUMANOID_V3)
-    MPPI_WAVE_MLP_X3_COST(MPPI_COST_HUMANOID_V1)
-    MPPI_WAVE_MLP_X3_COST(MPPI_COST_QUAD_EST)
-    MPPI_WAVE_MLP_X3_COST(MPPI_COST_QUAD_JL)
-    MPPI_WAVE_MLP_X3_COST(MPPI_COST_CARTPOLE_EST)
-    MPPI_WAVE_MLP_X3_COST(MPPI_COST_CARTPOLE)
-    default: return hipErrorInvalidValue;
-  }
-#undef MPPI_WAVE_MLP_X3_COST
+  if (grid > current_device_cus()) grid = current_device_cus();
+  return by_cost(a.cost_kind, [&](auto cost) {
+    constexpr int C = decltype(cost)::value;
+    static_assert(WaveMlpX3Lay::bytes<C>() <= 160 * 1024, "LDS per CU");
+    return fc_launch(fc_wave_mlp_x3_kernel<C>, grid, 64 * WaveMlpX3Lay::WAVES, WaveMlpX3Lay::bytes<C>(), stream, a, fa);
+  });
 }
 
 }  // namespace mppi

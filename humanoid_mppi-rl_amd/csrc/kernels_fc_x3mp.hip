@@ -9,7 +9,6 @@
 //   * layer 0's operand: the state as two 32x32 tiles (k-steps 0..3) and the controls laid out as a third tile (k-steps
 //     4, 5: lane half h holds controls 8 i + 4 h + r, r < 4), so all six k-steps split like an accumulator tile.
 //   * the running cost's state part from the registers (lane half 0; one v_permlane32_swap per slot that half 1 holds).
-#include <cstdlib>
 
 #include "x3_common.h"
 
@@ -29,7 +28,7 @@ struct WaveMlp32X3Lay {
   static constexpr int B2 = B1 + 512;          // 128 f32
   static constexpr int B3 = B2 + 512;          // 64 f32
   static constexpr int BYTES = B3 + 256;
-  static constexpr int WAVES = 8;
+  static constexpr int WAVES = kWaveMlp32X3Waves;
 };
 #ifndef X3MP_LQ  // W1 / W2 lo fragments read this many stream positions ahead (position = one MFMA triple)
 #define X3MP_LQ 8
@@ -285,40 +284,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   kclock_record(a, kc);
 }
 
-// MPPI_X3M32 (read per launch): 0 = never, 1 = always (when the image carries it); unset: from one round of 8
-// 32-sample wave-tiles per CU (below it fc_wave_mlp_x3_kernel or the M-split split kernel)
-bool fc_wave32_mlp_x3_wanted(const SolveArgs& a, const FcArgs& fa) {
-  if (fa.wm32x3_off < 0 || a.Kp < 32 || a.Kp % 32 != 0 || a.nx > kMlpBiasSlotHi || a.nu > 32) return false;
-  const char* e = std::getenv("MPPI_X3M32");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  return a.B * (a.Kp / 32) >= WaveMlp32X3Lay::WAVES * x3_device_cus();
-}
-
-hipError_t launch_fc_wave32_mlp_x3(const SolveArgs& a, const FcArgs& fa, hipStream_t stream) {
-  if (fa.wm32x3_off < 0 || a.Kp <= 0 || a.Kp % 32 != 0) return hipErrorInvalidValue;
+// Routed by fc_route (fc_route.h) from one round of 8 32-sample wave-tiles per CU (below it fc_wave_mlp_x3_kernel or
+// the M-split split kernel)
+hipError_t launch_fc_wave32_mlp_x3(const SolveArgs& a, const FcArgs& fa, const FcRoute&, hipStream_t stream) {
   const int wts = a.B * (a.Kp / 32);
   int grid = (wts + WaveMlp32X3Lay::WAVES - 1) / WaveMlp32X3Lay::WAVES;
-  if (grid > x3_device_cus()) grid = x3_device_cus();
-  auto go = [&](auto kern) {
-    constexpr int bytes = WaveMlp32X3Lay::BYTES;
-    static_assert(bytes <= 160 * 1024, "LDS per CU");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WaveMlp32X3Lay::WAVES), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
-  note_kernel("fc_wave32_mlp_x3_kernel");
-  switch (a.cost_kind) {
-    case MPPI_COST_HUMANOID_V3: return go(fc_wave32_mlp_x3_kernel<MPPI_COST_HUMANOID_V3>);
-    case MPPI_COST_HUMANOID_V1: return go(fc_wave32_mlp_x3_kernel<MPPI_COST_HUMANOID_V1>);
-    case MPPI_COST_QUAD_EST: return go(fc_wave32_mlp_x3_kernel<MPPI_COST_QUAD_EST>);
-    case MPPI_COST_QUAD_JL: return go(fc_wave32_mlp_x3_kernel<MPPI_COST_QUAD_JL>);
-    case MPPI_COST_CARTPOLE_EST: return go(fc_wave32_mlp_x3_kernel<MPPI_COST_CARTPOLE_EST>);
-    case MPPI_COST_CARTPOLE: return go(fc_wave32_mlp_x3_kernel<MPPI_COST_CARTPOLE>);
-    default: return hipErrorInvalidValue;
-  }
+  if (grid > current_device_cus()) grid = current_device_cus();
+  static_assert(WaveMlp32X3Lay::BYTES <= 160 * 1024, "LDS per CU");
+  return by_cost(a.cost_kind, [&](auto cost) {
+    return fc_launch(fc_wave32_mlp_x3_kernel<decltype(cost)::value>, grid, 64 * WaveMlp32X3Lay::WAVES,
+                     WaveMlp32X3Lay::BYTES, stream, a, fa);
+  });
 }
 
 }  // namespace mppi

@@ -12,7 +12,6 @@
 //     after one v_permlane32_swap per slot 4..6), so there is no LDS cost ring: the LDS holds the 144 KiB image and
 //     b1 / bx only.
 // Its own translation unit, so that its machine-scheduler flags are its own (build.py PER_FILE_FLAGS).
-#include <cstdlib>
 
 #include "x3_common.h"
 
@@ -527,35 +526,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   kclock_record(a, kc);
 }
 
-hipError_t launch_fc_wave_x3p(const SolveArgs& a, const FcArgs& fa, hipStream_t stream) {
+hipError_t launch_fc_wave_x3p(const SolveArgs& a, const FcArgs& fa, const FcRoute& r, hipStream_t stream) {
   const int wts = a.B * (a.Kp / 32);
   int grid = (wts + X3P_WAVES - 1) / X3P_WAVES;  // 8 wave-tiles per CU and round
-  if (grid > x3_device_cus()) grid = x3_device_cus();
-  auto go = [&](auto kern) {
-    const int bytes = WaveX3Lay::RING;  // the image + b1 / bx (no cost ring)
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * X3P_WAVES), bytes, stream, a, fa);
-    return hipGetLastError();
-  };
-  const int form = x3_form(a.H, fa.x3_l1, fa.x3_f16, fa.w32f16_off);
-  static const char* const names[4] = {
-      MPPI_X3_F16_L0 ? "fc_wave32_x3p_kernel<f16,l2=1>" : "fc_wave32_x3p_kernel<l1=f16,l2=1>",
-      MPPI_X3_F16_L0 ? "fc_wave32_x3p_kernel<f16>" : "fc_wave32_x3p_kernel<l1=f16>", "fc_wave32_x3p_kernel<l1=2>",
-      "fc_wave32_x3p_kernel<l1=3>"};
-  note_kernel(names[form]);
-  auto by_form = [&](auto cost) {
+  if (grid > current_device_cus()) grid = current_device_cus();
+  return by_humanoid_cost(a.cost_kind, [&](auto cost) {
     constexpr int C = decltype(cost)::value;
-    switch (form) {
-      case 0: return go(fc_wave32_x3p_kernel<C, 0>);
-      case 1: return go(fc_wave32_x3p_kernel<C, 1>);
-      case 2: return go(fc_wave32_x3p_kernel<C, 2>);
-      default: return go(fc_wave32_x3p_kernel<C, 3>);
+    constexpr int bytes = WaveX3Lay::RING, kBlock = 64 * X3P_WAVES;  // the image + b1 / bx (no cost ring)
+    switch (r.form) {
+      case 0: return fc_launch(fc_wave32_x3p_kernel<C, 0>, grid, kBlock, bytes, stream, a, fa);
+      case 1: return fc_launch(fc_wave32_x3p_kernel<C, 1>, grid, kBlock, bytes, stream, a, fa);
+      case 2: return fc_launch(fc_wave32_x3p_kernel<C, 2>, grid, kBlock, bytes, stream, a, fa);
+      default: return fc_launch(fc_wave32_x3p_kernel<C, 3>, grid, kBlock, bytes, stream, a, fa);
     }
-  };
-  if (a.cost_kind == MPPI_COST_HUMANOID_V1) return by_form(std::integral_constant<int, MPPI_COST_HUMANOID_V1>{});
-  return by_form(std::integral_constant<int, MPPI_COST_HUMANOID_V3>{});
+  });
 }
 
 }  // namespace mppi

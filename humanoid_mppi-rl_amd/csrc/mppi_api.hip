@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "costs.h"
-#include "fc_common.h"  // x3_l1_terms, kX3ProbeTol (the split CA's layer-1 probe)
+#include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
 
 namespace mppi {
@@ -223,7 +223,7 @@ void mppi_destroy(mppi_handle* h) {
   harvest_events(h);
   for (hipEvent_t e : h->evt_pool) (void)hipEventDestroy(e);
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
-                  h->d_tickets, h->net.d_img, h->fa.d_img, h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs,
+                  h->d_tickets, const_cast<char*>(h->net.fa.img), h->fa.d_img, h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs,
                   h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
@@ -317,7 +317,7 @@ int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes
     } catch (const std::exception& ex) {
       return fail(MPPI_E_UNSUPPORTED, std::string("mppi_load_dynamics: ") + ex.what());
     }
-    if (h->cfg.precision == MPPI_PREC_BF16 && net.lds_bytes > 128 * 1024)
+    if (h->cfg.precision == MPPI_PREC_BF16 && net.fa.lds_bytes > 128 * 1024)
       return fail(MPPI_E_UNSUPPORTED, "mppi_load_dynamics: LDS part of the packed bf16 image exceeds 128 KiB");
     HIP_TRY(hipStreamSynchronize(h->stream));
     void* d = nullptr;
@@ -326,8 +326,8 @@ int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes
       (void)hipFree(d);
       return fail(MPPI_E_HIP, std::string("mppi_load_dynamics: image upload: ") + hipGetErrorString(e));
     }
-    if (h->net.d_img) (void)hipFree(h->net.d_img);
-    net.d_img = d;
+    if (h->net.fa.img) (void)hipFree(const_cast<char*>(h->net.fa.img));
+    net.fa.img = static_cast<const char*>(d);
     net.x3_l1 = 0;  // a new net: the split layer-1 probe runs again at the next solve (x3_probe)
     h->net = net;
     h->dyn_kind = kind;
@@ -852,7 +852,7 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   return finish_solve(h, B, io);
 }
 
-// The split CA's two-product layer 1 (fc_common.h x3_l1_terms) as a CHECKED property of the loaded weights.  Before
+// The split CA's two-product layer 1 (fc_route.h x3_l1_terms; fc_common.h) as a CHECKED property of the loaded weights.  Before
 // the first split-mode solve of a CrossAttention net the engine rolls the first solve's own states and U (up to
 // kProbeB solves, kProbeK samples each, seeded device noise of the configured sigma, the configured horizon, cost and
 // context) through the same routed kernel twice, with two and with three products on layer 1, and keeps the two-product
@@ -861,9 +861,10 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
 // two-product form's own error on this net, these states and this horizon.  Runs once per loaded net, on the handle's
 // stream, with its own buffers (no effect on the noise counter, the prefetched noise or U), before any graph capture.
 // Horizons beyond kX3TwoTermMaxH keep three products without a probe (the error grows ~H^2); MPPI_X3_L1_TERMS forces.
-// The same run decides the fp16 form (fc_common.h x3_f16_on): one more rollout of the same inputs through each kernel
-// that runs the form -- fc_wave32_x3p_kernel (the large batches) and fc_rollout_kernel_x3h (the few-tiles shards),
-// x3_route, whatever the probe's batch -- kept only if both are within kX3ProbeTol of the three-product costs
+// The same run decides the fp16 form (fc_route.h x3_f16_on): one more rollout of the same inputs through each kernel
+// the probe covers -- fc_wave32_x3p_kernel (the large batches) and fc_rollout_kernel_x3h (the few-tiles shards), by
+// routes of its own (launch_fc_route) whatever the probe's batch -- kept only if both are within kX3ProbeTol of the
+// three-product costs
 // (FcNet::x3_f16 = 1, x3_f16_err = the larger error), else not (-1).  The probe covers up to kProbeB of the first batch's solves at kProbeK samples
 // each: the CA surrogate's dynamics do not depend on the controls (its action encoder never reaches the output), so
 // the form's error is one number per state -- more states, not more samples, find the worst.
@@ -872,14 +873,15 @@ static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
       h->net.x3_l1 != 0)
     return MPPI_OK;
   const mppi_config& c = h->cfg;
-  if (x3_l1_env() || c.H > kX3TwoTermMaxH) {
-    h->net.x3_l1 = c.H > kX3TwoTermMaxH ? 3 : x3_l1_env();
+  const FcKnobs knobs = fc_knobs_from_env();
+  if (knobs.x3_l1_terms || c.H > kX3TwoTermMaxH) {
+    h->net.x3_l1 = c.H > kX3TwoTermMaxH ? 3 : knobs.x3_l1_terms;
     h->net.x3_l1_err = -1.0f;
     h->net.x3_f16 = -1;  // (MPPI_X3_F16=1 still forces it: x3_f16_on)
     h->net.x3_f16_err = -1.0f;
     return MPPI_OK;
   }
-  const bool f16 = h->net.w32f16_off >= 0;
+  const bool f16 = h->net.fa.w32f16_off >= 0;
   constexpr int kProbeB = 64, kProbeK = 64;
   const int Bp = B < kProbeB ? B : kProbeB, Kpr = h->Kp < kProbeK ? h->Kp : kProbeK;
   const bool dev = (flags & MPPI_FLAG_DEVICE) != 0, colmajor = (flags & MPPI_FLAG_COLMAJOR) != 0;
@@ -898,13 +900,6 @@ static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
   unsigned* p_st = reinterpret_cast<unsigned*>(p_ctx + (size_t)Bp * MPPI_CTX_MAX);
   hipStream_t s = h->stream;
   std::vector<float> hc1(nC), hc2(nC), hc3(nC), hch(nC), stage;
-  FcArgs fh{};  // (only fc_x3h_wanted's fields: the shards' kernel can run this net's fp16 form)
-  fh.w_off[1] = h->net.w_off[1];
-  fh.ln_n = h->net.ln_n;
-  fh.wmf16_0_off = h->net.wmf16_0_off;
-  fh.wmf16_0b_off = h->net.wmf16_0b_off;
-  fh.wmf16_off = h->net.wmf16_off;
-  fh.x3_f16 = 1;
   bool x3h = false;
   auto run = [&]() -> hipError_t {
     const hipMemcpyKind k = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -943,24 +938,23 @@ static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
     a.noise = p_noise;
     a.ctx = io->ctx ? p_ctx : nullptr;
     a.status = p_st;
-    FcNet n = h->net;
-    n.x3_f16 = -1;
-    for (int terms : {2, 3}) {
-      n.x3_l1 = terms;
+    const FcNet& n = h->net;
+    const int cus = current_device_cus();
+    for (int terms : {2, 3}) {  // as routed for the probe's batch, the fp16 form decided off
       a.costs = terms == 2 ? p_c2 : p_c3;
-      if (e == hipSuccess) e = launch_fc_rollout(a, n, s);
+      const FcRoute r = fc_route(n.arch, n.precision, a, n.fa, terms, -1, cus, knobs);
+      if (e == hipSuccess) e = launch_fc_route(a, n, r, s);
     }
-    if (f16) {  // the fp16 form on fc_wave32_x3p_kernel
-      n.x3_route = 1;
-      n.x3_f16 = 1;
+    if (f16) {  // the fp16 form (form 1; a knob that forces the form forces the probe's too) on fc_wave32_x3p_kernel
       a.costs = p_c1;
-      if (e == hipSuccess) e = launch_fc_rollout(a, n, s);
+      const FcRoute rp = {FcKernel::x3p, x3_form(c.H, 3, 1, n.fa.w32f16_off, knobs), 1};
+      if (e == hipSuccess) e = launch_fc_route(a, n, rp, s);
       if (e == hipSuccess) e = hipMemcpyAsync(hc1.data(), p_c1, nC * 4, hipMemcpyDeviceToHost, s);
       a.costs = p_ch;
-      x3h = fc_x3h_wanted(a, fh);
+      x3h = fc_route_can_run(FcKernel::x3h, a, n.fa) && x3_f16_on(c.H, 1, n.fa.wmf16_off, knobs) && knobs.x3h;
       if (x3h) {  // ... and on fc_rollout_kernel_x3h
-        n.x3_route = 2;
-        if (e == hipSuccess) e = launch_fc_rollout(a, n, s);
+        const FcRoute rh = {FcKernel::x3h, x3_form(c.H, 3, 1, n.fa.wmf16_off, knobs), x3h_tiles(a.Kp, knobs)};
+        if (e == hipSuccess) e = launch_fc_route(a, n, rh, s);
         if (e == hipSuccess) e = hipMemcpyAsync(hch.data(), p_ch, nC * 4, hipMemcpyDeviceToHost, s);
       }
     }
@@ -1000,7 +994,7 @@ int mppi_x3_layer1(mppi_handle* h, int* products, float* probe_rel_err) {
   if (!h) return fail(MPPI_E_ARG, "mppi_x3_layer1: null handle");
   const bool split_ca = h->dyn_kind == MPPI_DYN_CROSS_ATTN && h->cfg.precision == MPPI_PREC_BF16X3 &&
                         h->net.arch == kArchCA;
-  if (products) *products = split_ca && h->net.x3_l1 ? x3_l1_terms(h->cfg.H, h->net.x3_l1) : 0;
+  if (products) *products = split_ca && h->net.x3_l1 ? x3_l1_terms(h->cfg.H, h->net.x3_l1, fc_knobs_from_env()) : 0;
   if (probe_rel_err) *probe_rel_err = split_ca ? h->net.x3_l1_err : -1.0f;
   return MPPI_OK;
 }
@@ -1009,10 +1003,11 @@ int mppi_x3_f16(mppi_handle* h, int* on, float* probe_rel_err) {
   if (!h) return fail(MPPI_E_ARG, "mppi_x3_f16: null handle");
   const bool split_ca = h->dyn_kind == MPPI_DYN_CROSS_ATTN && h->cfg.precision == MPPI_PREC_BF16X3 &&
                         h->net.arch == kArchCA;
-  if (on)
-    *on = split_ca && x3_f16_on(h->cfg.H, h->net.x3_f16, h->net.w32f16_off)
-              ? (x3_f16_l2x1(h->net.x3_f16) ? 2 : 1)
-              : 0;
+  if (on) {
+    const FcKnobs k = fc_knobs_from_env();
+    *on = split_ca && x3_f16_on(h->cfg.H, h->net.x3_f16, h->net.fa.w32f16_off, k) ? (x3_f16_l2x1(h->net.x3_f16, k) ? 2 : 1)
+                                                                                  : 0;
+  }
   if (probe_rel_err) *probe_rel_err = split_ca ? h->net.x3_f16_err : -1.0f;
   return MPPI_OK;
 }

@@ -134,24 +134,24 @@ struct FcGenNet {
   int maxw = 0;                    // widest activation row (padded to 32)
 };
 
-struct FcNet {
-  int arch = kArchNone;
-  FcGenNet gen;                    // arch == kArchGeneric
-  int precision = MPPI_PREC_BF16;
-  // Byte offsets inside the packed image (identical layout for LDS copy and global reads).
+// The packed image of an fc-stack net as the kernels take it (a kernel argument, by value): plain ints and one pointer.
+// Byte offsets inside the image (identical layout for the LDS copy and global reads), filled by the packer
+// (mppi_nets.cpp); img is set when the image is uploaded.  -1: that part is not built (other shapes or precisions).
+struct FcArgs {
+  const char* img = nullptr;       // device copy of the packed image
+  int lds_bytes = 0;               // bf16: prefix of the image staged in LDS (the other layers live in VGPRs)
   int w_off[4] = {0, 0, 0, 0};     // per-layer packed weight fragments
   int b_off[4] = {0, 0, 0, 0};     // per-layer fp32 bias (padded rows)
   int lnb_off = 0;                 // beta' of the LayerNorm after layer 0, folded (fp32; gamma lives in layer 1)
   int ln_n = 0;                    // true LayerNorm width (pads excluded)
-  int img_bytes = 0;
-  int lds_bytes = 0;               // bf16: prefix of the image staged in LDS (the other layers live in VGPRs)
-  int reg_mask = 0;                // layers packed after the LDS prefix (kCaRegMask / kMlpRegMask)
   // state slots: x[0, qp) -> slots [0, qp); x[qp, qp+qv) -> slots [32, 32+qv) (CA: qpos | qvel).
   int qp = 0, qv = 0;
+  int groups_per_block = 1;        // set by the M-split launchers (the only non-offset field a kernel reads)
   // folded humanoid CA, bf16: the per-wave rollout (kernels_fc_wave.hip) also needs the layer-0 Gram matrix of the
   // bf16 columns as hi / lo bf16 fragments (G_hi at g_off, G_lo at g_off + 8 KiB) and beta' as bf16 hi / lo in the pad
-  // state columns kCaBetaSlotHi0/Lo/Hi1 of layer 0; -1: not built (other shapes or fp32)
+  // state columns kCaBetaSlotHi0/Lo/Hi1 of layer 0
   int g_off = -1;
+  int wave = 0;                    // the image carries what the per-wave kernel needs (CA: g_off, beta'; MLP: the b0 pair)
   int w32_off = -1;                // ... and the CA layers + Gram factor as 32x32x16 A fragments (fc_wave32_kernel)
   int w32_bd = 0;                  // ... with layer 0 block-diagonal, uncentred (the mean from the Gram factor's row 30):
                                    // 1 = 112 MFMAs per wave-step, 2 = 108 (qpos rows' bias via the accumulators); 0 = dense
@@ -159,24 +159,30 @@ struct FcNet {
   int w32x3_off = -1, w32x3_l1lo_off = -1;  // split bf16 per-wave image (fc_wave32_x3_kernel): LDS part, W1 lo part
   int wmx3_off = -1, wmx3_lo_off = -1;      // split bf16 per-wave MLP image (fc_wave_mlp_x3_kernel): LDS part, W1|W2 lo
   int wm32x3_off = -1, wm32x3_lo_off = -1;  // ... 32 samples per wave (fc_wave32_mlp_x3_kernel): LDS part, W1|W2 lo
-  int wave = 0;                    // the image carries what the per-wave kernel needs (CA: g_off, beta'; MLP: the b0 pair)
-  // split bf16 (MPPI_PREC_BF16X3) CA only: products on layer 1 as decided for THIS net by the engine's probe
-  // (mppi_api.hip x3_probe: the two- and three-product rollouts of the first solve's own states against each other);
-  // 0 = not probed yet (three products), 2 = the probe stayed within kX3ProbeTol, 3 = it did not
-  int x3_l1 = 0;
-  float x3_l1_err = -1.0f;         // the probe's max relative cost difference (-1: no probe ran)
-  // ... and the fp16 form (fc_common.h x3_f16_on): its images (fc_wave32_x3p_kernel's: the w32x3 LDS image in fp16;
-  // the M-split kernel's below), the probe's decision (0 = not probed, 1 = within kX3ProbeTol, -1 = not; 2 = the
-  // opt-in one-product last layer, x3_f16_l2x1) and difference; x3_route = 1 / 2 only in the probe's own copy
-  // (fc_wave32_x3p_kernel whatever the batch)
+  // the split CA's fp16 form (fc_route.h x3_f16_on): fc_wave32_x3p_kernel's image (the w32x3 LDS image in fp16),
   int w32f16_off = -1;
   int wmf16_off = -1, wmf16_x_off = -1;  // ... the M-split kernels' (fc_rollout_kernel_x3d<F16>): W1, the last layer,
   int wmf16_0_off = -1;                  //     layer 0 (fp16 hi / lo)
   int wmf16_0b_off = -1;                 //     ... with b0 in the pad column kCaX3hBiasSlot (fc_rollout_kernel_x3h)
+};
+
+struct FcNet {
+  int arch = kArchNone;
+  FcGenNet gen;                    // arch == kArchGeneric
+  int precision = MPPI_PREC_BF16;
+  FcArgs fa;                       // arch == kArchCA / kArchMLP: the packed image
+  int img_bytes = 0;               // size of the packed image (what mppi_load_dynamics uploads; no kernel reads it)
+  int reg_mask = 0;                // layers packed after the LDS prefix (kCaRegMask / kMlpRegMask)
+  // Host-only state, read by fc_route (fc_route.h), never by a kernel.  Split bf16 (MPPI_PREC_BF16X3) CA only: products
+  // on layer 1 as decided for THIS net by the engine's probe (mppi_api.hip x3_probe: the two- and three-product
+  // rollouts of the first solve's own states against each other); 0 = not probed yet (three products), 2 = the probe
+  // stayed within kX3ProbeTol, 3 = it did not
+  int x3_l1 = 0;
+  float x3_l1_err = -1.0f;         // the probe's max relative cost difference (-1: no probe ran)
+  // ... and the fp16 form: the probe's decision (0 = not probed, 1 = within kX3ProbeTol, -1 = not; 2 = the opt-in
+  // one-product last layer, x3_f16_l2x1) and difference
   int x3_f16 = 0;
   float x3_f16_err = -1.0f;
-  int x3_route = 0;
-  void* d_img = nullptr;           // device copy of the packed image
 };
 
 // CU count of the CURRENT device (the launchers size persistent grids by it), cached per device id: a process that
@@ -242,7 +248,11 @@ struct FaNet {
 hipError_t launch_noise(float* noise, int B, int nu, int H, int Kp, uint64_t seed, const unsigned long long* seed_ctr,
                         float sigma, hipStream_t stream);
 hipError_t launch_seed_bump(unsigned long long* seed_ctr, long long delta, hipStream_t stream);  // += delta
+// fc-stack rollout: fc_route (fc_route.h) decides the kernel from the shape, the image, the probe outcomes and the
+// knobs; launch_fc_route launches a given route (the engine's probe passes routes of its own)
+struct FcRoute;
 hipError_t launch_fc_rollout(const SolveArgs& a, const FcNet& net, hipStream_t stream);
+hipError_t launch_fc_route(const SolveArgs& a, const FcNet& net, const FcRoute& route, hipStream_t stream);
 hipError_t launch_fc_generic(const SolveArgs& a, const FcNet& net, hipStream_t stream);  // kernels_fc_generic.hip
 
 // LDS layout (bytes) of one block of the generic fc-stack kernel: activation rows A0 | A1 ([16][maxw] of E-byte

@@ -159,7 +159,7 @@ static double f16_to_f64(uint16_t b) {
 }
 
 // Pack the layer stack + LN into one image; fills offsets in `net`.  Image order: the weight fragments of the
-// layers NOT in `reg_mask` (bit l: layer l) -- the prefix [0, net.lds_bytes) the bf16 kernel stages in LDS --, then
+// layers NOT in `reg_mask` (bit l: layer l) -- the prefix [0, net.fa.lds_bytes) the bf16 kernel stages in LDS --, then
 // the fragments of the `reg_mask` layers (loaded into VGPRs once per launch), then every layer's fp32 bias and the
 // folded LayerNorm's beta'.
 static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, const std::vector<double>* ln_b,
@@ -233,28 +233,28 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
   };
   auto put_layer = [&](size_t l) {
     align16();
-    net.w_off[l] = (int)img.size();
+    net.fa.w_off[l] = (int)img.size();
     put_frags(L[l]);
   };
   for (size_t l = 0; l < L.size(); ++l)
     if (!(reg_mask >> l & 1)) put_layer(l);
   align16();
-  net.lds_bytes = (int)img.size();
+  net.fa.lds_bytes = (int)img.size();
   for (size_t l = 0; l < L.size(); ++l)
     if (reg_mask >> l & 1) put_layer(l);
   for (size_t l = 0; l < L.size(); ++l) {
     align16();
-    net.b_off[l] = (int)img.size();
+    net.fa.b_off[l] = (int)img.size();
     for (double v : L[l].b) put_f32((float)v);
   }
   if (ln_b) {
     align16();
-    net.lnb_off = (int)img.size();
+    net.fa.lnb_off = (int)img.size();
     for (double v : *ln_b) put_f32((float)v);
   }
   if (gram) {  // the per-wave CA kernel's Gram matrix: G_hi, then G_lo (8 KiB each)
     align16();
-    net.g_off = (int)img.size();
+    net.fa.g_off = (int)img.size();
     for (const SlotLayer& S : *gram) put_frags(S);
     // ... and every layer + the Gram factor again as v_mfma_f32_32x32x16_bf16 A fragments (kernels_fc_wave.hip,
     // fc_wave32_kernel): fragment (D-tile T of 32 rows, k-step ks of 16) at index T * KS16 + ks, lane l holds row
@@ -263,7 +263,7 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
     // -- the row a lane of the previous layer's 32x32 accumulator tile holds there (value v = 4 i + r of lane l is row
     // 8 i + 4 (l >> 5) + r), so that accumulator packed to bf16 (values 8 (ks % 2) .. + 7) is this layer's B operand.
     align16();
-    net.w32_off = (int)img.size();
+    net.fa.w32_off = (int)img.size();
     auto put32 = [&](const SlotLayer& S) {
       const int MT32 = S.mto / 2, KS16 = S.mti;  // 32-row D-tiles; 16-wide k-steps over 16 mti inputs
       for (int T = 0; T < MT32; ++T)
@@ -278,15 +278,15 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
             }
           }
     };
-    // (fc_wave32_kernel's own layer 0 and Gram factor when given: the block-diagonal form, net.w32_bd)
+    // (fc_wave32_kernel's own layer 0 and Gram factor when given: the block-diagonal form, net.fa.w32_bd)
     for (size_t l = 0; l < L.size(); ++l) put32(l == 0 && l0_32 ? *l0_32 : L[l]);
     for (const SlotLayer& S : gram32 ? *gram32 : *gram) put32(S);
-    if (l0_32 && gram32 && net.w32_bd == 2) {  // ... and for fc_wave_kernel (16x32 fragments, put_frags order)
+    if (l0_32 && gram32 && net.fa.w32_bd == 2) {  // ... and for fc_wave_kernel (16x32 fragments, put_frags order)
       align16();
-      net.w0bd_off = (int)img.size();
+      net.fa.w0bd_off = (int)img.size();
       put_frags(*l0_32);
       align16();
-      net.gbd_off = (int)img.size();
+      net.fa.gbd_off = (int)img.size();
       for (const SlotLayer& S : *gram32) put_frags(S);
     }
   }
@@ -324,7 +324,7 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
         for (int ks = 0; ks < S.mti; ++ks) frag32(S, T, ks, part, f16);
     };
     align16();
-    net.w32x3_off = (int)img.size();
+    net.fa.w32x3_off = (int)img.size();
     l0(0);
     layer(L[1], 0);
     layer(L[2], 0);
@@ -333,7 +333,7 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
     layer(L[2], 1);
     layer(*r_x3, 1);
     align16();
-    net.w32x3_l1lo_off = (int)img.size();
+    net.fa.w32x3_l1lo_off = (int)img.size();
     layer(L[1], 1);
     // ... and fc_wave32_x3p_kernel's fp16 form (fc_common.h x3_f16_on): the same LDS image with W1 as ONE fp16
     // fragment per (T, ks) in W1's hi place and the last layer's hi / lo as fp16 (lo = W - hi, itself rounded to fp16,
@@ -344,7 +344,7 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
         for (int ks = T < 4 ? 0 : 2; ks < (T < 4 ? 2 : 4); ++ks) frag32(*l0_x3, T, ks, part, MPPI_X3_F16_L0 != 0);
     };
     align16();
-    net.w32f16_off = (int)img.size();
+    net.fa.w32f16_off = (int)img.size();
     l0f(0);
     layer(L[1], 0, true);
     layer(L[2], 0, true);
@@ -355,20 +355,20 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
     // ... and the M-split kernels' fp16 form (fc_rollout_kernel_x3d<F16>): layer 1 as one fp16 16x32 fragment per
     // (m-tile, k-step), the last layer and (MPPI_X3_F16_L0) the dense layer 0 as fp16 hi / lo (put_frags16)
     align16();
-    net.wmf16_off = (int)img.size();
+    net.fa.wmf16_off = (int)img.size();
     put_frags16(L[1], 1);
     align16();
-    net.wmf16_x_off = (int)img.size();
+    net.fa.wmf16_x_off = (int)img.size();
     put_frags16(L[2], 2);
     align16();
-    net.wmf16_0_off = (int)img.size();
+    net.fa.wmf16_0_off = (int)img.size();
     put_frags16(L[0], 2);
     // ... and for fc_rollout_kernel_x3h the same with b0 in the pad column kCaX3hBiasSlot (the state holds 1.0 there)
-    if (net.qp > 0 && net.qp <= kCaX3hBiasSlot) {
+    if (net.fa.qp > 0 && net.fa.qp <= kCaX3hBiasSlot) {
       SlotLayer L0b = L[0];
       for (int r = 0; r < 16 * L0b.mto; ++r) L0b.W(r, kCaX3hBiasSlot) = L0b.b[r];
       align16();
-      net.wmf16_0b_off = (int)img.size();
+      net.fa.wmf16_0b_off = (int)img.size();
       put_frags16(L0b, 2);
     }
   }
@@ -401,12 +401,12 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
         }
     };
     align16();
-    net.wmx3_off = (int)img.size();
+    net.fa.wmx3_off = (int)img.size();
     for (size_t l = 0; l < 4; ++l) part_frags(L[l], 0);
     part_frags(L[0], 1);
     part_frags(L[3], 1);
     align16();
-    net.wmx3_lo_off = (int)img.size();
+    net.fa.wmx3_lo_off = (int)img.size();
     part_frags(L[1], 1);
     part_frags(L[2], 1);
     // ... and as 32x32x16 A fragments for fc_wave32_mlp_x3_kernel (32 samples per wave): lane l holds row 32 T + (l & 31)
@@ -434,12 +434,12 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
           }
     };
     align16();
-    net.wm32x3_off = (int)img.size();
+    net.fa.wm32x3_off = (int)img.size();
     for (size_t l = 0; l < 4; ++l) part32(L[l], 0);
     part32(L[0], 1);
     part32(L[3], 1);
     align16();
-    net.wm32x3_lo_off = (int)img.size();
+    net.fa.wm32x3_lo_off = (int)img.size();
     part32(L[1], 1);
     part32(L[2], 1);
   }
@@ -450,10 +450,10 @@ static std::vector<unsigned char> pack_image(const std::vector<SlotLayer>& L, co
 }
 
 // Slot index of original state feature i, and original feature of slot s (-1 = pad).
-static int slot_of(const FcNet& n, int i) { return i < n.qp ? i : 32 + (i - n.qp); }
+static int slot_of(const FcNet& n, int i) { return i < n.fa.qp ? i : 32 + (i - n.fa.qp); }
 static int src_of(const FcNet& n, int s) {
-  if (s < 32) return s < n.qp ? s : -1;
-  return (s - 32) < n.qv ? n.qp + (s - 32) : -1;
+  if (s < 32) return s < n.fa.qp ? s : -1;
+  return (s - 32) < n.fa.qv ? n.fa.qp + (s - 32) : -1;
 }
 
 static void pack_frags(std::vector<unsigned char>& img, const Mat& W, int precision);
@@ -662,8 +662,8 @@ std::vector<unsigned char> build_fc_net(int kind, const void* blob, size_t nbyte
       return build_generic(L, &betap, precision, nx, nu, net);
     }
     net.arch = kArchCA;
-    net.qp = nq;
-    net.qv = nv;
+    net.fa.qp = nq;
+    net.fa.qv = nv;
     const Tensor& inw1 = get(T, "attn_qpos_to_qvel.in_proj_weight", {3 * D, D});
     const Tensor& inb1 = get(T, "attn_qpos_to_qvel.in_proj_bias", {3 * D});
     const Tensor& inw2 = get(T, "attn_qvel_to_qpos.in_proj_weight", {3 * D, D});
@@ -996,9 +996,9 @@ std::vector<unsigned char> build_fc_net(int kind, const void* blob, size_t nbyte
       }
     }
     L = {L0, L1, L2};
-    net.ln_n = 2 * D;
-    net.wave = gram.empty() ? 0 : 1;
-    net.w32_bd = bd ? bd_form : 0;  // (pack_image reads it: the 16x16 copies of form 2)
+    net.fa.ln_n = 2 * D;
+    net.fa.wave = gram.empty() ? 0 : 1;
+    net.fa.w32_bd = bd ? bd_form : 0;  // (pack_image reads it: the 16x16 copies of form 2)
     return pack_image(L, &ln_b, precision, kCaRegMask, net, gram.empty() ? nullptr : &gram, bd ? &L0bd : nullptr,
                       bd ? &gram_bd : nullptr, x3w ? &L0x : nullptr, x3w ? &Rx : nullptr);
   }
@@ -1017,8 +1017,8 @@ std::vector<unsigned char> build_fc_net(int kind, const void* blob, size_t nbyte
     }
     const int h = 128;
     net.arch = kArchMLP;
-    net.qp = nx < 32 ? nx : 32;
-    net.qv = nx - net.qp;
+    net.fa.qp = nx < 32 ? nx : 32;
+    net.fa.qv = nx - net.fa.qp;
     SlotLayer L0{8, 6, Mat(128, 96), M[0].b};
     for (int o = 0; o < h; ++o) {
       for (int s2 = 0; s2 < 64; ++s2) {
@@ -1047,7 +1047,7 @@ std::vector<unsigned char> build_fc_net(int kind, const void* blob, size_t nbyte
         L0.W(o, kMlpBiasSlotHi) = hi;
         L0.W(o, kMlpBiasSlotLo) = L0.b[o] - (double)hi;
       }
-      net.wave = precision == MPPI_PREC_BF16 ? 1 : 0;
+      net.fa.wave = precision == MPPI_PREC_BF16 ? 1 : 0;
     }
     L = {L0, L1, L2, L3};
     return pack_image(L, nullptr, precision, kMlpRegMask, net, nullptr, nullptr, nullptr, nullptr, nullptr,

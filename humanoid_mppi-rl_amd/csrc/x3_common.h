@@ -24,7 +24,6 @@ __device__ __forceinline__ unsigned pk_f16(float a, float b) {  // one v_cvt_pk_
 __device__ __forceinline__ float f16_hi_value(unsigned p) {  // the fp16 in the upper half of a packed pair, as fp32
   return (float)__builtin_bit_cast(_Float16, (unsigned short)(p >> 16));
 }
-static inline int x3_device_cus() { return current_device_cus(); }
 
 }  // namespace mppi
 
@@ -54,7 +53,7 @@ struct WaveX3Lay {
   static constexpr int B1 = IMG;             // 128 f32
   static constexpr int BX = B1 + 512;        // 64 f32
   static constexpr int RING = BX + 256;
-  static constexpr int WAVES = 4;
+  static constexpr int WAVES = kWaveX3Waves;
   template <int COST>
   static constexpr int ring_bytes() { return 2 * 32 * CostChunks<kArchCA, COST>::HS * 4; }
   template <int COST>

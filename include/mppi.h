@@ -220,8 +220,9 @@ int mppi_x3_layer1(mppi_handle* h, int* products, float* probe_rel_err);
 const char* mppi_rollout_kernel(mppi_handle* h);
 /* MPPI_PREC_BF16X3 with a CrossAttention net: *on = 1 if the rollouts run the fp16 form (MPPI_PREC_BF16X3 above) for
  * this handle's horizon, 2 with the opt-in one-product last layer (MPPI_X3_F16_L2=1), 0 if not (also before the first
- * solve); *probe_rel_err = the probe's max relative cost difference between the fp16 form on fc_wave32_x3p_kernel and
- * three products (-1: no probe ran).  Either pointer may be NULL. */
+ * solve); *probe_rel_err = the probe's max relative cost difference between the fp16 form and three products, the
+ * LARGER of its two runs: on fc_wave32_x3p_kernel and (where that kernel can run the net) on fc_rollout_kernel_x3h
+ * (-1: no probe ran).  Either pointer may be NULL. */
 int mppi_x3_f16(mppi_handle* h, int* on, float* probe_rel_err);
 
 /* Warm start: handle-resident nominal sequence, [B][nu][H] host memory. */

@@ -709,7 +709,7 @@ def test_split_x3d_kernel_matches_x3w_and_oracle(M, B, K, H, cost, terminal, cla
         out[a] for a in ("x3h", "x3d", "x3d_bf16", "x3w", "x3p"))
     assert kern == "fc_rollout_kernel_x3h<f16>", kern
     assert kern_d == "fc_rollout_kernel_x3d<f16>", kern_d
-    for ns in (2, 4):  # NS tiles per wave (kernels_fc_x3h.hip x3h_ns): the same products, in the same order per tile
+    for ns in (2, 4):  # NS tiles per wave (fc_route.h x3h_tiles): the same products, in the same order per tile
         got_n, kern_n = out[f"x3h_ns{ns}"]
         assert kern_n == f"fc_rollout_kernel_x3hw<f16,ns={ns}>", kern_n
         np.testing.assert_allclose(got_n.costs, got.costs, rtol=1e-6)
@@ -991,3 +991,38 @@ def test_config4_64_solves_fp32_accurate(M, net):
         if net == "mlp":
             assert int(np.argmin(res.costs[b])) == int(np.argmin(ref32["costs"]))
     assert well == 3, "the checked solves were expected to be well conditioned"
+
+
+def test_fc_routes_match_recorded(M):
+    """What the engine launches is what fc_route (csrc/fc_route.h) says: the recorded routes of
+    tests/golden/fc_routes.json (tests/test_fc_route.py evaluates the function on every row on the CPU) on both sides
+    of every batch threshold -- for each net and precision, the knob-free rows between which the recorded kernel
+    changes -- replayed through the engine at the recorded shapes (H = 2, injected noise): mppi_rollout_kernel equals
+    the recorded name."""
+    import itertools
+    import torch
+    from test_fc_route import fixture_rows
+    cus, rows = fixture_rows()
+    assert torch.cuda.get_device_properties(0).multi_processor_count == cus, "the routes were recorded on another device"
+    plain = [r for r in rows if not r["knobs"] and r["H"] == 2 and r["K"] == 1024 and r["cost"] == "humanoid_v3"]
+    picked = []
+    for _, grp in itertools.groupby(sorted(plain, key=lambda r: (r["net"], r["precision"], r["B"])),
+                                    key=lambda r: (r["net"], r["precision"])):
+        grp = list(grp)
+        for lo, hi in zip(grp, grp[1:]):
+            if lo["kernel"] != hi["kernel"]:
+                picked += [r for r in (lo, hi) if r not in picked]
+    assert 10 <= len(picked) <= 20, len(picked)
+    assert any(r["kernel"] == "fc_wave32_x3_kernel<f16>" for r in picked)  # exactly 4 wave-tiles per CU
+    blobs = {net: _net(M, net)[0] for net in ("ca", "mlp")}
+    x0_all = golden("g5_ca_humanoid_fwd.npz")["x0_stride20"].astype(np.float32)
+    rs = np.random.RandomState(60)
+    for r in picked:
+        B, K, H = r["B"], r["K"], r["H"]
+        eng = M.Engine(M.Config.preset("humanoid_v3", K=K, H=H, precision=r["precision"], max_batch=B))
+        eng.load_dynamics(*blobs[r["net"]]).set_cost(r["cost"])
+        noise = (0.5 * rs.randn(1, NU, H, K)).astype(np.float32).repeat(B, 0)
+        eng.solve(x0_all[np.arange(B) % len(x0_all)], np.zeros((B, NU, H), np.float32), noise=noise)
+        kern = eng.rollout_kernel()
+        eng.close()
+        assert kern == r["kernel"], (r, kern)
