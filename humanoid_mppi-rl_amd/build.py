@@ -65,6 +65,8 @@ PER_FILE_FLAGS: dict[str, list[str]] = {
     # its fp16 form at one group per block (round 6, late): the same flags
     "kernels_fc_x3h.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
     "kernels_common.hip": ["-fno-slp-vectorize"],
+    # the AR(1) noise generator: the same Philox / Box-Muller VALU code as kernels_common.hip's generators
+    "kernels_noise.hip": ["-fno-slp-vectorize"],
     # the analytic cartpole's 8-step chunks: the iterative-ILP machine scheduler interleaves the steps' independent
     # work into the dependent chain better (config #2 rollout 13.3 -> 12.9 us, same box, two pairs; max-ilp 13.4)
     "kernels_cartpole.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],

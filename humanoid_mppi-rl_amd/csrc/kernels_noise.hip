@@ -1,0 +1,136 @@
+// The configurable sampling law (mppi_set_noise_model): per-actuator scale and AR(1) correlation along the horizon.
+// The law itself is noise_model.h; the default law (white noise of one sigma) stays noise_kernel and the fused
+// generators of kernels_common.hip / kernels_cartpole.hip.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <cstring>
+
+#include "mppi_internal.h"
+#include "noise_model.h"
+#include "philox.h"
+
+namespace mppi {
+
+// ------------------------------------------------------------------------------------------------
+// a1 with the model active: eps[b][u][t][k] = sigma_u[u] * e[t][k], e the AR(1) recursion of noise_model.h over
+// the same normals noise_kernel draws (Philox counter (k/4, t, u, b), key = seed + *seed_ctr).
+// One thread = 4 consecutive k of one (b, u), walking t = 0..H-1: one 16-B nontemporal store per step into row
+// (b*nu + u)*H + t, so a wave's stores stay contiguous in k (1 KiB per wave and step).  The pad lanes K..Kp are
+// written like every other lane, as noise_kernel does.
+// The draws of different t are independent: a tile of kAr1Tile steps is drawn first (Philox + Box-Muller of the tile
+// overlap in the pipeline) and only the one-fma chain e[t] = fma(rho, e[t-1], c z[t]) is serial.
+// grid = (k-quad chunks, b*nu folded over y and z): no 64-bit div/mod per element, u and b are uniform per block.
+// ------------------------------------------------------------------------------------------------
+constexpr int kAr1Tile = 4;
+
+__global__ __launch_bounds__(256) void noise_ar1_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
+                                                        uint64_t seed, const unsigned long long* seed_ctr,
+                                                        NoiseModel m) {
+  const int bu = blockIdx.z * 65535 + blockIdx.y;  // b*nu + u
+  const int kq = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+  if (bu >= nbu || 4 * kq >= Kp) return;
+  const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+  const int u = bu % nu;
+  const int b = bu / nu;
+  const float su = m.sigma_u[u], rho = m.rho, c = m.c;
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const int nq = Kp >> 2;
+  f4* dst = reinterpret_cast<f4*>(noise + (long)bu * H * Kp) + kq;  // row t: dst + t * nq
+  float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int t0 = 0; t0 < H; t0 += kAr1Tile) {
+    float z[kAr1Tile][4];
+#pragma unroll
+    for (int j = 0; j < kAr1Tile; ++j)
+      if (t0 + j < H) philox_normal4((uint32_t)kq, (uint32_t)(t0 + j), (uint32_t)u, (uint32_t)b, k0, k1, z[j]);
+#pragma unroll
+    for (int j = 0; j < kAr1Tile; ++j) {
+      const int t = t0 + j;
+      if (t < H) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) e[i] = t == 0 ? z[j][i] : ar1_step(rho, c, e[i], z[j][i]);
+        const f4 v = {su * e[0], su * e[1], su * e[2], su * e[3]};
+        __builtin_nontemporal_store(v, dst + (long)t * nq);
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same values for grids too small to fill the chip (config #2: one (b, u) row of 16 k-quads, where the kernel
+// above is 16 lanes drawing H = 100 steps one after the other).  One block = kAr1LdsK = 64 consecutive k of one
+// (b, u): its 256 threads first draw all H x 16 (t, k-quad) innovations side by side into LDS ([H][64] floats; row 0
+// holds z[0] itself), then the first wave walks t with one lane per k: an LDS read, the fma, a 4-B nontemporal store
+// per lane (256 contiguous bytes per wave and step).  Same operations in the same order per element as the kernel
+// above, so the two agree bit for bit.  Kp is a multiple of 64 (kKpAlign): every block's 16 quads exist.
+// ------------------------------------------------------------------------------------------------
+constexpr int kAr1LdsK = 64;
+constexpr int kAr1LdsMaxH = 256;  // [H][64] floats <= 64 KiB
+static_assert(kKpAlign % kAr1LdsK == 0, "every block of noise_ar1_lds_kernel owns 64 existing k");
+
+__global__ __launch_bounds__(256) void noise_ar1_lds_kernel(float* __restrict__ noise, int nbu, int nu, int H,
+                                                            int Kp, uint64_t seed,
+                                                            const unsigned long long* seed_ctr, NoiseModel m) {
+  extern __shared__ __attribute__((aligned(16))) float inno[];  // [H][kAr1LdsK]
+  const int bu = blockIdx.z * 65535 + blockIdx.y;  // b*nu + u
+  const int k_base = blockIdx.x * kAr1LdsK;
+  const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+  if (bu >= nbu || k_base >= Kp) return;  // (uniform per block: before the barrier)
+  const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+  const int u = bu % nu;
+  const int b = bu / nu;
+  const float su = m.sigma_u[u], rho = m.rho, c = m.c;
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  constexpr int kQ = kAr1LdsK / 4;  // k-quads per block
+  for (int i = threadIdx.x; i < H * kQ; i += blockDim.x) {
+    const int t = i / kQ, q = i - t * kQ;
+    float z[4];
+    philox_normal4((uint32_t)(k_base / 4 + q), (uint32_t)t, (uint32_t)u, (uint32_t)b, k0, k1, z);
+    f4 v;
+    if (t == 0) v = f4{z[0], z[1], z[2], z[3]};
+    else v = f4{ar1_innovation(c, z[0]), ar1_innovation(c, z[1]), ar1_innovation(c, z[2]), ar1_innovation(c, z[3])};
+    reinterpret_cast<f4*>(inno)[i] = v;  // [t][4 q .. 4 q + 3]
+  }
+  __syncthreads();
+  if (threadIdx.x >= kAr1LdsK) return;
+  float* dst = noise + (long)bu * H * Kp + k_base + threadIdx.x;
+  float e = 0.0f;
+#pragma unroll 4
+  for (int t = 0; t < H; ++t) {
+    const float v = inno[t * kAr1LdsK + threadIdx.x];
+    e = t == 0 ? v : ar1_advance(rho, e, v);
+    __builtin_nontemporal_store(su * e, dst + (long)t * Kp);
+  }
+}
+
+// MPPI_NOISE_AR1=direct|lds (read per launch; an A/B and test knob): force one of the two kernels (lds: where its
+// LDS row fits, H <= 256); default: noise_ar1_lds_kernel when noise_ar1_kernel would have fewer waves than SIMDs
+static int ar1_knob() {
+  const char* e = std::getenv("MPPI_NOISE_AR1");
+  if (!e) return 0;
+  return std::strcmp(e, "direct") == 0 ? 1 : (std::strcmp(e, "lds") == 0 ? 2 : 0);
+}
+
+hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
+                              const unsigned long long* seed_ctr, float sigma, const NoiseModel& model,
+                              hipStream_t stream) {
+  if (!model.active) return launch_noise(noise, B, nu, H, Kp, seed, seed_ctr, sigma, stream);
+  if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_model refuses such a handle)
+  const int nbu = B * nu, nq = Kp / 4;
+  const int knob = ar1_knob();
+  const long waves = ((long)nbu * nq + kWave - 1) / kWave;
+  const bool lds = H <= kAr1LdsMaxH && (knob == 2 || (knob == 0 && waves < 4L * current_device_cus()));
+  if (lds) {
+    const dim3 grid(Kp / kAr1LdsK, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
+    hipLaunchKernelGGL(noise_ar1_lds_kernel, grid, dim3(256), (size_t)H * kAr1LdsK * sizeof(float), stream, noise,
+                       nbu, nu, H, Kp, seed, seed_ctr, model);
+    return hipGetLastError();
+  }
+  const int threads = nq >= 256 ? 256 : (nq + kWave - 1) / kWave * kWave;
+  const dim3 grid((nq + threads - 1) / threads, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
+  hipLaunchKernelGGL(noise_ar1_kernel, grid, dim3(threads), 0, stream, noise, nbu, nu, H, Kp, seed, seed_ctr, model);
+  return hipGetLastError();
+}
+
+}  // namespace mppi

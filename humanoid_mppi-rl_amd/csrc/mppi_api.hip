@@ -14,6 +14,7 @@
 #include "costs.h"
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
+#include "noise_model.h"  // ar1_innovation_scale
 
 namespace mppi {
 std::vector<unsigned char> build_fc_net(int kind, const void* blob, size_t nbytes, int precision, int nx, int nu,
@@ -102,6 +103,7 @@ struct mppi_handle {
   hipEvent_t ev_switch = nullptr;  // mppi_set_stream: the old stream's tail, waited on by the new one
   bool gen_pending = false;     // ev_gen guards the prefetched noise: the solve stream must wait on it before use
   const char* rollout_kernel = "";  // the kernel the last solve's rollout was routed to (mppi_rollout_kernel)
+  NoiseModel noise_model;  // the sampling law (mppi_set_noise_model); inactive = white noise of cfg.sigma
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -675,12 +677,17 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
                              dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     if (!tmp.empty()) HIP_TRY(hipStreamSynchronize(s));
   } else if (!ns) {
-    HIP_TRY(timed(h, kNoise, [&] { return launch_noise(a.noise, B, nu, H, Kp, seed, a.seed_ctr, c.sigma, s); }));
+    HIP_TRY(timed(h, kNoise, [&] {
+      return launch_noise_model(a.noise, B, nu, H, Kp, seed, a.seed_ctr, c.sigma, h->noise_model, s);
+    }));
   }
 
   // ---- a2-a6: rollout + cost; a7-a9: softmin + weighted-noise reduce + update + shift
   const NoiseGen gen{ns ? ns->next : nullptr, seed, c.sigma, h->d_gticket};
-  const NoiseGen* pg = ns && ns->next ? &gen : nullptr;
+  // an active noise model's rows depend on the row before them, which the fused generators (one row at a time, in
+  // reduce order) cannot give: the next noise then comes from its own launch behind the reduce (below)
+  const bool gen_after = ns && ns->next && h->noise_model.active;
+  const NoiseGen* pg = ns && ns->next && !gen_after ? &gen : nullptr;
   if (h->dyn_kind == MPPI_DYN_CARTPOLE) {  // one launch: the rollout blocks finish the solve (fused epilogue)
     a.part = h->d_part;
     HIP_TRY(timed(h, kRollout, [&] { return launch_cartpole_rollout(a, h->cart, pg, s); }));
@@ -689,6 +696,12 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
     h->rollout_kernel = g_rollout_kernel;
     HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(a, pg, s); }));
+  }
+  if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
+    HIP_TRY(timed(h, kNoise, [&] {
+      return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s);
+    }));
+    HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, s));
   }
 
   // ---- env step: x0 <- f(x0, u0), the rollout kernel over one sample, one step, zero noise, U = u0, final
@@ -777,8 +790,8 @@ static int prime_prefetch(mppi_handle* h, int B, uint64_t seed) {
   if (h->prefetch_valid && (h->prefetch_B != B || h->prefetch_seed != seed)) HIP_TRY(drop_prefetch(h));
   if (h->prefetch_valid) return MPPI_OK;
   const mppi_config& c = h->cfg;
-  HIP_TRY(launch_noise(h->graph_parity ? h->d_noise2 : h->d_noise, B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr, c.sigma,
-                       h->stream));
+  HIP_TRY(launch_noise_model(h->graph_parity ? h->d_noise2 : h->d_noise, B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr,
+                             c.sigma, h->noise_model, h->stream));
   HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->stream));
   h->prefetch_valid = true;
   h->prefetch_B = B;
@@ -840,7 +853,8 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   // generator stream alone reads and bumps the key counter from here on, in launch order
   HIP_TRY(hipEventRecord(h->ev_red, h->stream));  // = the previous reduce (everything enqueued so far)
   HIP_TRY(hipStreamWaitEvent(h->gstream, h->ev_red, 0));
-  HIP_TRY(launch_noise(buf[h->graph_parity ^ 1], B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr, c.sigma, h->gstream));
+  HIP_TRY(launch_noise_model(buf[h->graph_parity ^ 1], B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr, c.sigma,
+                             h->noise_model, h->gstream));
   HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->gstream));
   HIP_TRY(hipEventRecord(h->ev_gen, h->gstream));
   h->gen_pending = true;
@@ -867,7 +881,8 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
 // three-product costs
 // (FcNet::x3_f16 = 1, x3_f16_err = the larger error), else not (-1).  The probe covers up to kProbeB of the first batch's solves at kProbeK samples
 // each: the CA surrogate's dynamics do not depend on the controls (its action encoder never reaches the output), so
-// the form's error is one number per state -- more states, not more samples, find the worst.
+// the form's error is one number per state -- more states, not more samples, find the worst.  For the same reason the
+// probe keeps its own white noise of cfg.sigma whatever mppi_set_noise_model selected: it is a per-state measure.
 static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if (h->dyn_kind != MPPI_DYN_CROSS_ATTN || h->cfg.precision != MPPI_PREC_BF16X3 || h->net.arch != kArchCA ||
       h->net.x3_l1 != 0)
@@ -1142,6 +1157,48 @@ int mppi_get_seed_counter(mppi_handle* h, uint64_t* value) {
   // is already prefetched and the device counter already advanced past its key (drop_prefetch steps it back for the
   // same reason), so mppi_set_seed_counter(value) -- which drops any prefetch -- resumes the stream exactly
   *value = h->prefetch_valid ? v - 1 : v;
+  return MPPI_OK;
+}
+
+int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_model: null handle");
+  if (!(rho >= 0.0f && rho < 1.0f)) return fail(MPPI_E_ARG, "mppi_set_noise_model: rho must be in [0, 1)");
+  const int nu = h->cfg.nu;
+  if (sigma_u)
+    for (int u = 0; u < nu; ++u)
+      if (!(std::isfinite(sigma_u[u]) && sigma_u[u] >= 0.0f))
+        return fail(MPPI_E_ARG, "mppi_set_noise_model: sigma_u[" + std::to_string(u) + "] must be finite and >= 0");
+  // (NULL, 0) = the default law, exactly the code path of a handle without a model
+  const bool active = sigma_u != nullptr || rho != 0.0f;
+  if (active && nu > kMaxNu)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_model: the model travels as a kernel argument (nu <= 32)");
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state: a prefetched noise was drawn with the old law (the counter steps back: the key sequence is unchanged),
+  // and the captured graphs hold the old model in their kernel arguments (a launch still in flight finishes first)
+  HIP_TRY(drop_prefetch(h));
+  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
+  for (hipGraphExec_t& g : h->graph_exec)
+    if (g) {
+      HIP_TRY(hipGraphExecDestroy(g));
+      g = nullptr;
+    }
+  NoiseModel m;
+  m.active = active ? 1 : 0;
+  m.rho = rho;
+  m.c = ar1_innovation_scale(rho);
+  if (active)
+    for (int u = 0; u < nu; ++u) m.sigma_u[u] = sigma_u ? sigma_u[u] : h->cfg.sigma;
+  h->noise_model = m;
+  return MPPI_OK;
+}
+
+int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_model: null handle");
+  const NoiseModel& m = h->noise_model;
+  if (sigma_u)
+    for (int u = 0; u < h->cfg.nu; ++u) sigma_u[u] = m.active ? m.sigma_u[u] : h->cfg.sigma;
+  if (rho) *rho = m.rho;
+  if (active) *active = m.active;
   return MPPI_OK;
 }
 

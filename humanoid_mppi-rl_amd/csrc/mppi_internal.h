@@ -248,6 +248,20 @@ struct FaNet {
 hipError_t launch_noise(float* noise, int B, int nu, int H, int Kp, uint64_t seed, const unsigned long long* seed_ctr,
                         float sigma, hipStream_t stream);
 hipError_t launch_seed_bump(unsigned long long* seed_ctr, long long delta, hipStream_t stream);  // += delta
+// The sampling law (mppi_set_noise_model; noise_model.h), a kernel argument by value: no device allocation, so a
+// solve that generates with it stays graph-capturable.  active = 0: the default law (white noise of cfg.sigma, the
+// fused generators); active = 1: eps = sigma_u[u] * AR(1)(rho) from noise_ar1_kernel (kernels_noise.hip), nu <= kMaxNu.
+struct NoiseModel {
+  int active = 0;
+  float rho = 0.0f;
+  float c = 1.0f;  // sqrtf(1 - rho*rho), fp32, computed on the host
+  float sigma_u[kMaxNu] = {0};
+};
+// every explicit generation site: noise_kernel (inactive model, sigma) or, with the model active, noise_ar1_kernel /
+// noise_ar1_lds_kernel (grids too small to fill the chip); kernels_noise.hip
+hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
+                              const unsigned long long* seed_ctr, float sigma, const NoiseModel& model,
+                              hipStream_t stream);
 // fc-stack rollout: fc_route (fc_route.h) decides the kernel from the shape, the image, the probe outcomes and the
 // knobs; launch_fc_route launches a given route (the engine's probe passes routes of its own)
 struct FcRoute;

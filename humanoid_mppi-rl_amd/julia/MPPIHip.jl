@@ -193,6 +193,25 @@ function x3_layer1(c::Controller)
     return (Int(prod[]), Float32(err[]))
 end
 
+"""
+    set_noise_model!(c; sigma_u = nothing, rho = 0.0)
+
+The sampling law of the device noise (mppi_set_noise_model): per-actuator standard deviations `sigma_u` (length nu;
+`nothing` = the preset's sigma for all) and the AR(1) correlation `rho` in [0, 1) along the horizon.
+`set_noise_model!(c)` restores the default white noise.
+"""
+function set_noise_model!(c::Controller; sigma_u = nothing, rho::Real = 0.0)
+    if sigma_u === nothing
+        check(ccall((:mppi_set_noise_model, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cfloat), c.handle, C_NULL, rho))
+    else
+        s = Float32.(vec(collect(sigma_u)))
+        length(s) == c.cfg.nu || throw(ArgumentError("sigma_u must have nu = $(c.cfg.nu) entries"))
+        GC.@preserve s check(ccall((:mppi_set_noise_model, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cfloat), c.handle,
+                                   pointer(s), rho))
+    end
+    return c
+end
+
 "rollout_kernel: the kernel the last solve was routed to (mppi_rollout_kernel; ABI 3)."
 rollout_kernel(c::Controller) = unsafe_string(ccall((:mppi_rollout_kernel, LIB), Cstring, (Ptr{Cvoid},), c.handle))
 

@@ -25,6 +25,7 @@ import numpy as np
 from . import _lib as L
 from .engine import Config, Engine
 from .nets import cross_attention_blob, feature_attention_blob, mlp_blob
+from .noise import ar1_filter
 
 # default cost of each preset (the reference script it mirrors)
 PRESET_COST = {"cartpole_py": "cartpole", "cartpole_jl": "cartpole", "cartpole_collect": "cartpole",
@@ -50,11 +51,14 @@ class MPPIModel:
     noise:    "device" -> Philox on the GPU (seeded, advances per call);
               "numpy"  -> np.random.randn(nu,T,K)*sigma from numpy's global RNG, exactly the reference's draw
                           (src/cartpole_mppi.py:89), injected into the engine.
+    noise_sigma, noise_rho: the sampling law (Engine.set_noise_model): per-actuator standard deviations [nu] (None =
+              the preset's sigma) and AR(1) correlation along the horizon; both noise modes sample the same law.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
                  noise: str = "device", seed: int = 0, precision: int = L.PREC_BF16, ctx=None,
-                 body_ids: dict | None = None, u0_before: bool = False, **overrides):
+                 body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
+                 **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -84,6 +88,10 @@ class MPPIModel:
         self.target = tuple(float(v) for v in np.asarray(ctx, np.float64).ravel()[:3]) if ctx is not None \
             else HUMANOID_TARGET
         self.U_global = np.zeros((self.config.nu, self.config.H))
+        self.noise_sigma = None if noise_sigma is None else np.asarray(noise_sigma, np.float64).ravel()
+        self.noise_rho = float(noise_rho)
+        if self.noise_sigma is not None or self.noise_rho != 0.0:
+            self.engine.set_noise_model(self.noise_sigma, self.noise_rho)
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0
@@ -100,7 +108,10 @@ class MPPIModel:
     def draw_noise(self):
         c = self.config
         if self.noise == "numpy":
-            return np.random.randn(c.nu, c.H, c.K) * c.sigma
+            z = np.random.randn(c.nu, c.H, c.K)
+            if self.noise_sigma is None and self.noise_rho == 0.0:
+                return z * c.sigma
+            return ar1_filter(z, self.noise_rho, c.sigma if self.noise_sigma is None else self.noise_sigma)
         return None
 
     def next_seed(self) -> int:

@@ -272,7 +272,10 @@ def solve_k_sharded(solve_shard: Callable, x0: np.ndarray, U: np.ndarray, lam: f
     solve_shard(x0, U) -> (costs [K_r], dU_r [nu, H]) runs this rank's shard (e.g. Engine.solve on an engine created
     with update_mode = replace, no U clamp, no shift, and a rank-specific seed).  Then the exact combine above, and
     the update of the reference controller on the combined dU: add or replace, clamp, u0 = U[:, 0], and the shift
-    when shift_fill is given (src/cartpole_mppi.py:96-106, src/mppi.jl:91-98).  Returns (U_new, u0)."""
+    when shift_fill is given (src/cartpole_mppi.py:96-106, src/mppi.jl:91-98).  Returns (U_new, u0).
+
+    K-sharded solves keep the default sampling law (white noise of one sigma): the shards' engines are not given a
+    noise model (Engine.set_noise_model) here."""
     costs, dU_r = solve_shard(x0, U)
     dU = combine_k_shards(costs, dU_r, lam, norm_eps, group)
     Un = dU if update == "replace" else np.asarray(U, np.float64) + dU

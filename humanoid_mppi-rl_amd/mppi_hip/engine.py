@@ -109,6 +109,27 @@ class Engine:
             L.check(self.lib.mppi_set_cost(self._h, kind, p.ctypes.data_as(L._fp), int(p.size)))
         return self
 
+    def set_noise_model(self, sigma_u=None, rho: float = 0.0):
+        """The sampling law of the device noise (mppi_set_noise_model): per-actuator standard deviations sigma_u [nu]
+        (None = config.sigma for all) and the AR(1) correlation rho in [0, 1) along the horizon (noise.ar1_filter
+        states the law).  (None, 0.0) restores the default white noise and its code path."""
+        p = None
+        if sigma_u is not None:
+            s = _f32(sigma_u).ravel()
+            if s.size != self.config.nu:
+                raise ValueError(f"set_noise_model: sigma_u must have nu = {self.config.nu} entries, got {s.size}")
+            p = s.ctypes.data_as(L._fp)
+        L.check(self.lib.mppi_set_noise_model(self._h, p, ctypes.c_float(rho)))
+        return self
+
+    def noise_model(self) -> tuple[np.ndarray, float, bool]:
+        """(sigma_u [nu], rho, active) of the handle's sampling law (mppi_get_noise_model)."""
+        s = np.empty(self.config.nu, np.float32)
+        rho, active = ctypes.c_float(), ctypes.c_int()
+        L.check(self.lib.mppi_get_noise_model(self._h, s.ctypes.data_as(L._fp), ctypes.byref(rho),
+                                              ctypes.byref(active)))
+        return s, float(rho.value), bool(active.value)
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,

@@ -61,7 +61,9 @@ extern "C" {
  *      returns the LOGICAL counter (the key the next solve draws) also after chained solves and graph launches,
  *      whose prefetched noise had already advanced the device counter by one.
  *   4  mppi_x3_f16.  BEHAVIOUR CHANGE: MPPI_PREC_BF16X3 CrossAttention solves run the fp16 form when the engine's
- *      probe of the loaded weights allows it (below). */
+ *      probe of the loaded weights allows it (below).
+ *      Additive, version unchanged: mppi_set_noise_model / mppi_get_noise_model (per-actuator sigma and AR(1)
+ *      correlation of the device noise).  A handle that never calls them behaves exactly as before. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -210,6 +212,23 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
  * (set drops any prefetch) continues a plain, chained or graph stream with the noise it would have drawn. */
 int mppi_set_seed_counter(mppi_handle* h, uint64_t value);
 int mppi_get_seed_counter(mppi_handle* h, uint64_t* value);
+
+/* The sampling law of the DEVICE noise (injected io.noise is taken as given).  Default: white noise, one cfg.sigma
+ * for every actuator.  With z[b][u][t][k] the standard normals of the default law (same Philox counters and keys):
+ *     e[0] = z[0];   e[t] = fmaf(rho, e[t-1], c z[t]),  c = sqrtf(1 - rho^2) in fp32;   eps = sigma_u[u] e[t]
+ * i.e. unit variance at every step before scaling and corr(e[t], e[s]) = rho^|t-s|.
+ * sigma_u: [nu] per-actuator standard deviations (finite, >= 0; 0 freezes an actuator) or NULL = cfg.sigma for all;
+ * 0 <= rho < 1; anything else is MPPI_E_ARG and leaves the model as it was.  (NULL, 0) restores the default law and
+ * its code path (*active = 0); every other setting is *active = 1 and generates with its own kernel, also when its
+ * values equal the default's (then value for value the same noise).  An active model needs nu <= 32
+ * (MPPI_E_UNSUPPORTED otherwise).  Allowed any time after mppi_create, also between solves of a plain, chained or graph
+ * stream: the noise-key sequence is unchanged (a prefetched noise is dropped and its key drawn again), captured graphs
+ * are destroyed (mppi_graph_launch returns MPPI_E_STATE until the next mppi_graph_capture).  Chained solves, graph
+ * streams, trajectory logging and the seed counter work as with the default law and draw the keys a loop of plain
+ * counter solves draws.
+ * mppi_get_noise_model: sigma_u [nu] or NULL, rho, active; each pointer may be NULL. */
+int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho);
+int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active);
 
 /* MPPI_PREC_BF16X3 with a CrossAttention net: *products = the products layer 1 runs with (2 or 3; 0 = not a split CA
  * handle, or no solve yet), *probe_rel_err = the probe's max relative cost difference between the two forms (-1: no
