@@ -185,7 +185,7 @@ inline FcRoute fc_route_msplit(int arch, int precision, const SolveArgs& a, int 
 
 // arch / precision: FcNet's; a: the solve's shape (B, Kp, H, nx, nu); fa: the image; x3_l1 / x3_f16: FcNet's probe
 // outcomes; cus: the device's CU count.  The fp16 form (form 0 / 1) runs on x3p and x3h, which the engine's probe both
-// checks on the loaded net, and on x3_wave32, which it does not.
+// checks on the loaded net, and on x3_wave32, which it does not (tests/test_gpu_split_offprobe.py does).
 inline FcRoute fc_route(int arch, int precision, const SolveArgs& a, const FcArgs& fa, int x3_l1, int x3_f16, int cus,
                         const FcKnobs& k) {
   if (arch == kArchGeneric) return {FcKernel::generic, precision, 1};
@@ -204,8 +204,11 @@ inline FcRoute fc_route(int arch, int precision, const SolveArgs& a, const FcArg
     if (precision == MPPI_PREC_BF16X3) {
       // the per-wave kernels from 4 wave-tiles per CU (one per SIMD).  BOUNDARY: x3_wave32 takes wts32 >= 4 cus, but
       // x3p only wts32 > 4 cus, so at EXACTLY 4 wave-tiles per CU (the 32-solve shard of config #4 on 256 CUs) the
-      // form -- the fp16 one included -- runs on x3_wave32, a kernel the probe never checked (ADVICE.md, round 6,
-      // second item).  Kept as it is (tests/test_fc_route.py pins it); moving it is a behaviour change.
+      // form -- the fp16 one included -- runs on x3_wave32, a kernel the probe does not run (ADVICE.md, round 6,
+      // second item).  Its fp16 form is held to the fp32 oracle at the full horizon, on logged states and on states
+      // no probe saw, and to x3p within 8e-5, by tests/test_gpu_split_offprobe.py
+      // (test_wave32_fp16_form_at_full_horizon, test_fp16_form_holds_off_probe[x3_wave32-*]).  Kept as it is
+      // (tests/test_fc_route.py pins it); moving it is a behaviour change.
       if (fc_route_can_run(FcKernel::x3_wave32, a, fa) &&
           (k.x3_wave == 2 || (k.x3_wave == 1 && wts32 >= kWaveX3Waves * cus))) {
         const bool pair = k.x3_pair >= 0 ? k.x3_pair == 1 : wts32 > kWaveX3Waves * cus;

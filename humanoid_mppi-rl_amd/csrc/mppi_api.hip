@@ -61,6 +61,9 @@ struct mppi_handle {
   float cost_params[MPPI_CTX_MAX] = {0};
   CartpoleParams cart{};
   FcNet net;
+  // MPPI_PREC_BF16X3 only: the same net packed for exact fp32, which the env step runs (launch_rollout): its output is
+  // the next STATE, and the split forms are fp32-accurate in the costs (what x3_probe measures), not entry by entry
+  FcNet net_env;
   FaNet fa;
   // device buffers (sized for cfg.max_batch)
   float *d_x0 = nullptr, *d_U = nullptr, *d_noise = nullptr, *d_costs = nullptr, *d_dU = nullptr;
@@ -225,8 +228,8 @@ void mppi_destroy(mppi_handle* h) {
   harvest_events(h);
   for (hipEvent_t e : h->evt_pool) (void)hipEventDestroy(e);
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
-                  h->d_tickets, const_cast<char*>(h->net.fa.img), h->fa.d_img, h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs,
-                  h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock};
+                  h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
+                  h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -312,10 +315,12 @@ int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes
   }
   if (kind == MPPI_DYN_MLP || kind == MPPI_DYN_CROSS_ATTN) {
     if (!blob || nbytes == 0) return fail(MPPI_E_ARG, "mppi_load_dynamics: weight blob required");
-    std::vector<unsigned char> img;
-    FcNet net;
+    std::vector<unsigned char> img, img_env;
+    FcNet net, net_env;
     try {
       img = build_fc_net(kind, blob, nbytes, h->cfg.precision, h->cfg.nx, h->cfg.nu, net);
+      if (h->cfg.precision == MPPI_PREC_BF16X3)
+        img_env = build_fc_net(kind, blob, nbytes, MPPI_PREC_FP32, h->cfg.nx, h->cfg.nu, net_env);
     } catch (const std::exception& ex) {
       return fail(MPPI_E_UNSUPPORTED, std::string("mppi_load_dynamics: ") + ex.what());
     }
@@ -328,8 +333,21 @@ int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes
       (void)hipFree(d);
       return fail(MPPI_E_HIP, std::string("mppi_load_dynamics: image upload: ") + hipGetErrorString(e));
     }
+    void* d_env = nullptr;
+    if (!img_env.empty()) {
+      hipError_t e = hipMalloc(&d_env, img_env.size());
+      if (e == hipSuccess) e = hipMemcpy(d_env, img_env.data(), img_env.size(), hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        (void)hipFree(d);
+        (void)hipFree(d_env);
+        return fail(MPPI_E_HIP, std::string("mppi_load_dynamics: env-step image upload: ") + hipGetErrorString(e));
+      }
+    }
     if (h->net.fa.img) (void)hipFree(const_cast<char*>(h->net.fa.img));
+    if (h->net_env.fa.img) (void)hipFree(const_cast<char*>(h->net_env.fa.img));
     net.fa.img = static_cast<const char*>(d);
+    net_env.fa.img = static_cast<const char*>(d_env);
+    h->net_env = net_env;
     net.x3_l1 = 0;  // a new net: the split layer-1 probe runs again at the next solve (x3_probe)
     h->net = net;
     h->dyn_kind = kind;
@@ -403,6 +421,22 @@ int mppi_set_cost(mppi_handle* h, int kind, const float* params, int nparams) {
     def[2] = 0.35f;
   }
   for (int i = 0; i < nparams; ++i) def[i] = params[i];
+  if (h->net.x3_l1 != 0) {
+    // the split CA's probe (x3_probe) measured a relative COST error under the cost it found: a new cost returns the
+    // handle to "not probed" and the next solve (or capture) probes again.  Graphs captured under the old decision
+    // are stale the way mppi_set_noise_model's are (a launch still in flight finishes first)
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
+    for (hipGraphExec_t& g : h->graph_exec)
+      if (g) {
+        HIP_TRY(hipGraphExecDestroy(g));
+        g = nullptr;
+      }
+    h->net.x3_l1 = 0;
+    h->net.x3_l1_err = -1.0f;
+    h->net.x3_f16 = 0;
+    h->net.x3_f16_err = -1.0f;
+  }
   std::memcpy(h->cost_params, def, sizeof(def));
   h->cost_kind = kind;
   return MPPI_OK;
@@ -561,6 +595,7 @@ static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
 static hipError_t launch_rollout(mppi_handle* h, const SolveArgs& a, hipStream_t s) {
   if (h->dyn_kind == MPPI_DYN_CARTPOLE) return launch_cartpole_rollout(a, h->cart, nullptr, s);
   if (h->dyn_kind == MPPI_DYN_FEATURE_ATTN) return launch_fa_rollout(a, h->fa, s);
+  if (a.xout && h->net_env.fa.img) return launch_fc_rollout(a, h->net_env, s);  // the split mode's env step: exact fp32
   return launch_fc_rollout(a, h->net, s);
 }
 
@@ -872,8 +907,11 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
 // context) through the same routed kernel twice, with two and with three products on layer 1, and keeps the two-product
 // form only if the costs agree within kX3ProbeTol (relative, every finite cost; a non-finite mismatch fails it).  Three
 // products are within ~1.5e-6 of the fp32 oracle (profiles/r05_x3_error_budget.txt), so the difference measures the
-// two-product form's own error on this net, these states and this horizon.  Runs once per loaded net, on the handle's
-// stream, with its own buffers (no effect on the noise counter, the prefetched noise or U), before any graph capture.
+// two-product form's own error on this net, these states, this cost and this horizon.  Runs once per loaded net and
+// cost (mppi_load_dynamics and mppi_set_cost reset it), on the handle's stream, with its own buffers (no effect on the
+// noise counter, the prefetched noise or U), before any graph capture.  The decision then holds for every later solve
+// and every replay of a captured graph, on states the probe never saw: tests/test_gpu_split_offprobe.py holds those to
+// the same 1e-4 bar (DESIGN.md §4 has the figures).
 // Horizons beyond kX3TwoTermMaxH keep three products without a probe (the error grows ~H^2); MPPI_X3_L1_TERMS forces.
 // The same run decides the fp16 form (fc_route.h x3_f16_on): one more rollout of the same inputs through each kernel
 // the probe covers -- fc_wave32_x3p_kernel (the large batches) and fc_rollout_kernel_x3h (the few-tiles shards), by

@@ -113,7 +113,16 @@ extern "C" {
                               fp16 operand) and the last layer as two too, fp32 accumulate, when the same probe finds
                               it within 7.5e-5 of three products (H <= 64); mppi_x3_f16 reports it.  Env
                               MPPI_X3_F16=0 (=1) forces the form off (on) without a probe; MPPI_X3_F16_L2=1 opts into
-                              a one-product last layer (faster, NOT fp32-accurate on every state). */
+                              a one-product last layer (faster, NOT fp32-accurate on every state).
+                              SCOPE of the probe: it runs once per loaded net and cost (mppi_load_dynamics and
+                              mppi_set_cost reset it), on up to 64 states of the first solve -- or of the first
+                              capture: a captured graph replays the decision made before the capture on whatever states
+                              its env steps reach, the host does not look again.  Every later solve keeps the decision;
+                              tests/test_gpu_split_offprobe.py holds it to the 1e-4 bar on states the probe never saw
+                              (worst measured 9.4e-5).  The bar is on the COSTS (and U / u0): entry by
+                              entry a state that went through the reduced forms is only ~1e-3 accurate, so
+                              MPPI_FLAG_ENV_STEP, whose output is the next state, runs the net in exact fp32 in this
+                              mode (a second, fp32 image of the weights loaded beside the split one). */
 
 /* ---- solve flags ---- */
 #define MPPI_FLAG_SHIFT 0x1        /* controller step: u0_out = U[:,0], shift U left, fill last  */
@@ -183,7 +192,12 @@ void mppi_destroy(mppi_handle* h);
  * MPPI_DYN_CARTPOLE blob may be NULL (models/cartpole.xml constants) or 10 floats. */
 int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes);
 
-/* params: cost-kind specific floats (may be NULL => reference defaults). */
+/* params: cost-kind specific floats (may be NULL => reference defaults).
+ * MPPI_PREC_BF16X3 with a CrossAttention net: the probe behind mppi_x3_layer1 / mppi_x3_f16 measures a relative COST
+ * difference under the cost in effect, so a call after the probe ran returns the handle to "not probed" (both report 0
+ * again, as after mppi_load_dynamics) and the next solve or capture probes under the new cost.  Graphs captured
+ * before the call hold the old decision (and the old cost) and are destroyed, as by mppi_set_noise_model:
+ * mppi_graph_launch returns MPPI_E_STATE until the next mppi_graph_capture. */
 int mppi_set_cost(mppi_handle* h, int kind, const float* params, int nparams);
 
 /* Survey 8(b) signature: plain pointers, host memory unless MPPI_FLAG_DEVICE. */

@@ -815,7 +815,7 @@ def test_env_step_with_forced_wave_kernels(M, net):
             np.testing.assert_allclose(out[wave], out["0"], rtol=2e-2, atol=2e-3)
 
 
-@pytest.mark.parametrize("kind,precision", [("cartpole", 0), ("ca", 1), ("fa", 1)])
+@pytest.mark.parametrize("kind,precision", [("cartpole", 0), ("ca", 1), ("fa", 1), ("ca", 2)])
 def test_graph_stream_replays_the_solve_loop(M, kind, precision):
     """mppi_graph_capture of n chained solves (shift + env step, seed counter) == the same n solves issued one
     by one, bitwise; a second replay continues the stream (fresh noise keys)."""
@@ -848,14 +848,15 @@ def test_graph_stream_replays_the_solve_loop(M, kind, precision):
         np.testing.assert_array_equal(a, b)
 
 
-@pytest.mark.parametrize("kind", ["cartpole", "ca"])
-def test_stream_trajectory_log(M, kind):
+@pytest.mark.parametrize("kind,precision", [("cartpole", 0), ("ca", 0), ("ca", 2)])
+def test_stream_trajectory_log(M, kind, precision):
     """mppi_graph_capture_traj: the logged (x_t, u_t) rows are the states the env steps started from and the
-    controls they applied; x_{t+1} = f(x_t, u_t) (oracle step); rows equal an explicit solve loop bitwise."""
+    controls they applied; x_{t+1} = f(x_t, u_t) (fp32 oracle step, also for the split mode: precision 2 is held to
+    the fp32 bar); rows equal an explicit solve loop bitwise."""
     import torch
     from mppi_hip.trajectory import run_stream
     K, H, B, n = 128, 10, 2, 6
-    eng, x0, U0, f = _dev_setup(M, kind, K, H, B, precision=0)
+    eng, x0, U0, f = _dev_setup(M, kind, K, H, B, precision=precision)
     states, actions, U_end = run_stream(eng, x0, U0, n, seed=4, launches=2)
     assert states.shape == (2 * n, B, x0.shape[1])
     np.testing.assert_array_equal(states[0], x0)
@@ -864,7 +865,7 @@ def test_stream_trajectory_log(M, kind):
             ref = f(states[i, b].astype(np.float64), actions[i, b].astype(np.float64))
             np.testing.assert_allclose(states[i + 1, b], ref, rtol=1e-4, atol=1e-5)
     # the same solves issued one by one
-    eng2, _, _, _ = _dev_setup(M, kind, K, H, B, precision=0)
+    eng2, _, _, _ = _dev_setup(M, kind, K, H, B, precision=precision)
     dev = torch.device("cuda")
     eng2.set_stream(torch.cuda.current_stream().cuda_stream)
     tx, tU = torch.from_numpy(x0).to(dev), torch.from_numpy(U0).to(dev)
@@ -878,7 +879,43 @@ def test_stream_trajectory_log(M, kind):
     np.testing.assert_array_equal(tU.cpu().numpy(), U_end)
 
 
-@pytest.mark.parametrize("kind,precision", [("cartpole", 0), ("ca", 1)])
+def test_split_stream_states_meet_the_fp32_bar(M):
+    """A long-lived split-mode handle (precision 2) decides its fp16 form once, on the stream's first states, and a
+    receding-horizon stream then solves states it never probed.  32 steps of a captured stream (B = 4, K = 64, H = 64,
+    the horizon where the form's error peaks); the logged states of steps 0, 15 and 31 are solved again with injected
+    noise on the streamed handle (its decision is 32 steps old) and on a fresh handle (which probes on those very
+    states): both within rtol 1e-4 of the fp32 oracle on every solve."""
+    from mppi_hip.trajectory import run_stream
+    K, H, B, n = 64, 64, 4, 16
+    eng, x0, U0, _ = _dev_setup(M, "ca", K, H, B, precision=2)
+    states, _, _ = run_stream(eng, x0, U0, n, seed=4, launches=2)
+    assert states.shape == (2 * n, B, 55) and np.isfinite(states).all()
+    assert eng.x3_f16()[1] >= 0.0  # the probe ran, before the first capture
+    rs = np.random.RandomState(63)
+    U = (0.1 * rs.randn(B, 21, H)).astype(np.float32)
+    noise = (0.75 * rs.randn(B, 21, H, K)).astype(np.float32)
+    cfg = eng.config
+    pre = R.Preset("stream", K=K, H=H, lam=cfg.lambda_, sigma=0.75, terminal_weight=cfg.terminal_weight)
+    dyn = N.learned_dynamics(N.ca_fold(golden_sd("ca_humanoid_weights.npz"), 28, 27, 21), 55, precision="fp32")
+    ctx = np.array([2.0, 0, 1.28, 0, 0, 0, 0, 0])  # mppi_set_cost's humanoid_v3 defaults
+    for step in (0, 15, 31):
+        xs = states[step]
+        fresh, _ = _ca_setup(M, K, H, 2, B=B)
+        fresh.set_cost("humanoid_v3")
+        got = {"fresh": fresh.solve(xs, U, noise=noise).costs, "streamed": eng.solve(xs, U, noise=noise).costs}
+        kern = {"fresh": fresh.rollout_kernel(), "streamed": eng.rollout_kernel()}
+        fresh.close()
+        for b in range(B):
+            ref = R.rollout(pre, dyn, R.humanoid_v3_cost, xs[b], U[b], noise[b], ctx=ctx, dtype=np.float32)
+            for who, costs in got.items():
+                err = float(np.max(np.abs(costs[b] - ref) / np.abs(ref)))
+                print(f"step {step} solve {b} {who} ({kern[who]}): rel err {err:.3e}")
+                assert np.isfinite(costs[b]).all() and err <= 1e-4, (
+                    f"step {step}, solve {b}, {who} handle ({kern[who]}): rel err {err:.3e} vs the fp32 oracle")
+    eng.close()
+
+
+@pytest.mark.parametrize("kind,precision", [("cartpole", 0), ("ca", 1), ("ca", 2)])
 def test_graph_noise_prefetch_mixed_with_plain_solves(M, kind, precision):
     """Graph streams generate the next solve's noise inside the current solve's reduce (double-buffered, one
     counter value ahead). Interleaving graph launches (odd and even stream lengths, a re-capture) with plain
@@ -1122,7 +1159,7 @@ def test_max_tokens_feature_attention(M):
 
 
 @pytest.mark.parametrize("overlap", ["1", "0", "toggle"])
-@pytest.mark.parametrize("kind,precision", [("cartpole", 0), ("ca", 1), ("fa", 1)])
+@pytest.mark.parametrize("kind,precision", [("cartpole", 0), ("ca", 1), ("fa", 1), ("ca", 2)])
 def test_chained_solves_equal_plain_solves(M, kind, precision, overlap):
     """MPPI_FLAG_CHAIN (the stream-launched form of a graph stream: the next solve's noise prefetched, by default inside
     the reduce, reduce_kernel<GEN>; MPPI_GEN_OVERLAP=1, an A/B arm, on the handle's generator stream concurrently with
