@@ -40,8 +40,8 @@ static int fail(int code, const std::string& msg) {
 
 namespace {
 
-enum KernelId { kNoise = 0, kRollout = 1, kReduce = 2, kUpdate = 3, kNumKernels = 4 };
-const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update"};
+enum KernelId { kNoise = 0, kRollout = 1, kReduce = 2, kUpdate = 3, kStats = 4, kNumKernels = 5 };
+const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats"};
 
 struct PendingEvt {
   int id;
@@ -107,6 +107,15 @@ struct mppi_handle {
   bool gen_pending = false;     // ev_gen guards the prefetched noise: the solve stream must wait on it before use
   const char* rollout_kernel = "";  // the kernel the last solve's rollout was routed to (mppi_rollout_kernel)
   NoiseModel noise_model;  // the sampling law (mppi_set_noise_model); inactive = white noise of cfg.sigma
+  // solve diagnostics (MPPI_FLAG_STATS; kernels_stats.hip), allocated by ensure_stats before the first flagged solve or
+  // capture.  Outputs are slot-major with max_batch as the batch pitch: stats_slots slots for solves (a graph's solve i
+  // writes slot i) and one more, the last, for mppi_stats_eval, so an evaluation leaves a solve's statistics readable.
+  mppi_solve_stats* d_stats = nullptr;              // [stats_slots + 1][max_batch]
+  float *d_stats_m2 = nullptr, *d_stats_m11 = nullptr;  // [stats_slots + 1][max_batch][nu]
+  float *d_stats_w = nullptr, *d_stats_part = nullptr;  // scratch: normalised weights [max_batch][Kp], cell partials
+  int stats_slots = 0;
+  int stats_B = 0, stats_n = 0;  // batch and slot count of the last flagged solve / graph launch (0: none ran)
+  bool graph_stats = false;      // the captured graph carries the flag
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -229,7 +238,8 @@ void mppi_destroy(mppi_handle* h) {
   for (hipEvent_t e : h->evt_pool) (void)hipEventDestroy(e);
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
-                  h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock};
+                  h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
+                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -570,6 +580,47 @@ int mppi_set_U(mppi_handle* h, int B, const float* U) {
 
 }  // extern "C"
 
+// The diagnostics' buffers for `slots` solve slots (+ 1 for mppi_stats_eval).  Growing them (a graph with more solves
+// than any before) waits for the stream and forgets the statistics held so far.  Never called inside a capture.
+static int ensure_stats(mppi_handle* h, int slots) {
+  const mppi_config& c = h->cfg;
+  const size_t B = (size_t)c.max_batch;
+  if (!h->d_stats_w) {
+    const size_t nw = B * h->Kp * 4, np = stats_part_floats(c.max_batch, c.nu, c.H, h->Kp) * 4;
+    HIP_TRY(hipMalloc(&h->d_stats_w, nw));
+    HIP_TRY(hipMemset(h->d_stats_w, 0, nw));
+    HIP_TRY(hipMalloc(&h->d_stats_part, np));
+    HIP_TRY(hipMemset(h->d_stats_part, 0, np));
+  }
+  if (slots <= h->stats_slots) return MPPI_OK;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  void* old[] = {h->d_stats, h->d_stats_m2, h->d_stats_m11};
+  for (void* p : old)
+    if (p) (void)hipFree(p);
+  h->d_stats = nullptr;
+  h->d_stats_m2 = h->d_stats_m11 = nullptr;
+  h->stats_slots = 0;
+  h->stats_B = h->stats_n = 0;
+  const size_t n = (size_t)(slots + 1) * B;
+  HIP_TRY(hipMalloc(&h->d_stats, n * sizeof(mppi_solve_stats)));
+  HIP_TRY(hipMemset(h->d_stats, 0, n * sizeof(mppi_solve_stats)));
+  HIP_TRY(hipMalloc(&h->d_stats_m2, n * c.nu * 4));
+  HIP_TRY(hipMemset(h->d_stats_m2, 0, n * c.nu * 4));
+  HIP_TRY(hipMalloc(&h->d_stats_m11, n * c.nu * 4));
+  HIP_TRY(hipMemset(h->d_stats_m11, 0, n * c.nu * 4));
+  h->stats_slots = slots;
+  return MPPI_OK;
+}
+
+// The diagnostics of B solves from costs [B][Kp] and noise [B][nu][H][Kp] (or nullptr) into output slot `slot`.
+static hipError_t enqueue_stats(mppi_handle* h, int B, const float* costs, const float* noise, int slot) {
+  const mppi_config& c = h->cfg;
+  const size_t off = (size_t)slot * c.max_batch;
+  const StatsArgs sa{B, c.nu, c.H, c.K, h->Kp, c.lambda, c.norm_eps, costs, noise, h->d_stats_w, h->d_stats_part,
+                     h->d_stats + off, h->d_stats_m2 + off * c.nu, h->d_stats_m11 + off * c.nu};
+  return launch_stats(sa, h->stream);
+}
+
 // Validate one solve request against the handle.
 static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if (!h || !io) return fail(MPPI_E_ARG, "mppi_solve: null argument");
@@ -624,7 +675,7 @@ struct NoiseStep {
 // Enqueue one solve on the handle's stream: inputs, noise, rollout, reduce (+ update, shift), env step, outputs.
 // Synchronises only for host-side column-major staging. Capturable into a hipGraph in device mode.
 static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int flags, float* rec_x = nullptr,
-                         float* rec_u = nullptr, const NoiseStep* ns = nullptr) {
+                         float* rec_u = nullptr, const NoiseStep* ns = nullptr, int stats_slot = 0) {
   const mppi_config& c = h->cfg;
   const bool dev = (flags & MPPI_FLAG_DEVICE) != 0;
   const bool resident = (flags & MPPI_FLAG_RESIDENT_U) != 0;
@@ -648,7 +699,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   a.shift_fill = c.shift_fill;
   a.terminal_weight = c.terminal_weight;
   a.update_mode = c.update_mode;
-  a.flags = flags;
+  a.flags = flags & ~MPPI_FLAG_STATS;  // (host-side only: the kernels see the arguments of a solve without it)
   a.cost_kind = h->cost_kind;
   std::memcpy(a.ctx_default, h->cost_params, sizeof(a.ctx_default));
   a.noise = ns ? ns->cur : h->d_noise;
@@ -732,6 +783,11 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     h->rollout_kernel = g_rollout_kernel;
     HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(a, pg, s); }));
   }
+  // diagnostics (MPPI_FLAG_STATS): read-only on this solve's costs and noise, behind the reduce (or the cartpole's fused
+  // epilogue) and ahead of everything that may write a.noise -- the next solve's generators, on this stream or ordered
+  // behind it (ev_red), only ever write the OTHER buffer of the pair before this point
+  if (flags & MPPI_FLAG_STATS)
+    HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, a.costs, a.noise, stats_slot); }));
   if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
     HIP_TRY(timed(h, kNoise, [&] {
       return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s);
@@ -856,6 +912,14 @@ static int ensure_gen_stream(mppi_handle* h) {
   return MPPI_OK;
 }
 
+// a flagged plain or chained solve was enqueued: its statistics are slot 0
+static void note_stats(mppi_handle* h, int B, int flags) {
+  if (flags & MPPI_FLAG_STATS) {
+    h->stats_B = B;
+    h->stats_n = 1;
+  }
+}
+
 // MPPI_FLAG_CHAIN: one solve of a graph stream, launched on the stream (rollout -> reduce_kernel<GEN>, or with
 // gen_overlap the generator stream's noise launch beside the rollout, then the read-only reduce).  A graph launch pays
 // a fixed gap at its boundary (~8.5 us on the box, rocprof trace) that back-to-back stream launches do not, so
@@ -876,6 +940,7 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
     const NoiseStep ns{buf[h->graph_parity], buf[h->graph_parity ^ 1]};
     const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns);
     if (rc != MPPI_OK) return rc;
+    note_stats(h, B, flags);
     h->graph_parity ^= 1;  // this solve's reduce prefetched the next one's noise (still key-valid for B, seed)
     if (flags & MPPI_FLAG_ASYNC) return MPPI_OK;
     return finish_solve(h, B, io);
@@ -896,6 +961,7 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   const NoiseStep ns{buf[h->graph_parity], nullptr};  // read-only reduce, no counter bump (the generator owns it)
   const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns);
   if (rc != MPPI_OK) return rc;
+  note_stats(h, B, flags);
   h->graph_parity ^= 1;  // the generator prefetched the next one's noise (key-valid for B, seed)
   if (flags & MPPI_FLAG_ASYNC) return MPPI_OK;
   return finish_solve(h, B, io);
@@ -1072,10 +1138,12 @@ int mppi_solve_ex(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int f
   if (rc != MPPI_OK) return rc;
   HIP_TRY(hipSetDevice(h->device));
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, 1)) != MPPI_OK) return rc;
   if (flags & MPPI_FLAG_CHAIN) return chain_solve(h, B, io, seed, flags);
   HIP_TRY(drop_prefetch(h));  // a plain solve generates its own noise into d_noise
   rc = enqueue_solve(h, B, io, seed, flags);
   if (rc != MPPI_OK) return rc;
+  note_stats(h, B, flags);
   if ((flags & MPPI_FLAG_DEVICE) && (flags & MPPI_FLAG_ASYNC)) return MPPI_OK;
   return finish_solve(h, B, io);
 }
@@ -1106,6 +1174,8 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   if (h->prefetch_valid && (B != h->prefetch_B || seed != h->prefetch_seed)) HIP_TRY(drop_prefetch(h));
   const mppi_config& c = h->cfg;
   if (const int e = ensure_stream_buffers(h); e != MPPI_OK) return e;
+  // the statistics' slots exist before the capture begins: solve i's launches carry slot i's pointers
+  if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, n_solves)) != MPPI_OK) return rc;
   float* buf[2] = {h->d_noise, h->d_noise2};
   const bool prof = h->prof;
   h->prof = false;  // no event nodes inside the graph
@@ -1117,7 +1187,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
     for (int i = 0; i < n_solves && rc == MPPI_OK; ++i) {
       const NoiseStep ns{buf[(p + i) % 2], buf[(p + i + 1) % 2]};
       rc = enqueue_solve(h, B, io, seed, flags, traj_x ? traj_x + (size_t)i * B * c.nx : nullptr,
-                         traj_u ? traj_u + (size_t)i * B * c.nu : nullptr, &ns);
+                         traj_u ? traj_u + (size_t)i * B * c.nu : nullptr, &ns, i);
     }
     hipGraph_t g = nullptr;
     const hipError_t ec = hipStreamEndCapture(h->stream, &g);
@@ -1140,6 +1210,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->prof = prof;
   h->capturing = false;
   h->graph_kclock = h->kclock;
+  h->graph_stats = (flags & MPPI_FLAG_STATS) != 0;
   h->graph_B = B;
   h->graph_n = n_solves;
   h->graph_seed = seed;
@@ -1159,6 +1230,10 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
   if (const int rc = prime_prefetch(h, h->graph_B, h->graph_seed); rc != MPPI_OK) return rc;
   HIP_TRY(hipGraphLaunch(h->graph_exec[h->graph_parity], h->stream));
   if (h->graph_kclock) h->kclock_launches += h->graph_n;
+  if (h->graph_stats) {
+    h->stats_B = h->graph_B;
+    h->stats_n = h->graph_n;
+  }
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1238,6 +1313,57 @@ int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active
   if (rho) *rho = m.rho;
   if (active) *active = m.active;
   return MPPI_OK;
+}
+
+// slot `slot` of the diagnostics' buffers -> host (the stream is idle)
+static int copy_stats(mppi_handle* h, int B, int slot, mppi_solve_stats* stats, float* eps_m2, float* eps_m11) {
+  const size_t off = (size_t)slot * h->cfg.max_batch, nu = (size_t)h->cfg.nu;
+  if (stats) HIP_TRY(hipMemcpy(stats, h->d_stats + off, (size_t)B * sizeof(mppi_solve_stats), hipMemcpyDeviceToHost));
+  if (eps_m2) HIP_TRY(hipMemcpy(eps_m2, h->d_stats_m2 + off * nu, (size_t)B * nu * 4, hipMemcpyDeviceToHost));
+  if (eps_m11) HIP_TRY(hipMemcpy(eps_m11, h->d_stats_m11 + off * nu, (size_t)B * nu * 4, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_get_stats(mppi_handle* h, int B, int step, mppi_solve_stats* stats, float* eps_m2, float* eps_m11) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_stats: null handle");
+  if (h->stats_n == 0) return fail(MPPI_E_STATE, "mppi_get_stats: no solve with MPPI_FLAG_STATS has run on the handle");
+  if (B < 1 || B > h->stats_B) return fail(MPPI_E_ARG, "mppi_get_stats: B beyond the batch of the last flagged solve");
+  if (step < 0 || step >= h->stats_n)
+    return fail(MPPI_E_ARG, "mppi_get_stats: step beyond the solves of the last flagged solve or graph");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_stats(h, B, step, stats, eps_m2, eps_m11);
+}
+
+int mppi_device_stats(mppi_handle* h, void** d_stats, void** d_m2, void** d_m11) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_device_stats: null handle");
+  HIP_TRY(hipSetDevice(h->device));
+  if (const int rc = ensure_stats(h, 1); rc != MPPI_OK) return rc;
+  if (d_stats) *d_stats = h->d_stats;
+  if (d_m2) *d_m2 = h->d_stats_m2;
+  if (d_m11) *d_m11 = h->d_stats_m11;
+  return MPPI_OK;
+}
+
+int mppi_stats_eval(mppi_handle* h, int B, const float* costs, const float* noise, mppi_solve_stats* stats,
+                    float* eps_m2, float* eps_m11) {
+  if (!h || !costs) return fail(MPPI_E_ARG, "mppi_stats_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_stats_eval: B out of range [1, max_batch]");
+  HIP_TRY(hipSetDevice(h->device));
+  if (const int rc = ensure_stats(h, 1); rc != MPPI_OK) return rc;
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  HIP_TRY(hipMemcpy2DAsync(h->d_costs, Kp * 4, costs, K * 4, K * 4, B, hipMemcpyHostToDevice, s));
+  if (noise) {
+    if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, s));
+    HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, noise, K * 4, K * 4, rows, hipMemcpyHostToDevice, s));
+  }
+  const int slot = h->stats_slots;  // the evaluation's own slot
+  HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, h->d_costs, noise ? h->d_noise : nullptr, slot); }));
+  HIP_TRY(hipStreamSynchronize(s));
+  return copy_stats(h, B, slot, stats, noise ? eps_m2 : nullptr, noise ? eps_m11 : nullptr);
 }
 
 int mppi_solve(mppi_handle* h, int B, const float* x0, float* U, const float* noise, uint64_t seed, float* costs_out,

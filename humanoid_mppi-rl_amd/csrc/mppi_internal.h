@@ -303,6 +303,21 @@ hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t st
 // analytic cartpole rollout; with a.part set it also runs a7-a9 (fused epilogue) and, given gen, writes the next
 // solve's noise (graph streams)
 hipError_t launch_cartpole_rollout(const SolveArgs& a, const CartpoleParams& p, const NoiseGen* gen, hipStream_t stream);
+// Solve diagnostics (kernels_stats.hip; MPPI_FLAG_STATS, mppi_stats_eval), by value like SolveArgs: read-only on the
+// solve's costs and noise, so the launches can sit in a captured graph.
+struct StatsArgs {
+  int B, nu, H, K, Kp;
+  float lambda, norm_eps;
+  const float* costs;       // [B][Kp]
+  const float* noise;       // [B][nu][H][Kp], or nullptr: only the struct is computed
+  float* w;                 // [B][Kp] scratch: the normalised softmin weights (pads 0)
+  float* part;              // [stats_part_floats] scratch: the moment kernel's per-cell partial sums
+  mppi_solve_stats* stats;  // [B] out
+  float* m2;                // [B][nu] out
+  float* m11;               // [B][nu] out
+};
+size_t stats_part_floats(int B, int nu, int H, int Kp);
+hipError_t launch_stats(const StatsArgs& a, hipStream_t stream);  // cost part, moment part, fixed-order finish
 hipError_t launch_record(const float* x, const float* u, float* rx, float* ru, int nxB, int nuB, hipStream_t stream);
 
 }  // namespace mppi

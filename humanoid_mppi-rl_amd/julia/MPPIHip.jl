@@ -32,6 +32,7 @@ const DYN_CARTPOLE, DYN_MLP, DYN_CROSS_ATTN, DYN_FEATURE_ATTN = Cint(1), Cint(2)
 const COST = Dict(:cartpole => Cint(1), :cartpole_est => Cint(2), :humanoid_v3 => Cint(3),
                   :quad_jl => Cint(4), :quad_est => Cint(5), :humanoid_v1 => Cint(6))
 const FLAG_SHIFT, FLAG_COLMAJOR, FLAG_U0_BEFORE = Cint(0x1), Cint(0x2), Cint(0x10)
+const FLAG_STATS = Cint(0x200)   # also compute the solve's diagnostics (solve_stats)
 const CTX_MAX = 8
 
 # must match `mppi_io` in include/mppi.h (7 pointers)
@@ -47,6 +48,13 @@ mutable struct Config
     shift_fill::Float32; terminal_weight::Float32; update_mode::Int32; precision::Int32
     r0::Int32; r1::Int32; r2::Int32; r3::Int32
     Config() = new(0, 0, 0, 0, 0, 0f0, 0f0, 0f0, 0f0, 0f0, 0f0, 0f0, 0, 0, 0, 0, 0, 0)
+end
+
+# must match `mppi_solve_stats` in include/mppi.h field for field (40 bytes)
+struct SolveStats
+    cost_min::Float32; cost_max::Float32; cost_mean::Float32; cost_std::Float32
+    cost_weighted::Float32; ess::Float32; entropy::Float32; free_energy::Float32
+    n_finite::Int32; k_best::Int32
 end
 
 struct MPPIError <: Exception
@@ -157,6 +165,7 @@ function _context!(c::Controller, m, d)
     return pointer(c.ctx)
 end
 
+# (`stats = true` of mppi_step! / mppi_controller! adds FLAG_STATS here; solve_stats reads the result)
 function _solve!(c::Controller, m, d; flags::Cint = Cint(0), noise = nothing)
     x0 = state(d)
     u0 = zeros(Float32, c.cfg.nu)
@@ -173,11 +182,12 @@ function _solve!(c::Controller, m, d; flags::Cint = Cint(0), noise = nothing)
 end
 
 "mppi_step!: noise -> rollout -> softmin -> U update (no shift); U_global kept in `c.U`."
-mppi_step!(c::Controller, m, d; noise = nothing) = (_solve!(c, m, d; noise = noise); nothing)
+mppi_step!(c::Controller, m, d; noise = nothing, stats::Bool = false) =
+    (_solve!(c, m, d; flags = stats ? FLAG_STATS : Cint(0), noise = noise); nothing)
 
 "mppi_controller!: mppi_step!, then d.ctrl .= U[:,1] and the receding-horizon shift (0.1 decay or zero fill)."
-function mppi_controller!(c::Controller, m, d; noise = nothing)
-    flags = FLAG_SHIFT | (c.u0_before ? FLAG_U0_BEFORE : Cint(0))
+function mppi_controller!(c::Controller, m, d; noise = nothing, stats::Bool = false)
+    flags = FLAG_SHIFT | (c.u0_before ? FLAG_U0_BEFORE : Cint(0)) | (stats ? FLAG_STATS : Cint(0))
     u0 = _solve!(c, m, d; flags = flags, noise = noise)
     d.ctrl .= u0
     return nothing
@@ -210,6 +220,50 @@ function set_noise_model!(c::Controller; sigma_u = nothing, rho::Real = 0.0)
                                    pointer(s), rho))
     end
     return c
+end
+
+"""
+    solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
+
+The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and
+the weighted moments of the noise it used, per actuator, taken about the nominal U:
+`sqrt.(eps_m2)` estimates sigma_u and `eps_m11 ./ eps_m2` the AR(1) correlation of the samples that won.
+"""
+function solve_stats(c::Controller)
+    st = Ref{SolveStats}()
+    m2 = zeros(Float32, c.cfg.nu)
+    m11 = zeros(Float32, c.cfg.nu)
+    GC.@preserve m2 m11 check(ccall((:mppi_get_stats, LIB), Cint,
+                                    (Ptr{Cvoid}, Cint, Cint, Ref{SolveStats}, Ptr{Float32}, Ptr{Float32}),
+                                    c.handle, 1, 0, st, pointer(m2), pointer(m11)))
+    return (st[], m2, m11)
+end
+
+"""
+    stats_eval(c, costs; noise = nothing)
+
+The same statistics of a given cost vector (length K; non-finite entries allowed) and, optionally, noise (nu, H, K)
+column-major as everywhere in this module (mppi_stats_eval).  Without noise only the SolveStats is returned.
+"""
+function stats_eval(c::Controller, costs; noise = nothing)
+    cs = Float32.(vec(collect(costs)))
+    length(cs) == c.cfg.K || throw(ArgumentError("costs must have K = $(c.cfg.K) entries"))
+    st = Ref{SolveStats}()
+    if noise === nothing
+        GC.@preserve cs check(ccall((:mppi_stats_eval, LIB), Cint,
+                                    (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}, Ref{SolveStats}, Ptr{Float32},
+                                     Ptr{Float32}), c.handle, 1, pointer(cs), C_NULL, st, C_NULL, C_NULL))
+        return st[]
+    end
+    size(noise) == (c.cfg.nu, c.cfg.H, c.cfg.K) || throw(ArgumentError("noise must be (nu, H, K)"))
+    nz = Float32.(permutedims(noise, (3, 2, 1)))   # the C ABI's [nu][H][K]: k fastest
+    m2 = zeros(Float32, c.cfg.nu)
+    m11 = zeros(Float32, c.cfg.nu)
+    GC.@preserve cs nz m2 m11 check(ccall((:mppi_stats_eval, LIB), Cint,
+                                          (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}, Ref{SolveStats},
+                                           Ptr{Float32}, Ptr{Float32}), c.handle, 1, pointer(cs), pointer(nz), st,
+                                          pointer(m2), pointer(m11)))
+    return (st[], m2, m11)
 end
 
 "rollout_kernel: the kernel the last solve was routed to (mppi_rollout_kernel; ABI 3)."

@@ -17,7 +17,7 @@ COST_CARTPOLE, COST_CARTPOLE_EST, COST_HUMANOID_V3, COST_QUAD_JL, COST_QUAD_EST,
 UPDATE_ADD, UPDATE_REPLACE = 0, 1
 PREC_FP32, PREC_BF16, PREC_BF16X3 = 0, 1, 2  # BF16X3: fp32-accurate split bf16 (fc nets)
 FLAG_SHIFT, FLAG_COLMAJOR, FLAG_DEVICE, FLAG_ASYNC, FLAG_U0_BEFORE, FLAG_RESIDENT_U = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
-FLAG_ENV_STEP, FLAG_SEED_COUNTER, FLAG_CHAIN = 0x40, 0x80, 0x100
+FLAG_ENV_STEP, FLAG_SEED_COUNTER, FLAG_CHAIN, FLAG_STATS = 0x40, 0x80, 0x100, 0x200
 CTX_MAX = 8
 
 EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", "mppi_set_cost", "mppi_solve",
@@ -26,7 +26,7 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_graph_launch", "mppi_set_seed_counter", "mppi_get_seed_counter", "mppi_graph_capture_traj",
             "mppi_kernel_clock",
             "mppi_kernel_clock_read", "mppi_build_id", "mppi_x3_layer1", "mppi_rollout_kernel", "mppi_x3_f16",
-            "mppi_set_noise_model", "mppi_get_noise_model"]
+            "mppi_set_noise_model", "mppi_get_noise_model", "mppi_get_stats", "mppi_device_stats", "mppi_stats_eval"]
 
 
 class MPPIError(RuntimeError):
@@ -54,6 +54,17 @@ class mppi_io(ctypes.Structure):
     _fields_ = [("x0", ctypes.c_void_p), ("U", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("costs", ctypes.c_void_p),
                 ("weights", ctypes.c_void_p), ("u0", ctypes.c_void_p), ("ctx", ctypes.c_void_p)]
 
+
+class mppi_solve_stats(ctypes.Structure):
+    """Diagnostics of one solve (include/mppi.h mppi_solve_stats; 40 bytes)."""
+    _fields_ = [("cost_min", ctypes.c_float), ("cost_max", ctypes.c_float), ("cost_mean", ctypes.c_float),
+                ("cost_std", ctypes.c_float), ("cost_weighted", ctypes.c_float), ("ess", ctypes.c_float),
+                ("entropy", ctypes.c_float), ("free_energy", ctypes.c_float), ("n_finite", ctypes.c_int32),
+                ("k_best", ctypes.c_int32)]
+
+
+# the same record as a numpy dtype (Engine.stats reads [B] of them at once)
+STATS_DTYPE = [(n, "<f4" if t is ctypes.c_float else "<i4") for n, t in mppi_solve_stats._fields_]
 
 _lib = None
 
@@ -98,6 +109,9 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_x3_f16": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float)]),
         "mppi_set_noise_model": (i32, [vp, _fp, ctypes.c_float]),
         "mppi_get_noise_model": (i32, [vp, _fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i32)]),
+        "mppi_get_stats": (i32, [vp, i32, i32, vp, vp, vp]),
+        "mppi_device_stats": (i32, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]),
+        "mppi_stats_eval": (i32, [vp, i32, vp, vp, vp, vp, vp]),
         "mppi_kernel_clock_read": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_double)]),
     }

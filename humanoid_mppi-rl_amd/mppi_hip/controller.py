@@ -26,6 +26,7 @@ from . import _lib as L
 from .engine import Config, Engine
 from .nets import cross_attention_blob, feature_attention_blob, mlp_blob
 from .noise import ar1_filter
+from .stats import adapt_noise_model
 
 # default cost of each preset (the reference script it mirrors)
 PRESET_COST = {"cartpole_py": "cartpole", "cartpole_jl": "cartpole", "cartpole_collect": "cartpole",
@@ -53,12 +54,17 @@ class MPPIModel:
                           (src/cartpole_mppi.py:89), injected into the engine.
     noise_sigma, noise_rho: the sampling law (Engine.set_noise_model): per-actuator standard deviations [nu] (None =
               the preset's sigma) and AR(1) correlation along the horizon; both noise modes sample the same law.
+    adapt_noise: above 0, mppi_step / mppi_controller request the solve's statistics (Engine.solve(stats=True)) and
+              after each step move the law towards the weighted moments of the noise that won
+              (stats.adapt_noise_model with this rate and adapt_limits = (sigma_min, sigma_max, rho_max)), through
+              Engine.set_noise_model.  The moments are about the nominal U.  Setting the law destroys captured graphs
+              (mppi_set_noise_model), so a graph stream on the same engine has to be captured again after a step.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
                  noise: str = "device", seed: int = 0, precision: int = L.PREC_BF16, ctx=None,
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
-                 **overrides):
+                 adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -92,6 +98,10 @@ class MPPIModel:
         self.noise_rho = float(noise_rho)
         if self.noise_sigma is not None or self.noise_rho != 0.0:
             self.engine.set_noise_model(self.noise_sigma, self.noise_rho)
+        self.adapt_noise = float(adapt_noise)
+        self.adapt_limits = tuple(float(v) for v in adapt_limits)
+        if not 0.0 <= self.adapt_noise <= 1.0:
+            raise ValueError("MPPIModel: adapt_noise must be in [0, 1]")
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0
@@ -113,6 +123,15 @@ class MPPIModel:
                 return z * c.sigma
             return ar1_filter(z, self.noise_rho, c.sigma if self.noise_sigma is None else self.noise_sigma)
         return None
+
+    def adapt(self, stats: dict):
+        """Move the sampling law towards the moments of one solve's statistics (adapt_noise > 0)."""
+        c = self.config
+        sig = np.full(c.nu, c.sigma) if self.noise_sigma is None else self.noise_sigma
+        lo, hi, rho_max = self.adapt_limits
+        self.noise_sigma, self.noise_rho = adapt_noise_model(sig, self.noise_rho, stats["eps_m2"], stats["eps_m11"],
+                                                             self.adapt_noise, lo, hi, rho_max)
+        self.engine.set_noise_model(self.noise_sigma, self.noise_rho)
 
     def next_seed(self) -> int:
         self.calls += 1
@@ -211,15 +230,27 @@ def rollout_learned_model_batched(model: MPPIModel, state, U, noise, device=None
     return res.costs.astype(np.float64)
 
 
+def _stats_kw(model) -> dict:
+    """stats=True for the solve of a model that adapts its sampling law; nothing otherwise (the solve call of a model
+    that does not adapt is what it always was)."""
+    return {"stats": True} if getattr(model, "adapt_noise", 0.0) > 0.0 else {}
+
+
+def _adapt(model, res):
+    if getattr(model, "adapt_noise", 0.0) > 0.0 and res.status == L.MPPI_OK:
+        model.adapt(res.stats)
+
+
 def mppi_step(model: MPPIModel, data, ctx=None):
     """noise -> rollout -> softmin -> U_global update (add or replace per preset), in place.  ctx None: built from
     data's real-env kinematics for the humanoid costs (env_context), as the reference reads them per call."""
     ctx = env_context(model, data) if ctx is None else ctx
     noise = model.draw_noise()
     res = model.engine.solve(_state(data), model.U_global, noise=noise, seed=model.next_seed(), ctx=ctx,
-                             want_costs=True, want_weights=True)
+                             want_costs=True, want_weights=True, **_stats_kw(model))
     model.U_global = res.U.astype(np.float64)
     model.last = res
+    _adapt(model, res)
     return res
 
 
@@ -228,9 +259,11 @@ def mppi_controller(model: MPPIModel, data, ctx=None):
     ctx = env_context(model, data) if ctx is None else ctx
     noise = model.draw_noise()
     res = model.engine.solve(_state(data), model.U_global, noise=noise, seed=model.next_seed(), ctx=ctx,
-                             want_costs=True, want_weights=True, shift=True, u0_before=model.u0_before)
+                             want_costs=True, want_weights=True, shift=True, u0_before=model.u0_before,
+                             **_stats_kw(model))
     model.U_global = res.U.astype(np.float64)
     model.last = res
+    _adapt(model, res)
     data.ctrl[:] = res.u0
     return res
 

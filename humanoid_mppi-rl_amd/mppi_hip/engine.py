@@ -62,6 +62,7 @@ class SolveResult:
     weights: np.ndarray | None = None
     u0: np.ndarray | None = None
     status: int = 0
+    stats: dict | None = None  # solve(..., stats=True): Engine.stats of this solve
 
 
 class Engine:
@@ -133,9 +134,10 @@ class Engine:
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,
-              raise_nonfinite: bool = False) -> SolveResult:
+              raise_nonfinite: bool = False, stats: bool = False) -> SolveResult:
         """One batched solve. x0 [B,nx] (or [nx]); U [B,nu,H] (or [nu,H]); noise None (device Philox) or
-        [B,nu,H,K] (or [nu,H,K]). Returns the updated (and optionally shifted) U plus diagnostics."""
+        [B,nu,H,K] (or [nu,H,K]). Returns the updated (and optionally shifted) U plus diagnostics.
+        stats: also compute the solve's statistics on the device (MPPI_FLAG_STATS) into SolveResult.stats."""
         c = self.config
         single = np.ndim(x0) == 1
         x0 = _f32(x0).reshape(-1, c.nx)
@@ -151,27 +153,30 @@ class Engine:
         u0 = np.empty((B, c.nu), np.float32)
         io = L.mppi_io(_ptr(x0), _ptr(Uo), _ptr(nz), _ptr(costs), _ptr(weights), _ptr(u0), _ptr(cx))
         flags = (L.FLAG_SHIFT if shift else 0) | (L.FLAG_U0_BEFORE if u0_before else 0) | (
-            L.FLAG_COLMAJOR if colmajor else 0)
+            L.FLAG_COLMAJOR if colmajor else 0) | (L.FLAG_STATS if stats else 0)
         rc = self.lib.mppi_solve_ex(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags)
         if rc != L.MPPI_E_NONFINITE or raise_nonfinite:
             L.check(rc)
         sq = (lambda a: a[0]) if single else (lambda a: a)
+        st = {k: sq(v) for k, v in self.stats(B).items()} if stats else None
         return SolveResult(U=sq(Uo), costs=None if costs is None else sq(costs),
-                           weights=None if weights is None else sq(weights), u0=sq(u0), status=rc)
+                           weights=None if weights is None else sq(weights), u0=sq(u0), status=rc, stats=st)
 
     # -- device-memory solve (pointers are integers, e.g. torch tensor .data_ptr())
     def solve_device(self, B: int, x0_ptr: int, U_ptr: int | None = None, noise_ptr: int | None = None, seed: int = 0,
                      costs_ptr: int | None = None, u0_ptr: int | None = None, ctx_ptr: int | None = None,
                      weights_ptr: int | None = None, shift: bool = False, resident_U: bool = False,
                      asynchronous: bool = True, env_step: bool = False, seed_counter: bool = False,
-                     chain: bool = False) -> int:
-        """env_step: advance x0 in place by one dynamics step with u0 (MPPI_FLAG_ENV_STEP);
+                     chain: bool = False, stats: bool = False) -> int:
+        """stats: also compute the solve's statistics (MPPI_FLAG_STATS; read with Engine.stats);
+        env_step: advance x0 in place by one dynamics step with u0 (MPPI_FLAG_ENV_STEP);
         seed_counter: noise key = seed + the handle's device counter (MPPI_FLAG_SEED_COUNTER);
         chain: a chained solve (MPPI_FLAG_CHAIN: the previous chained solve's reduce generated this one's noise;
         2 launches, bitwise equal to plain counter solves)."""
         io = L.mppi_io(x0_ptr, U_ptr, noise_ptr, costs_ptr, weights_ptr, u0_ptr, ctx_ptr)
         flags = self._dev_flags(shift, resident_U, env_step) | (L.FLAG_ASYNC if asynchronous else 0) | (
-            L.FLAG_SEED_COUNTER if seed_counter else 0) | (L.FLAG_CHAIN if chain else 0)
+            L.FLAG_SEED_COUNTER if seed_counter else 0) | (L.FLAG_CHAIN if chain else 0) | (
+            L.FLAG_STATS if stats else 0)
         return L.check(self.lib.mppi_solve_ex(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags))
 
     @staticmethod
@@ -182,19 +187,19 @@ class Engine:
     # -- receding-horizon stream as one hipGraph (mppi_graph_capture / mppi_graph_launch)
     def graph_capture(self, B: int, n_solves: int, x0_ptr: int, U_ptr: int | None = None, u0_ptr: int | None = None,
                       ctx_ptr: int | None = None, costs_ptr: int | None = None, seed: int = 0, shift: bool = True,
-                      resident_U: bool = False, env_step: bool = True):
+                      resident_U: bool = False, env_step: bool = True, stats: bool = False):
         return self.graph_capture_traj(B, n_solves, x0_ptr, U_ptr, u0_ptr, ctx_ptr, costs_ptr, seed, shift,
-                                       resident_U, env_step)
+                                       resident_U, env_step, stats=stats)
 
     def graph_capture_traj(self, B: int, n_solves: int, x0_ptr: int, U_ptr: int | None = None,
                            u0_ptr: int | None = None, ctx_ptr: int | None = None, costs_ptr: int | None = None,
                            seed: int = 0, shift: bool = True, resident_U: bool = False, env_step: bool = True,
-                           traj_x_ptr: int | None = None, traj_u_ptr: int | None = None):
+                           traj_x_ptr: int | None = None, traj_u_ptr: int | None = None, stats: bool = False):
         """Capture n_solves chained solves; with traj_*_ptr (device [n][B][nx] / [n][B][nu]) the env steps log
-        the (state, control) trajectory."""
+        the (state, control) trajectory.  stats: solve i also writes its statistics, Engine.stats(B, step=i)."""
         io = L.mppi_io(x0_ptr, U_ptr, None, costs_ptr, None, u0_ptr, ctx_ptr)
         self._graph_io = io  # the graph holds these device pointers
-        flags = self._dev_flags(shift, resident_U, env_step)
+        flags = self._dev_flags(shift, resident_U, env_step) | (L.FLAG_STATS if stats else 0)
         L.check(self.lib.mppi_graph_capture_traj(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags,
                                                  n_solves, traj_x_ptr, traj_u_ptr))
         return self
@@ -211,6 +216,44 @@ class Engine:
         v = ctypes.c_uint64(0)
         L.check(self.lib.mppi_get_seed_counter(self._h, ctypes.byref(v)))
         return int(v.value)
+
+    # -- solve diagnostics (MPPI_FLAG_STATS; mppi_hip.stats.solve_stats_ref states the definitions)
+    def _stats_dict(self, rec, m2, m11) -> dict:
+        out = {n: rec[n].copy() for n in rec.dtype.names}
+        if m2 is not None:
+            out["eps_m2"], out["eps_m11"] = m2, m11
+        return out
+
+    def stats(self, B: int = 1, step: int = 0) -> dict:
+        """The statistics of the last solve made with stats=True (mppi_get_stats; waits for the stream): the fields of
+        mppi_solve_stats as arrays [B], plus eps_m2 and eps_m11 [B, nu].  step: 0 after a plain or chained solve,
+        0..n_solves-1 after graph_launch of a graph captured with stats=True."""
+        rec = np.zeros(B, np.dtype(L.STATS_DTYPE))
+        m2 = np.zeros((B, self.config.nu), np.float32)
+        m11 = np.zeros((B, self.config.nu), np.float32)
+        L.check(self.lib.mppi_get_stats(self._h, B, step, _ptr(rec), _ptr(m2), _ptr(m11)))
+        return self._stats_dict(rec, m2, m11)
+
+    def stats_eval(self, costs, noise=None) -> dict:
+        """The same kernels on host arrays (mppi_stats_eval): costs [B, K] (or [K]; non-finite entries allowed), noise
+        None or [B, nu, H, K]; the dictionary of Engine.stats, without the moments when noise is None.  Uses the
+        handle's lambda_ and norm_eps; no dynamics or cost need be loaded."""
+        c = self.config
+        costs = _f32(costs).reshape(-1, c.K)
+        B = costs.shape[0]
+        nz = None if noise is None else _f32(noise).reshape(B, c.nu, c.H, c.K)
+        rec = np.zeros(B, np.dtype(L.STATS_DTYPE))
+        m2 = None if nz is None else np.zeros((B, c.nu), np.float32)
+        m11 = None if nz is None else np.zeros((B, c.nu), np.float32)
+        L.check(self.lib.mppi_stats_eval(self._h, B, _ptr(costs), _ptr(nz), _ptr(rec), _ptr(m2), _ptr(m11)))
+        return self._stats_dict(rec, m2, m11)
+
+    def device_stats(self) -> dict:
+        """Device pointers of the statistics' buffers (mppi_device_stats), slot-major with max_batch as the batch
+        pitch, for consumers on the stream."""
+        a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        L.check(self.lib.mppi_device_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return dict(stats=a.value, eps_m2=b.value, eps_m11=c.value)
 
     def x3_layer1(self) -> tuple[int, float]:
         """(products, probe_rel_err) of the split CA's layer 1 (mppi_x3_layer1): 2 or 3 once the first solve's probe

@@ -1,0 +1,110 @@
+"""Solve diagnostics on the host (include/mppi.h mppi_solve_stats, MPPI_FLAG_STATS; csrc/kernels_stats.hip).
+
+Per solve, with F = {k : isfinite(c_k)}, beta = min_F c, wt_k = exp(-(c_k - beta) / lambda) on F and 0 elsewhere,
+S = sum wt and w_k = wt_k / (S + norm_eps) -- the weights of the update itself:
+
+    cost_min / cost_max / cost_mean / cost_std   over F (population std)
+    cost_weighted = sum_k w_k c_k
+    ess           = S^2 / sum wt_k^2                        in [1, |F|]
+    entropy       = -sum p ln p, p = wt / S (0 ln 0 = 0)    in [0, ln |F|]
+    free_energy   = beta - lambda ln(S / |F|)
+    n_finite = |F|,  k_best = the lowest k attaining beta
+    eps_m2 [u]  = 1/H     sum_t      sum_k w_k eps[u,t,k]^2
+    eps_m11[u]  = 1/(H-1) sum_{t>=1} sum_k w_k eps[u,t,k] eps[u,t-1,k]     (0 when H == 1)
+
+The device computes these in fp32 (fp64 for the cost sums); solve_stats_ref is the float64 restatement: the reference
+of the tests, and for users.  adapt_noise_model turns the moments into the next sampling law.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+FIELDS = ("cost_min", "cost_max", "cost_mean", "cost_std", "cost_weighted", "ess", "entropy", "free_energy",
+          "n_finite", "k_best")
+
+
+def solve_stats_ref(costs, noise=None, lam: float = 1.0, norm_eps: float = 0.0) -> dict:
+    """costs [B, K] (or [K]), noise None or [B, nu, H, K] (or [nu, H, K]) -> the dictionary Engine.stats returns:
+    every field of mppi_solve_stats as an array [B] (float64; n_finite and k_best int64) and, with noise, eps_m2 and
+    eps_m11 [B, nu].  No finite cost: n_finite 0, k_best -1, ess = entropy = cost_std = cost_weighted = 0,
+    cost_min = cost_max = cost_mean = free_energy = +inf, both moments 0."""
+    c = np.asarray(costs, np.float64)
+    single = c.ndim == 1
+    c = c.reshape(-1, c.shape[-1])
+    B, K = c.shape
+    out = {n: np.zeros(B, np.int64 if n in ("n_finite", "k_best") else np.float64) for n in FIELDS}
+    w = np.zeros((B, K))
+    for b in range(B):
+        fin = np.isfinite(c[b])
+        n = int(fin.sum())
+        out["n_finite"][b] = n
+        if n == 0:
+            for name in ("cost_min", "cost_max", "cost_mean", "free_energy"):
+                out[name][b] = np.inf
+            out["k_best"][b] = -1
+            continue
+        cf = c[b][fin]
+        beta = cf.min()
+        wt = np.zeros(K)
+        wt[fin] = np.exp(-(cf - beta) / lam)
+        S = wt.sum()
+        w[b] = wt / (S + norm_eps)
+        p = wt[wt > 0.0] / S
+        out["cost_min"][b], out["cost_max"][b], out["cost_mean"][b] = beta, cf.max(), cf.mean()
+        out["cost_std"][b] = np.sqrt(np.mean((cf - cf.mean()) ** 2))
+        out["cost_weighted"][b] = np.sum(w[b][fin] * cf)
+        out["ess"][b] = S * S / np.sum(wt * wt)
+        out["entropy"][b] = -np.sum(p * np.log(p))
+        out["free_energy"][b] = beta - lam * np.log(S / n)
+        out["k_best"][b] = int(np.flatnonzero(fin & (c[b] == beta))[0])
+    if noise is not None:
+        e = np.asarray(noise, np.float64)
+        e = e.reshape(B, -1, e.shape[-2], K)
+        H = e.shape[2]
+        out["eps_m2"] = np.einsum("bk,buhk->bu", w, e * e) / H
+        out["eps_m11"] = (np.einsum("bk,buhk->bu", w, e[:, :, 1:] * e[:, :, :-1]) / (H - 1) if H > 1
+                          else np.zeros((B, e.shape[1])))
+    return {k: v[0] for k, v in out.items()} if single else out
+
+
+def adapt_noise_model(sigma_u, rho: float, eps_m2, eps_m11, rate: float, sigma_min: float = 1e-3,
+                      sigma_max: float = 10.0, rho_max: float = 0.95):
+    """One step of the sampling law towards the noise that won the last solve(s): (sigma_u [nu], rho) for
+    Engine.set_noise_model.  Pure.
+
+    eps_m2, eps_m11: the weighted noise moments [B, nu] (or [nu]) of Engine.stats.  They are moments about the NOMINAL
+    U (about zero noise), as the update itself is -- not about the weighted mean of the noise -- so a solve whose
+    winners share an offset widens sigma_u rather than only moving U.
+
+        var     <- (1 - rate) sigma_u^2 + rate * mean_b eps_m2;   sigma_u = sqrt(var) clipped to [sigma_min, sigma_max]
+        rho_hat  = sum_u mean_b eps_m11 / sum_u mean_b eps_m2,    clipped to [0, rho_max]   (0 if the denominator is 0)
+        rho     <- (1 - rate) rho + rate * rho_hat
+
+    rate = 0 returns the law unchanged (sigma_u still clipped).  ValueError on rate outside [0, 1], rho outside [0, 1),
+    rho_max outside [0, 1), sigma_min > sigma_max or negative, non-finite or negative sigma_u / eps_m2, non-finite
+    eps_m11, or moments whose last axis is not nu."""
+    s = np.atleast_1d(np.asarray(sigma_u, np.float64)).ravel()
+    m2 = np.asarray(eps_m2, np.float64)
+    m11 = np.asarray(eps_m11, np.float64)
+    rate, rho = float(rate), float(rho)
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError("adapt_noise_model: rate must be in [0, 1]")
+    if not 0.0 <= rho < 1.0:
+        raise ValueError("adapt_noise_model: rho must be in [0, 1)")
+    if not 0.0 <= rho_max < 1.0:
+        raise ValueError("adapt_noise_model: rho_max must be in [0, 1)")
+    if not 0.0 <= sigma_min <= sigma_max or not np.isfinite(sigma_max):
+        raise ValueError("adapt_noise_model: need 0 <= sigma_min <= sigma_max < inf")
+    if not (np.all(np.isfinite(s)) and np.all(s >= 0.0)):
+        raise ValueError("adapt_noise_model: sigma_u entries must be finite and >= 0")
+    if m2.shape != m11.shape or m2.ndim not in (1, 2) or m2.shape[-1] != s.size:
+        raise ValueError(f"adapt_noise_model: eps_m2 and eps_m11 must both be [B, {s.size}] or [{s.size}]")
+    if not (np.all(np.isfinite(m2)) and np.all(m2 >= 0.0) and np.all(np.isfinite(m11))):
+        raise ValueError("adapt_noise_model: moments must be finite (eps_m2 >= 0)")
+    m2 = m2.reshape(-1, s.size).mean(axis=0)
+    m11 = m11.reshape(-1, s.size).mean(axis=0)
+    var = (1.0 - rate) * s * s + rate * m2
+    sigma_new = np.clip(np.sqrt(var), sigma_min, sigma_max)
+    den = m2.sum()
+    rho_hat = float(np.clip(m11.sum() / den, 0.0, rho_max)) if den > 0.0 else 0.0
+    return sigma_new, (1.0 - rate) * rho + rate * rho_hat

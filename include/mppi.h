@@ -63,7 +63,10 @@ extern "C" {
  *   4  mppi_x3_f16.  BEHAVIOUR CHANGE: MPPI_PREC_BF16X3 CrossAttention solves run the fp16 form when the engine's
  *      probe of the loaded weights allows it (below).
  *      Additive, version unchanged: mppi_set_noise_model / mppi_get_noise_model (per-actuator sigma and AR(1)
- *      correlation of the device noise).  A handle that never calls them behaves exactly as before. */
+ *      correlation of the device noise).  A handle that never calls them behaves exactly as before.
+ *      Additive, version unchanged: MPPI_FLAG_STATS, mppi_solve_stats, mppi_get_stats / mppi_device_stats /
+ *      mppi_stats_eval (softmin statistics and weighted noise moments of a solve); kernel name "stats" in
+ *      mppi_kernel_time.  A solve without the flag launches exactly the kernels it launched before. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -145,6 +148,12 @@ extern "C" {
                                        low-priority stream concurrently with this solve's rollout); bitwise equal to
                                        plain counter solves either way.  Injected noise and MPPI_FLAG_COLMAJOR are
                                        not allowed */
+#define MPPI_FLAG_STATS 0x200       /* also compute this solve's diagnostics (mppi_solve_stats and the weighted noise
+                                       moments below) on the handle's stream, behind the reduce and before anything
+                                       overwrites the solve's noise; read with mppi_get_stats.  Every solve form takes
+                                       it (plain, chained, ASYNC, host pointers, captured graphs).  U, u0, costs,
+                                       weights, the seed counter and a prefetched noise are bit for bit what they are
+                                       without it */
 
 #define MPPI_CTX_MAX 8 /* floats of per-solve cost context */
 
@@ -175,6 +184,21 @@ typedef struct mppi_io {
   float* u0;          /* NULL or [B][nu] out                       */
   const float* ctx;   /* NULL or [B][MPPI_CTX_MAX] per-solve cost context */
 } mppi_io;
+
+/* Diagnostics of one solve b (MPPI_FLAG_STATS, mppi_stats_eval), from its K costs c with the handle's cfg.lambda and
+ * cfg.norm_eps.  F = {k < K : isfinite(c_k)}, beta = min_F c, wt_k = __expf(-(c_k - beta) / lambda) on F and 0
+ * elsewhere, S = sum wt, w_k = wt_k / (S + norm_eps): the reduce's own weights, so the numbers describe the update
+ * that was applied.  Pad lanes K..Kp never count.  Empty F (the solve itself returns MPPI_E_NONFINITE): n_finite = 0,
+ * k_best = -1, ess = entropy = cost_std = cost_weighted = 0, cost_min = cost_max = cost_mean = free_energy = +inf,
+ * both moments 0. */
+typedef struct mppi_solve_stats {
+  float cost_min, cost_max, cost_mean, cost_std; /* over F; std = population, two-pass (mean first)          */
+  float cost_weighted;                           /* sum_k w_k c_k                                            */
+  float ess;                                     /* S^2 / sum wt_k^2, in [1, n_finite]                       */
+  float entropy;                                 /* -sum p ln p, p = wt/S (0 ln 0 = 0), in [0, ln n_finite]  */
+  float free_energy;                             /* beta - lambda * ln(S / n_finite)                         */
+  int32_t n_finite, k_best;                      /* |F|; lowest k attaining beta                             */
+} mppi_solve_stats;
 
 typedef struct mppi_handle mppi_handle;
 
@@ -244,6 +268,30 @@ int mppi_get_seed_counter(mppi_handle* h, uint64_t* value);
 int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho);
 int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active);
 
+/* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
+ * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
+ *     eps_m2 [b][u] = 1/H     sum_{t=0..H-1} sum_k w_k eps[b][u][t][k]^2
+ *     eps_m11[b][u] = 1/(H-1) sum_{t=1..H-1} sum_k w_k eps[b][u][t][k] eps[b][u][t-1][k]      (0 when H == 1)
+ * With uniform weights sqrt(eps_m2) estimates sigma_u[u] and eps_m11 / eps_m2 estimates rho (mppi_set_noise_model).
+ * Sums are fp32 in a fixed order: bitwise repeatable from run to run (and between the two kernel forms; env
+ * MPPI_STATS_FORM=direct|seg, read per launch, forces one).
+ * mppi_get_stats waits for the stream and copies to host memory: stats [B], eps_m2 / eps_m11 [B][nu]; each pointer
+ * may be NULL.  step = 0 after a plain or chained solve; after mppi_graph_launch of a graph captured with the flag,
+ * step = 0..n_solves-1 (solve i of the chain writes slot i; the slots are allocated before the capture begins).
+ * MPPI_E_STATE if no solve with the flag has run on the handle; MPPI_E_ARG for step or B beyond that solve / graph.
+ * The last statistics stay readable after mppi_set_noise_model destroyed the graph.
+ * mppi_device_stats: the device buffers for consumers on the stream, slot-major with the handle's max_batch as the
+ * batch pitch: stats [slot][max_batch] (mppi_solve_stats), m2 / m11 [slot][max_batch][nu].  Valid until a graph with
+ * more solves than any before is captured with the flag (the buffers grow then).  Each pointer may be NULL.
+ * mppi_stats_eval: the same kernels on host arrays, costs [B][K] and noise [B][nu][H][K] (or NULL: only the struct is
+ * computed) -- offline analysis, and the entry that can be fed non-finite costs.  Needs only mppi_create.  It goes
+ * through the handle's staging buffers (its costs and noise): a prefetched noise is dropped as by
+ * mppi_set_noise_model (key sequence unchanged); the statistics of the last solve stay readable. */
+int mppi_get_stats(mppi_handle* h, int B, int step, mppi_solve_stats* stats, float* eps_m2, float* eps_m11);
+int mppi_device_stats(mppi_handle* h, void** d_stats, void** d_m2, void** d_m11);
+int mppi_stats_eval(mppi_handle* h, int B, const float* costs, const float* noise, mppi_solve_stats* stats,
+                    float* eps_m2, float* eps_m11);
+
 /* MPPI_PREC_BF16X3 with a CrossAttention net: *products = the products layer 1 runs with (2 or 3; 0 = not a split CA
  * handle, or no solve yet), *probe_rel_err = the probe's max relative cost difference between the two forms (-1: no
  * probe ran: forced by env, or H > 64).  Either pointer may be NULL. */
@@ -270,7 +318,7 @@ int mppi_sync(mppi_handle* h);
 
 /* Per-kernel timing with hipEvents recorded on the handle's stream around each launch.
  * enable != 0 starts accumulating; mppi_kernel_times returns {count, total_ms} per kernel
- * name. names: "noise", "rollout", "reduce", "update". */
+ * name. names: "noise", "rollout", "reduce", "update", "stats" (the launches of MPPI_FLAG_STATS). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
