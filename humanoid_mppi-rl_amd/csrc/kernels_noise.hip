@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "mppi_internal.h"
+#include "noise_adapt.h"
 #include "noise_model.h"
 #include "philox.h"
 
@@ -24,9 +25,27 @@ namespace mppi {
 // ------------------------------------------------------------------------------------------------
 constexpr int kAr1Tile = 4;
 
-__global__ __launch_bounds__(256) void noise_ar1_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
-                                                        uint64_t seed, const unsigned long long* seed_ctr,
-                                                        NoiseModel m) {
+// The law as the generators read it: the by-value kernel argument (NoiseModel), or the device law of a handle that
+// adapts it on the stream (mppi_set_noise_adapt; DeviceLaw: sigma_u[kMaxNu], rho, c in device memory, written by
+// noise_law_set_kernel / noise_adapt_kernel).  Both forms of a generator share one body: the same operations per
+// element in the same order, so equal law values give value-for-value the same noise.
+struct DeviceLaw {
+  const float* p;
+};
+__device__ __forceinline__ void law_read(const NoiseModel& m, int u, float& su, float& rho, float& c) {
+  su = m.sigma_u[u];
+  rho = m.rho;
+  c = m.c;
+}
+__device__ __forceinline__ void law_read(const DeviceLaw& m, int u, float& su, float& rho, float& c) {
+  su = m.p[u];
+  rho = m.p[kLawRho];
+  c = m.p[kLawC];
+}
+
+template <class Law>
+__device__ __forceinline__ void noise_ar1_body(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
+                                               uint64_t seed, const unsigned long long* seed_ctr, const Law& m) {
   const int bu = blockIdx.z * 65535 + blockIdx.y;  // b*nu + u
   const int kq = blockIdx.x * blockDim.x + threadIdx.x;
   const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
@@ -34,7 +53,8 @@ __global__ __launch_bounds__(256) void noise_ar1_kernel(float* __restrict__ nois
   const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
   const int u = bu % nu;
   const int b = bu / nu;
-  const float su = m.sigma_u[u], rho = m.rho, c = m.c;
+  float su, rho, c;
+  law_read(m, u, su, rho, c);
   typedef float f4 __attribute__((ext_vector_type(4)));
   const int nq = Kp >> 2;
   f4* dst = reinterpret_cast<f4*>(noise + (long)bu * H * Kp) + kq;  // row t: dst + t * nq
@@ -57,6 +77,17 @@ __global__ __launch_bounds__(256) void noise_ar1_kernel(float* __restrict__ nois
   }
 }
 
+__global__ __launch_bounds__(256) void noise_ar1_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
+                                                        uint64_t seed, const unsigned long long* seed_ctr,
+                                                        NoiseModel m) {
+  noise_ar1_body(noise, nbu, nu, H, Kp, seed, seed_ctr, m);
+}
+__global__ __launch_bounds__(256) void noise_ar1_dev_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
+                                                            uint64_t seed, const unsigned long long* seed_ctr,
+                                                            DeviceLaw m) {
+  noise_ar1_body(noise, nbu, nu, H, Kp, seed, seed_ctr, m);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The same values for grids too small to fill the chip (config #2: one (b, u) row of 16 k-quads, where the kernel
 // above is 16 lanes drawing H = 100 steps one after the other).  One block = kAr1LdsK = 64 consecutive k of one
@@ -69,10 +100,10 @@ constexpr int kAr1LdsK = 64;
 constexpr int kAr1LdsMaxH = 256;  // [H][64] floats <= 64 KiB
 static_assert(kKpAlign % kAr1LdsK == 0, "every block of noise_ar1_lds_kernel owns 64 existing k");
 
-__global__ __launch_bounds__(256) void noise_ar1_lds_kernel(float* __restrict__ noise, int nbu, int nu, int H,
-                                                            int Kp, uint64_t seed,
-                                                            const unsigned long long* seed_ctr, NoiseModel m) {
-  extern __shared__ __attribute__((aligned(16))) float inno[];  // [H][kAr1LdsK]
+template <class Law>
+__device__ __forceinline__ void noise_ar1_lds_body(float* inno, float* __restrict__ noise, int nbu, int nu, int H,
+                                                   int Kp, uint64_t seed, const unsigned long long* seed_ctr,
+                                                   const Law& m) {
   const int bu = blockIdx.z * 65535 + blockIdx.y;  // b*nu + u
   const int k_base = blockIdx.x * kAr1LdsK;
   const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
@@ -80,7 +111,8 @@ __global__ __launch_bounds__(256) void noise_ar1_lds_kernel(float* __restrict__ 
   const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
   const int u = bu % nu;
   const int b = bu / nu;
-  const float su = m.sigma_u[u], rho = m.rho, c = m.c;
+  float su, rho, c;
+  law_read(m, u, su, rho, c);
   typedef float f4 __attribute__((ext_vector_type(4)));
   constexpr int kQ = kAr1LdsK / 4;  // k-quads per block
   for (int i = threadIdx.x; i < H * kQ; i += blockDim.x) {
@@ -104,6 +136,19 @@ __global__ __launch_bounds__(256) void noise_ar1_lds_kernel(float* __restrict__ 
   }
 }
 
+__global__ __launch_bounds__(256) void noise_ar1_lds_kernel(float* __restrict__ noise, int nbu, int nu, int H,
+                                                            int Kp, uint64_t seed,
+                                                            const unsigned long long* seed_ctr, NoiseModel m) {
+  extern __shared__ __attribute__((aligned(16))) float inno[];  // [H][kAr1LdsK]
+  noise_ar1_lds_body(inno, noise, nbu, nu, H, Kp, seed, seed_ctr, m);
+}
+__global__ __launch_bounds__(256) void noise_ar1_lds_dev_kernel(float* __restrict__ noise, int nbu, int nu, int H,
+                                                                int Kp, uint64_t seed,
+                                                                const unsigned long long* seed_ctr, DeviceLaw m) {
+  extern __shared__ __attribute__((aligned(16))) float inno[];  // [H][kAr1LdsK]
+  noise_ar1_lds_body(inno, noise, nbu, nu, H, Kp, seed, seed_ctr, m);
+}
+
 // MPPI_NOISE_AR1=direct|lds (read per launch; an A/B and test knob): force one of the two kernels (lds: where its
 // LDS row fits, H <= 256); default: noise_ar1_lds_kernel when noise_ar1_kernel would have fewer waves than SIMDs
 static int ar1_knob() {
@@ -114,7 +159,7 @@ static int ar1_knob() {
 
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
                               const unsigned long long* seed_ctr, float sigma, const NoiseModel& model,
-                              hipStream_t stream) {
+                              hipStream_t stream, const float* d_law) {
   if (!model.active) return launch_noise(noise, B, nu, H, Kp, seed, seed_ctr, sigma, stream);
   if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_model refuses such a handle)
   const int nbu = B * nu, nq = Kp / 4;
@@ -123,13 +168,79 @@ hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64
   const bool lds = H <= kAr1LdsMaxH && (knob == 2 || (knob == 0 && waves < 4L * current_device_cus()));
   if (lds) {
     const dim3 grid(Kp / kAr1LdsK, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
-    hipLaunchKernelGGL(noise_ar1_lds_kernel, grid, dim3(256), (size_t)H * kAr1LdsK * sizeof(float), stream, noise,
-                       nbu, nu, H, Kp, seed, seed_ctr, model);
+    if (d_law)
+      hipLaunchKernelGGL(noise_ar1_lds_dev_kernel, grid, dim3(256), (size_t)H * kAr1LdsK * sizeof(float), stream,
+                         noise, nbu, nu, H, Kp, seed, seed_ctr, DeviceLaw{d_law});
+    else
+      hipLaunchKernelGGL(noise_ar1_lds_kernel, grid, dim3(256), (size_t)H * kAr1LdsK * sizeof(float), stream, noise,
+                         nbu, nu, H, Kp, seed, seed_ctr, model);
     return hipGetLastError();
   }
   const int threads = nq >= 256 ? 256 : (nq + kWave - 1) / kWave * kWave;
   const dim3 grid((nq + threads - 1) / threads, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
-  hipLaunchKernelGGL(noise_ar1_kernel, grid, dim3(threads), 0, stream, noise, nbu, nu, H, Kp, seed, seed_ctr, model);
+  if (d_law)
+    hipLaunchKernelGGL(noise_ar1_dev_kernel, grid, dim3(threads), 0, stream, noise, nbu, nu, H, Kp, seed, seed_ctr,
+                       DeviceLaw{d_law});
+  else
+    hipLaunchKernelGGL(noise_ar1_kernel, grid, dim3(threads), 0, stream, noise, nbu, nu, H, Kp, seed, seed_ctr, model);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// The device law (mppi_set_noise_adapt): [kLawFloats] = sigma_u[kMaxNu], rho, c.
+// noise_law_set_kernel: the by-value model into the device law, on the stream (no host buffer to keep alive).
+// noise_adapt_kernel: one wave behind a solve's statistics.  It records the law the solve drew its noise from into
+// hist[0..nu] (sigma_u, then rho) and moves the law by the rule of noise_adapt.h from slot-local statistics
+// (st [B], m2 / m11 [B][nu]).  Lane u owns actuator u (the batch mean of its m2, its sigma), lane 32 + u adds the
+// batch mean of its m11 beside it; lane 0 then adds the means in ascending u and updates rho and c: a fixed order,
+// bitwise repeatable.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void noise_law_set_kernel(float* __restrict__ law, NoiseModel m) {
+  const int i = threadIdx.x;
+  if (i < kMaxNu) law[i] = m.sigma_u[i];
+  if (i == kLawRho) law[i] = m.rho;
+  if (i == kLawC) law[i] = m.c;
+}
+
+__global__ __launch_bounds__(64) void noise_adapt_kernel(float* __restrict__ law, float* __restrict__ hist,
+                                                         const mppi_solve_stats* __restrict__ st,
+                                                         const float* __restrict__ m2, const float* __restrict__ m11,
+                                                         int B, int nu, NoiseAdapt a) {
+  static_assert(kWave == 2 * kMaxNu, "one half of the wave per moment");
+  __shared__ float s_bar[2][kMaxNu];  // [0]: the batch means of m2, [1]: of m11
+  const int lane = threadIdx.x;
+  const int u = lane & (kMaxNu - 1), half = lane / kMaxNu;  // lane u and lane kMaxNu + u work for actuator u
+  const float rho = law[kLawRho];
+  float s = 0.0f;
+  if (lane < nu) {
+    s = law[lane];
+    hist[lane] = s;
+  }
+  if (lane == 0) hist[nu] = rho;
+  int dead = 0;  // a solve without a finite cost: the law stays
+  for (int b = lane; b < B; b += kWave) dead |= st[b].n_finite == 0;
+  if (__any(dead)) return;  // (uniform over the wave)
+  if (u < nu) s_bar[half][u] = na_mean(half ? m11 : m2, B, nu, u);  // the two means side by side
+  __syncthreads();
+  if (lane < nu) law[lane] = na_sigma(a, s, s_bar[0][lane]);
+  if (lane == 0) {
+    const float den = na_sum(s_bar[0], nu, 1);
+    const float num = na_sum(s_bar[1], nu, 1);
+    const float r = na_rho(a, rho, num, den);
+    law[kLawRho] = r;
+    law[kLawC] = ar1_innovation_scale(r);
+  }
+}
+
+hipError_t launch_noise_law_set(float* d_law, const NoiseModel& model, hipStream_t stream) {
+  hipLaunchKernelGGL(noise_law_set_kernel, dim3(1), dim3(kWave), 0, stream, d_law, model);
+  return hipGetLastError();
+}
+
+hipError_t launch_noise_adapt(float* d_law, float* hist, const mppi_solve_stats* stats, const float* m2,
+                              const float* m11, int B, int nu, const NoiseAdapt& a, hipStream_t stream) {
+  if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_adapt refuses such a handle)
+  hipLaunchKernelGGL(noise_adapt_kernel, dim3(1), dim3(kWave), 0, stream, d_law, hist, stats, m2, m11, B, nu, a);
   return hipGetLastError();
 }
 

@@ -14,6 +14,7 @@
 #include "costs.h"
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
+#include "noise_adapt.h"  // NoiseAdapt
 #include "noise_model.h"  // ar1_innovation_scale
 
 namespace mppi {
@@ -116,6 +117,17 @@ struct mppi_handle {
   int stats_slots = 0;
   int stats_B = 0, stats_n = 0;  // batch and slot count of the last flagged solve / graph launch (0: none ran)
   bool graph_stats = false;      // the captured graph carries the flag
+  // the law adapted on the device (mppi_set_noise_adapt; noise_adapt.h, kernels_noise.hip).  While adapt_on, d_law is
+  // the law: the generators read it, noise_adapt_kernel moves it behind every solve's statistics, and noise_model
+  // only keeps active = 1.  d_law_hist [hist_slots + 1][nu + 1]: the law solve i of the last solve / graph launch drew
+  // its noise from (sigma_u, rho), allocated with and as large as the statistics' slots (ensure_stats).
+  bool adapt_on = false;
+  NoiseAdapt adapt{0.0f, 1e-3f, 10.0f, 0.95f};
+  float* d_law = nullptr;
+  float* d_law_hist = nullptr;
+  int hist_slots = 0;
+  int law_n = 0;             // history rows of the last adapting solve / graph launch (0: none ran)
+  bool graph_adapt = false;  // the captured graph adapts
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -239,7 +251,7 @@ void mppi_destroy(mppi_handle* h) {
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
-                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part};
+                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -592,24 +604,48 @@ static int ensure_stats(mppi_handle* h, int slots) {
     HIP_TRY(hipMalloc(&h->d_stats_part, np));
     HIP_TRY(hipMemset(h->d_stats_part, 0, np));
   }
-  if (slots <= h->stats_slots) return MPPI_OK;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  void* old[] = {h->d_stats, h->d_stats_m2, h->d_stats_m11};
-  for (void* p : old)
-    if (p) (void)hipFree(p);
-  h->d_stats = nullptr;
-  h->d_stats_m2 = h->d_stats_m11 = nullptr;
-  h->stats_slots = 0;
-  h->stats_B = h->stats_n = 0;
-  const size_t n = (size_t)(slots + 1) * B;
-  HIP_TRY(hipMalloc(&h->d_stats, n * sizeof(mppi_solve_stats)));
-  HIP_TRY(hipMemset(h->d_stats, 0, n * sizeof(mppi_solve_stats)));
-  HIP_TRY(hipMalloc(&h->d_stats_m2, n * c.nu * 4));
-  HIP_TRY(hipMemset(h->d_stats_m2, 0, n * c.nu * 4));
-  HIP_TRY(hipMalloc(&h->d_stats_m11, n * c.nu * 4));
-  HIP_TRY(hipMemset(h->d_stats_m11, 0, n * c.nu * 4));
-  h->stats_slots = slots;
+  if (slots > h->stats_slots) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    void* old[] = {h->d_stats, h->d_stats_m2, h->d_stats_m11};
+    for (void* p : old)
+      if (p) (void)hipFree(p);
+    h->d_stats = nullptr;
+    h->d_stats_m2 = h->d_stats_m11 = nullptr;
+    h->stats_slots = 0;
+    h->stats_B = h->stats_n = 0;
+    const size_t n = (size_t)(slots + 1) * B;
+    // (cleared in stream order: a memset on the null stream is not ordered against the handle's non-blocking stream)
+    HIP_TRY(hipMalloc(&h->d_stats, n * sizeof(mppi_solve_stats)));
+    HIP_TRY(hipMemsetAsync(h->d_stats, 0, n * sizeof(mppi_solve_stats), h->stream));
+    HIP_TRY(hipMalloc(&h->d_stats_m2, n * c.nu * 4));
+    HIP_TRY(hipMemsetAsync(h->d_stats_m2, 0, n * c.nu * 4, h->stream));
+    HIP_TRY(hipMalloc(&h->d_stats_m11, n * c.nu * 4));
+    HIP_TRY(hipMemsetAsync(h->d_stats_m11, 0, n * c.nu * 4, h->stream));
+    h->stats_slots = slots;
+  }
+  if (h->adapt_on && h->hist_slots < h->stats_slots) {  // the law history: one row per statistics slot, grown alike
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->d_law_hist) (void)hipFree(h->d_law_hist);
+    h->d_law_hist = nullptr;
+    h->hist_slots = 0;
+    h->law_n = 0;
+    const size_t n = (size_t)(h->stats_slots + 1) * (c.nu + 1) * 4;
+    HIP_TRY(hipMalloc(&h->d_law_hist, n));
+    HIP_TRY(hipMemsetAsync(h->d_law_hist, 0, n, h->stream));  // in stream order, ahead of the kernels that write rows
+    h->hist_slots = h->stats_slots;
+  }
   return MPPI_OK;
+}
+
+// the generators' law argument: the device law of an adapting handle, else nullptr (the by-value model)
+static const float* gen_law(const mppi_handle* h) { return h->adapt_on ? h->d_law : nullptr; }
+
+// Behind the statistics of slot `slot`: record the law the solve drew from, move the device law one step.
+static hipError_t enqueue_adapt(mppi_handle* h, int B, int slot) {
+  const mppi_config& c = h->cfg;
+  const size_t off = (size_t)slot * c.max_batch;
+  return launch_noise_adapt(h->d_law, h->d_law_hist + (size_t)slot * (c.nu + 1), h->d_stats + off,
+                            h->d_stats_m2 + off * c.nu, h->d_stats_m11 + off * c.nu, B, c.nu, h->adapt, h->stream);
 }
 
 // The diagnostics of B solves from costs [B][Kp] and noise [B][nu][H][Kp] (or nullptr) into output slot `slot`.
@@ -764,7 +800,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     if (!tmp.empty()) HIP_TRY(hipStreamSynchronize(s));
   } else if (!ns) {
     HIP_TRY(timed(h, kNoise, [&] {
-      return launch_noise_model(a.noise, B, nu, H, Kp, seed, a.seed_ctr, c.sigma, h->noise_model, s);
+      return launch_noise_model(a.noise, B, nu, H, Kp, seed, a.seed_ctr, c.sigma, h->noise_model, s, gen_law(h));
     }));
   }
 
@@ -788,9 +824,14 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // behind it (ev_red), only ever write the OTHER buffer of the pair before this point
   if (flags & MPPI_FLAG_STATS)
     HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, a.costs, a.noise, stats_slot); }));
+  // the adapted law (mppi_set_noise_adapt; every such solve carries the flag): one wave directly behind the statistics
+  // and ahead of the launch below that draws the next solve's noise, so chained and captured streams draw solve i + 1
+  // from the law adapted on solve i, as a loop of plain solves does
+  if (h->adapt_on) HIP_TRY(timed(h, kStats, [&] { return enqueue_adapt(h, B, stats_slot); }));
   if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
     HIP_TRY(timed(h, kNoise, [&] {
-      return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s);
+      return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s,
+                                gen_law(h));
     }));
     HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, s));
   }
@@ -882,7 +923,7 @@ static int prime_prefetch(mppi_handle* h, int B, uint64_t seed) {
   if (h->prefetch_valid) return MPPI_OK;
   const mppi_config& c = h->cfg;
   HIP_TRY(launch_noise_model(h->graph_parity ? h->d_noise2 : h->d_noise, B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr,
-                             c.sigma, h->noise_model, h->stream));
+                             c.sigma, h->noise_model, h->stream, gen_law(h)));
   HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->stream));
   h->prefetch_valid = true;
   h->prefetch_B = B;
@@ -918,6 +959,7 @@ static void note_stats(mppi_handle* h, int B, int flags) {
     h->stats_B = B;
     h->stats_n = 1;
   }
+  if (h->adapt_on) h->law_n = 1;
 }
 
 // MPPI_FLAG_CHAIN: one solve of a graph stream, launched on the stream (rollout -> reduce_kernel<GEN>, or with
@@ -929,7 +971,9 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   if (io->noise) return fail(MPPI_E_ARG, "mppi_solve: MPPI_FLAG_CHAIN draws device noise (no injected noise)");
   flags |= MPPI_FLAG_SEED_COUNTER;
   if (const int rc = ensure_stream_buffers(h); rc != MPPI_OK) return rc;
-  const bool overlap = gen_overlap() && !h->capturing;
+  // (an adapting handle ignores the overlap arm, as a capture does: it would draw the next noise ahead of this
+  // solve's update of the law)
+  const bool overlap = gen_overlap() && !h->capturing && !h->adapt_on;
   if (!overlap && h->gen_pending) {  // leaving overlap mode: order the solve stream behind the last generator launch
     HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_gen, 0));
     h->gen_pending = false;
@@ -1138,6 +1182,7 @@ int mppi_solve_ex(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int f
   if (rc != MPPI_OK) return rc;
   HIP_TRY(hipSetDevice(h->device));
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;
+  if (h->adapt_on) flags |= MPPI_FLAG_STATS;  // the adaptation reads the solve's moments
   if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, 1)) != MPPI_OK) return rc;
   if (flags & MPPI_FLAG_CHAIN) return chain_solve(h, B, io, seed, flags);
   HIP_TRY(drop_prefetch(h));  // a plain solve generates its own noise into d_noise
@@ -1163,6 +1208,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   flags = (flags | MPPI_FLAG_SEED_COUNTER | MPPI_FLAG_ASYNC) & ~MPPI_FLAG_COLMAJOR;
   int rc = check_solve(h, B, io, flags);
   if (rc != MPPI_OK) return rc;
+  if (h->adapt_on) flags |= MPPI_FLAG_STATS;  // the adaptation reads solve i's moments out of slot i
   HIP_TRY(hipSetDevice(h->device));
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;  // before the capture: it synchronises the stream
   for (hipGraphExec_t& g : h->graph_exec)
@@ -1211,6 +1257,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->capturing = false;
   h->graph_kclock = h->kclock;
   h->graph_stats = (flags & MPPI_FLAG_STATS) != 0;
+  h->graph_adapt = h->adapt_on;
   h->graph_B = B;
   h->graph_n = n_solves;
   h->graph_seed = seed;
@@ -1234,6 +1281,7 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
     h->stats_B = h->graph_B;
     h->stats_n = h->graph_n;
   }
+  if (h->graph_adapt) h->law_n = h->graph_n;
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1296,17 +1344,105 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
       g = nullptr;
     }
   NoiseModel m;
-  m.active = active ? 1 : 0;
+  m.active = active || h->adapt_on ? 1 : 0;  // (an adapting handle's model stays active: (NULL, 0) is its values)
   m.rho = rho;
   m.c = ar1_innovation_scale(rho);
-  if (active)
+  if (m.active)
     for (int u = 0; u < nu; ++u) m.sigma_u[u] = sigma_u ? sigma_u[u] : h->cfg.sigma;
+  if (h->adapt_on) HIP_TRY(launch_noise_law_set(h->d_law, m, h->stream));  // the device law starts again from here
   h->noise_model = m;
+  return MPPI_OK;
+}
+
+// the device law -> h->noise_model (waits for the stream); c is the host's, as for every by-value model
+static int fetch_law(mppi_handle* h) {
+  float law[kLawFloats];
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(law, h->d_law, sizeof(law), hipMemcpyDeviceToHost));
+  NoiseModel& m = h->noise_model;
+  m.active = 1;
+  for (int u = 0; u < h->cfg.nu; ++u) m.sigma_u[u] = law[u];
+  m.rho = law[kLawRho];
+  m.c = ar1_innovation_scale(m.rho);
+  return MPPI_OK;
+}
+
+int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigma_max, float rho_max) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_adapt: null handle");
+  if (!(rate >= 0.0f && rate <= 1.0f)) return fail(MPPI_E_ARG, "mppi_set_noise_adapt: rate must be in [0, 1]");
+  if (!(sigma_min >= 0.0f && sigma_min <= sigma_max && std::isfinite(sigma_max)))
+    return fail(MPPI_E_ARG, "mppi_set_noise_adapt: need 0 <= sigma_min <= sigma_max < inf");
+  if (!(rho_max >= 0.0f && rho_max < 1.0f)) return fail(MPPI_E_ARG, "mppi_set_noise_adapt: rho_max must be in [0, 1)");
+  const bool on = rate > 0.0f;
+  if (on && h->cfg.nu > kMaxNu)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: the adapted law is an active noise model (nu <= 32)");
+  if (!on && !h->adapt_on) {  // nothing to disable: only the limits are kept
+    h->adapt = NoiseAdapt{0.0f, sigma_min, sigma_max, rho_max};
+    return MPPI_OK;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state, as in mppi_set_noise_model: the prefetched noise (the counter steps back: the key sequence is
+  // unchanged) and the captured graphs, whose generators are those of the other path
+  HIP_TRY(drop_prefetch(h));
+  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
+  for (hipGraphExec_t& g : h->graph_exec)
+    if (g) {
+      HIP_TRY(hipGraphExecDestroy(g));
+      g = nullptr;
+    }
+  if (on && !h->adapt_on) {
+    // (no memset: noise_law_set_kernel below writes every entry, in stream order; a memset on the null stream is not
+    // ordered against the handle's stream and could land behind it)
+    if (!h->d_law) HIP_TRY(hipMalloc(&h->d_law, kLawFloats * sizeof(float)));
+    NoiseModel m = h->noise_model;
+    if (!m.active) {  // the default law as an active model: value for value the same noise
+      m = NoiseModel{};
+      m.active = 1;
+      for (int u = 0; u < h->cfg.nu; ++u) m.sigma_u[u] = h->cfg.sigma;
+    }
+    HIP_TRY(launch_noise_law_set(h->d_law, m, h->stream));
+    h->noise_model = m;
+    h->adapt_on = true;
+    h->law_n = 0;
+  } else if (!on) {  // back to the by-value path with the law as it stands
+    if (const int rc = fetch_law(h); rc != MPPI_OK) return rc;
+    h->adapt_on = false;
+  }
+  h->adapt = NoiseAdapt{rate, sigma_min, sigma_max, rho_max};
+  return MPPI_OK;
+}
+
+int mppi_get_noise_adapt(mppi_handle* h, float* rate, float* sigma_min, float* sigma_max, float* rho_max) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_adapt: null handle");
+  if (rate) *rate = h->adapt_on ? h->adapt.rate : 0.0f;
+  if (sigma_min) *sigma_min = h->adapt.sigma_min;
+  if (sigma_max) *sigma_max = h->adapt.sigma_max;
+  if (rho_max) *rho_max = h->adapt.rho_max;
+  return MPPI_OK;
+}
+
+int mppi_get_noise_law(mppi_handle* h, int step, float* sigma_u, float* rho) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_law: null handle");
+  if (h->law_n == 0) return fail(MPPI_E_STATE, "mppi_get_noise_law: no adapting solve has run on the handle");
+  if (step < 0 || step >= h->law_n)
+    return fail(MPPI_E_ARG, "mppi_get_noise_law: step beyond the solves of the last adapting solve or graph");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  const int nu = h->cfg.nu;
+  float row[kMaxNu + 1];
+  HIP_TRY(hipMemcpy(row, h->d_law_hist + (size_t)step * (nu + 1), (size_t)(nu + 1) * 4, hipMemcpyDeviceToHost));
+  if (sigma_u)
+    for (int u = 0; u < nu; ++u) sigma_u[u] = row[u];
+  if (rho) *rho = row[nu];
   return MPPI_OK;
 }
 
 int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active) {
   if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_model: null handle");
+  if (h->adapt_on) {  // the live law: every enqueued solve's update included
+    HIP_TRY(hipSetDevice(h->device));
+    if (const int rc = fetch_law(h); rc != MPPI_OK) return rc;
+  }
   const NoiseModel& m = h->noise_model;
   if (sigma_u)
     for (int u = 0; u < h->cfg.nu; ++u) sigma_u[u] = m.active ? m.sigma_u[u] : h->cfg.sigma;

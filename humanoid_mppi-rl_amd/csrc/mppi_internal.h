@@ -5,6 +5,8 @@
 
 #include "../../include/mppi.h"
 
+struct NoiseAdapt;  // noise_adapt.h: the settings of mppi_set_noise_adapt
+
 namespace mppi {
 
 constexpr int kWave = 64;
@@ -258,10 +260,19 @@ struct NoiseModel {
   float sigma_u[kMaxNu] = {0};
 };
 // every explicit generation site: noise_kernel (inactive model, sigma) or, with the model active, noise_ar1_kernel /
-// noise_ar1_lds_kernel (grids too small to fill the chip); kernels_noise.hip
+// noise_ar1_lds_kernel (grids too small to fill the chip); kernels_noise.hip.  d_law (or nullptr): the device law of
+// a handle that adapts it on the stream (mppi_set_noise_adapt) -- the same generators reading sigma_u, rho and c from
+// device memory instead of the by-value model (noise_ar1_dev_kernel / noise_ar1_lds_dev_kernel)
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
                               const unsigned long long* seed_ctr, float sigma, const NoiseModel& model,
-                              hipStream_t stream);
+                              hipStream_t stream, const float* d_law = nullptr);
+// The device law [kLawFloats] = sigma_u[kMaxNu], rho, c: set from a by-value model on the stream, and moved one step
+// by the rule of noise_adapt.h from one statistics slot (stats [B], m2 / m11 [B][nu]) after the law the solve drew
+// from was recorded into hist[0..nu] (sigma_u, rho).  One wave each; capturable.
+constexpr int kLawRho = kMaxNu, kLawC = kMaxNu + 1, kLawFloats = kMaxNu + 2;
+hipError_t launch_noise_law_set(float* d_law, const NoiseModel& model, hipStream_t stream);
+hipError_t launch_noise_adapt(float* d_law, float* hist, const mppi_solve_stats* stats, const float* m2,
+                              const float* m11, int B, int nu, const NoiseAdapt& a, hipStream_t stream);
 // fc-stack rollout: fc_route (fc_route.h) decides the kernel from the shape, the image, the probe outcomes and the
 // knobs; launch_fc_route launches a given route (the engine's probe passes routes of its own)
 struct FcRoute;

@@ -16,6 +16,9 @@
 
 // c of the recursion; the square and the difference are separate statements, so no compiler contracts them into an fma
 MPPI_HD float ar1_innovation_scale(float rho) {
+#if defined(__clang__)  // ... also where the default is to contract across statements (device code: noise_adapt_kernel)
+#pragma clang fp contract(off)
+#endif
   const float r2 = rho * rho;
   return sqrtf(1.0f - r2);
 }

@@ -223,6 +223,44 @@ function set_noise_model!(c::Controller; sigma_u = nothing, rho::Real = 0.0)
 end
 
 """
+    set_noise_adapt!(c, rate; sigma_min = 1e-3, sigma_max = 10.0, rho_max = 0.95)
+
+Adapt the sampling law on the device behind every solve (mppi_set_noise_adapt): `rate` in (0, 1] enables, 0 disables
+and keeps the law as it stands.  Chained solves and graph streams adapt step by step with no host round trip.
+"""
+function set_noise_adapt!(c::Controller, rate::Real; sigma_min::Real = 1e-3, sigma_max::Real = 10.0,
+                          rho_max::Real = 0.95)
+    check(ccall((:mppi_set_noise_adapt, LIB), Cint, (Ptr{Cvoid}, Cfloat, Cfloat, Cfloat, Cfloat), c.handle, rate,
+                sigma_min, sigma_max, rho_max))
+    return c
+end
+
+"""
+    noise_adapt(c) -> (rate, sigma_min, sigma_max, rho_max)
+
+The settings of `set_noise_adapt!` (mppi_get_noise_adapt); `rate` is 0 while adaptation is off.
+"""
+function noise_adapt(c::Controller)
+    v = [Ref{Cfloat}(0) for _ in 1:4]
+    check(ccall((:mppi_get_noise_adapt, LIB), Cint, (Ptr{Cvoid}, Ref{Cfloat}, Ref{Cfloat}, Ref{Cfloat}, Ref{Cfloat}),
+                c.handle, v[1], v[2], v[3], v[4]))
+    return (v[1][], v[2][], v[3][], v[4][])
+end
+
+"""
+    noise_law(c; step = 0) -> (sigma_u::Vector{Float32}, rho::Float32)
+
+The law the adapting solve `step` drew its noise from (mppi_get_noise_law; waits for the stream).
+"""
+function noise_law(c::Controller; step::Integer = 0)
+    s = zeros(Float32, c.cfg.nu)
+    rho = Ref{Cfloat}(0)
+    GC.@preserve s check(ccall((:mppi_get_noise_law, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Ref{Cfloat}),
+                               c.handle, step, pointer(s), rho))
+    return (s, rho[])
+end
+
+"""
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 
 The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and

@@ -26,7 +26,8 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_graph_launch", "mppi_set_seed_counter", "mppi_get_seed_counter", "mppi_graph_capture_traj",
             "mppi_kernel_clock",
             "mppi_kernel_clock_read", "mppi_build_id", "mppi_x3_layer1", "mppi_rollout_kernel", "mppi_x3_f16",
-            "mppi_set_noise_model", "mppi_get_noise_model", "mppi_get_stats", "mppi_device_stats", "mppi_stats_eval"]
+            "mppi_set_noise_model", "mppi_get_noise_model", "mppi_get_stats", "mppi_device_stats", "mppi_stats_eval",
+            "mppi_set_noise_adapt", "mppi_get_noise_adapt", "mppi_get_noise_law"]
 
 
 class MPPIError(RuntimeError):
@@ -109,6 +110,9 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_x3_f16": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float)]),
         "mppi_set_noise_model": (i32, [vp, _fp, ctypes.c_float]),
         "mppi_get_noise_model": (i32, [vp, _fp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(i32)]),
+        "mppi_set_noise_adapt": (i32, [vp] + [ctypes.c_float] * 4),
+        "mppi_get_noise_adapt": (i32, [vp] + [ctypes.POINTER(ctypes.c_float)] * 4),
+        "mppi_get_noise_law": (i32, [vp, i32, _fp, ctypes.POINTER(ctypes.c_float)]),
         "mppi_get_stats": (i32, [vp, i32, i32, vp, vp, vp]),
         "mppi_device_stats": (i32, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]),
         "mppi_stats_eval": (i32, [vp, i32, vp, vp, vp, vp, vp]),

@@ -57,14 +57,18 @@ class MPPIModel:
     adapt_noise: above 0, mppi_step / mppi_controller request the solve's statistics (Engine.solve(stats=True)) and
               after each step move the law towards the weighted moments of the noise that won
               (stats.adapt_noise_model with this rate and adapt_limits = (sigma_min, sigma_max, rho_max)), through
-              Engine.set_noise_model.  The moments are about the nominal U.  Setting the law destroys captured graphs
-              (mppi_set_noise_model), so a graph stream on the same engine has to be captured again after a step.
+              Engine.set_noise_model.  The moments are about the nominal U.
+    adapt_on: "host" (default): the loop above -- statistics read back, the next law computed in numpy and set through
+              Engine.set_noise_model per step (which destroys captured graphs).  "device": Engine.set_noise_adapt, the
+              same rule in fp32 in a kernel behind each solve's statistics; no statistics are requested and no law is
+              set per step, chained solves and graph streams on the engine adapt step by step and stay captured, and
+              noise_sigma / noise_rho read the engine's live law.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
                  noise: str = "device", seed: int = 0, precision: int = L.PREC_BF16, ctx=None,
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
-                 adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), **overrides):
+                 adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -94,18 +98,49 @@ class MPPIModel:
         self.target = tuple(float(v) for v in np.asarray(ctx, np.float64).ravel()[:3]) if ctx is not None \
             else HUMANOID_TARGET
         self.U_global = np.zeros((self.config.nu, self.config.H))
-        self.noise_sigma = None if noise_sigma is None else np.asarray(noise_sigma, np.float64).ravel()
-        self.noise_rho = float(noise_rho)
-        if self.noise_sigma is not None or self.noise_rho != 0.0:
-            self.engine.set_noise_model(self.noise_sigma, self.noise_rho)
+        self.adapt_on = adapt_on
+        if adapt_on not in ("host", "device"):
+            raise ValueError('MPPIModel: adapt_on must be "host" or "device"')
         self.adapt_noise = float(adapt_noise)
         self.adapt_limits = tuple(float(v) for v in adapt_limits)
         if not 0.0 <= self.adapt_noise <= 1.0:
             raise ValueError("MPPIModel: adapt_noise must be in [0, 1]")
+        self.noise_sigma = None if noise_sigma is None else np.asarray(noise_sigma, np.float64).ravel()
+        self.noise_rho = float(noise_rho)
+        if self._noise_sigma is not None or self._noise_rho != 0.0:
+            self.engine.set_noise_model(self._noise_sigma, self._noise_rho)
+        if self.device_adapt:
+            self.engine.set_noise_adapt(self.adapt_noise, *self.adapt_limits)
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0
         self.last = None  # SolveResult of the last mppi_step (costs, weights) for inspection
+
+    @property
+    def device_adapt(self) -> bool:
+        """The engine adapts the law itself (adapt_on="device" with adapt_noise > 0)."""
+        return getattr(self, "adapt_on", "host") == "device" and getattr(self, "adapt_noise", 0.0) > 0.0
+
+    # the sampling law: the host's copy, or (device adaptation) the engine's live law
+    @property
+    def noise_sigma(self):
+        if self.device_adapt:
+            return self.engine.noise_model()[0].astype(np.float64)
+        return self._noise_sigma
+
+    @noise_sigma.setter
+    def noise_sigma(self, v):
+        self._noise_sigma = v
+
+    @property
+    def noise_rho(self):
+        if self.device_adapt:
+            return float(self.engine.noise_model()[1])
+        return self._noise_rho
+
+    @noise_rho.setter
+    def noise_rho(self, v):
+        self._noise_rho = v
 
     @property
     def K(self):
@@ -230,14 +265,18 @@ def rollout_learned_model_batched(model: MPPIModel, state, U, noise, device=None
     return res.costs.astype(np.float64)
 
 
+def _device_adapt(model) -> bool:
+    return bool(getattr(model, "device_adapt", False))
+
+
 def _stats_kw(model) -> dict:
     """stats=True for the solve of a model that adapts its sampling law; nothing otherwise (the solve call of a model
     that does not adapt is what it always was)."""
-    return {"stats": True} if getattr(model, "adapt_noise", 0.0) > 0.0 else {}
+    return {"stats": True} if getattr(model, "adapt_noise", 0.0) > 0.0 and not _device_adapt(model) else {}
 
 
 def _adapt(model, res):
-    if getattr(model, "adapt_noise", 0.0) > 0.0 and res.status == L.MPPI_OK:
+    if getattr(model, "adapt_noise", 0.0) > 0.0 and res.status == L.MPPI_OK and not _device_adapt(model):
         model.adapt(res.stats)
 
 

@@ -124,12 +124,36 @@ class Engine:
         return self
 
     def noise_model(self) -> tuple[np.ndarray, float, bool]:
-        """(sigma_u [nu], rho, active) of the handle's sampling law (mppi_get_noise_model)."""
+        """(sigma_u [nu], rho, active) of the handle's sampling law (mppi_get_noise_model).  With set_noise_adapt on
+        it is the live device law after every enqueued solve (waits for the stream)."""
         s = np.empty(self.config.nu, np.float32)
         rho, active = ctypes.c_float(), ctypes.c_int()
         L.check(self.lib.mppi_get_noise_model(self._h, s.ctypes.data_as(L._fp), ctypes.byref(rho),
                                               ctypes.byref(active)))
         return s, float(rho.value), bool(active.value)
+
+    def set_noise_adapt(self, rate: float, sigma_min: float = 1e-3, sigma_max: float = 10.0, rho_max: float = 0.95):
+        """Adapt the sampling law on the device behind every solve (mppi_set_noise_adapt; the rule is
+        stats.adapt_noise_model_f32): rate in (0, 1] enables, 0 disables and keeps the law as it stands.  Chained
+        solves and graph streams adapt step by step with no host round trip.  Destroys captured graphs, as
+        set_noise_model does."""
+        L.check(self.lib.mppi_set_noise_adapt(self._h, ctypes.c_float(rate), ctypes.c_float(sigma_min),
+                                              ctypes.c_float(sigma_max), ctypes.c_float(rho_max)))
+        return self
+
+    def noise_adapt(self) -> tuple[float, float, float, float]:
+        """(rate, sigma_min, sigma_max, rho_max) of mppi_get_noise_adapt; rate 0.0 while adaptation is off."""
+        v = [ctypes.c_float() for _ in range(4)]
+        L.check(self.lib.mppi_get_noise_adapt(self._h, *(ctypes.byref(x) for x in v)))
+        return tuple(float(x.value) for x in v)
+
+    def noise_law(self, step: int = 0) -> tuple[np.ndarray, float]:
+        """(sigma_u [nu], rho) the adapting solve `step` drew its noise from (mppi_get_noise_law; waits for the
+        stream): step 0 after a plain or chained solve, 0..n_solves-1 after graph_launch."""
+        s = np.empty(self.config.nu, np.float32)
+        rho = ctypes.c_float()
+        L.check(self.lib.mppi_get_noise_law(self._h, step, s.ctypes.data_as(L._fp), ctypes.byref(rho)))
+        return s, float(rho.value)
 
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,

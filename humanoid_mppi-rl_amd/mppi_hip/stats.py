@@ -13,9 +13,12 @@ S = sum wt and w_k = wt_k / (S + norm_eps) -- the weights of the update itself:
     eps_m11[u]  = 1/(H-1) sum_{t>=1} sum_k w_k eps[u,t,k] eps[u,t-1,k]     (0 when H == 1)
 
 The device computes these in fp32 (fp64 for the cost sums); solve_stats_ref is the float64 restatement: the reference
-of the tests, and for users.  adapt_noise_model turns the moments into the next sampling law.
+of the tests, and for users.  adapt_noise_model turns the moments into the next sampling law; adapt_noise_model_f32 is
+the same step as the device takes it (mppi_set_noise_adapt), float32 operation by operation.
 """
 from __future__ import annotations
+
+from fractions import Fraction
 
 import numpy as np
 
@@ -108,3 +111,85 @@ def adapt_noise_model(sigma_u, rho: float, eps_m2, eps_m11, rate: float, sigma_m
     den = m2.sum()
     rho_hat = float(np.clip(m11.sum() / den, 0.0, rho_max)) if den > 0.0 else 0.0
     return sigma_new, (1.0 - rate) * rho + rate * rho_hat
+
+
+def _round_f32(v) -> np.float32:
+    """The exact rational v rounded once to fp32 (nearest, ties to even)."""
+    f = np.float32(float(v))  # (rounded twice: the neighbours decide)
+    best = None
+    for c in (f, np.nextafter(f, np.float32(np.inf)), np.nextafter(f, np.float32(-np.inf))):
+        if not np.isfinite(c):
+            continue
+        d = abs(Fraction(float(c)) - v)
+        even = (int(np.float32(c).view(np.uint32)) & 1) == 0
+        if best is None or d < best[0] or (d == best[0] and even and not best[2]):
+            best = (d, np.float32(c), even)
+    return f if best is None else best[1]
+
+
+def _fma32(a, b, c) -> np.float32:
+    """fmaf(a, b, c): the exact a * b + c rounded once to fp32 (non-finite operands as numpy propagates them)."""
+    a, b, c = np.float32(a), np.float32(b), np.float32(c)
+    if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(c)):
+        with np.errstate(all="ignore"):
+            return np.float32(np.float64(a) * np.float64(b) + np.float64(c))
+    v = Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c))
+    if abs(v) >= Fraction(2) ** 128:
+        return np.float32(np.inf if v > 0 else -np.inf)
+    return _round_f32(v)
+
+
+def adapt_noise_model_f32(sigma_u, rho, eps_m2, eps_m11, rate, sigma_min=1e-3, sigma_max=10.0, rho_max=0.95,
+                          n_finite=None):
+    """The device's adaptation step (csrc/noise_adapt.h, mppi_set_noise_adapt) restated in numpy float32, operation by
+    operation: (sigma_u [nu] float32, rho float32) after one step from the law (sigma_u, rho) and the moments
+    eps_m2, eps_m11 [B, nu] (or [nu]) of one batch.  Bitwise what noise_adapt_kernel writes.
+
+        if any n_finite[b] == 0: the law is returned unchanged
+        m2bar[u]  = (m2[0][u] + m2[1][u] + ...) / float32(B)        sequential float32 sums, b ascending; m11bar alike
+        var       = fmaf(rate, m2bar[u], (1 - rate) * (s * s));     sigma_u[u] = min(max(sqrt(var), sigma_min), sigma_max)
+        den, num  = sum_u m2bar[u], sum_u m11bar[u]                 u ascending
+        rho_hat   = clamp(num / den, 0, rho_max) if den > 0 else 0
+        rho       = fmaf(rate, rho_hat, (1 - rate) * rho)
+        a non-finite var or rho leaves that entry as it was
+
+    adapt_noise_model is the same rule in float64 (it raises on invalid input, this one follows the kernel)."""
+    f = np.float32
+    s = np.atleast_1d(np.asarray(sigma_u, f)).ravel().copy()
+    nu = s.size
+    m2 = np.asarray(eps_m2, f).reshape(-1, nu)
+    m11 = np.asarray(eps_m11, f).reshape(-1, nu)
+    B = m2.shape[0]
+    rho, rate, lo, hi, rho_max = f(rho), f(rate), f(sigma_min), f(sigma_max), f(rho_max)
+    if n_finite is not None and np.any(np.asarray(n_finite).ravel()[:B] == 0):
+        return s, rho
+
+    def mean(col):
+        acc = f(0.0)
+        for b in range(B):
+            acc = f(acc + col[b])
+        return f(acc / f(B))
+
+    with np.errstate(all="ignore"):
+        keep = f(f(1.0) - rate)
+        m2bar = [mean(m2[:, u]) for u in range(nu)]
+        m11bar = [mean(m11[:, u]) for u in range(nu)]
+        for u in range(nu):
+            var = _fma32(rate, m2bar[u], f(keep * f(s[u] * s[u])))
+            r = np.sqrt(var, dtype=f)
+            if not (np.isfinite(var) and np.isfinite(r)):
+                continue
+            r = lo if r < lo else r
+            r = hi if r > hi else r
+            s[u] = r
+        den, num = f(0.0), f(0.0)
+        for u in range(nu):
+            den = f(den + m2bar[u])
+            num = f(num + m11bar[u])
+        rho_hat = f(0.0)
+        if den > 0.0:
+            rho_hat = f(num / den)
+            rho_hat = f(0.0) if rho_hat < 0.0 else rho_hat
+            rho_hat = rho_max if rho_hat > rho_max else rho_hat
+        r = _fma32(rate, rho_hat, f(keep * rho))
+    return s, (r if np.isfinite(r) else rho)

@@ -66,7 +66,10 @@ extern "C" {
  *      correlation of the device noise).  A handle that never calls them behaves exactly as before.
  *      Additive, version unchanged: MPPI_FLAG_STATS, mppi_solve_stats, mppi_get_stats / mppi_device_stats /
  *      mppi_stats_eval (softmin statistics and weighted noise moments of a solve); kernel name "stats" in
- *      mppi_kernel_time.  A solve without the flag launches exactly the kernels it launched before. */
+ *      mppi_kernel_time.  A solve without the flag launches exactly the kernels it launched before.
+ *      Additive, version unchanged: mppi_set_noise_adapt / mppi_get_noise_adapt / mppi_get_noise_law (the sampling
+ *      law adapted on the device behind each solve's statistics).  A handle that never enables it launches exactly
+ *      the kernels it launched before, with the same arguments. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -267,6 +270,36 @@ int mppi_get_seed_counter(mppi_handle* h, uint64_t* value);
  * mppi_get_noise_model: sigma_u [nu] or NULL, rho, active; each pointer may be NULL. */
 int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho);
 int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active);
+
+/* The sampling law adapted ON THE DEVICE, solve by solve, with no host round trip: chained solves, MPPI_FLAG_ASYNC and
+ * captured graph streams adapt step by step and give bit for bit what a loop of plain solves gives.
+ * With adaptation on, the law (sigma_u, rho, c) lives in device memory, the AR(1) generators read it from there, and
+ * every solve (plain with host or device pointers, ASYNC, CHAIN, every solve of a captured graph) behaves as if
+ * MPPI_FLAG_STATS were set and runs one more one-wave kernel directly behind its statistics, ahead of the launch that
+ * draws the next solve's noise.  That kernel moves the law towards the batch's weighted noise moments (eps_m2,
+ * eps_m11 below; the fp32 rule is csrc/noise_adapt.h, its numpy restatement mppi_hip.stats.adapt_noise_model_f32):
+ *     var = rate * mean_b eps_m2[b][u] + (1 - rate) * sigma_u[u]^2;   sigma_u[u] = clamp(sqrt(var), sigma_min, sigma_max)
+ *     rho_hat = clamp(sum_u mean_b eps_m11 / sum_u mean_b eps_m2, 0, rho_max)   (0 when the denominator is not > 0)
+ *     rho = rate * rho_hat + (1 - rate) * rho
+ * One law per handle, shared by the batch's B solves.  A batch in which some solve had no finite cost
+ * (MPPI_E_NONFINITE) leaves the law unchanged.  Injected io.noise is allowed: the moments are the injected noise's.
+ * mppi_stats_eval never adapts.  MPPI_GEN_OVERLAP=1 is ignored while adaptation is on.
+ * mppi_set_noise_adapt: rate in (0, 1] enables, rate == 0 disables and returns the handle to the by-value path with
+ * the law as it stands; 0 <= sigma_min <= sigma_max < inf and 0 <= rho_max < 1; anything else is MPPI_E_ARG and changes
+ * nothing.  Enabling makes the model active (an inactive one becomes sigma_u = cfg.sigma, rho = 0) and so needs
+ * nu <= 32 (MPPI_E_UNSUPPORTED otherwise).  Enabling, disabling and changing the settings drop a prefetched noise and
+ * destroy captured graphs exactly as mppi_set_noise_model does; the key sequence is unchanged.
+ * While adaptation is on, mppi_set_noise_model keeps its semantics and also resets the device law to the given
+ * values, and mppi_get_noise_model waits for the stream and returns the current device law: saved together with
+ * mppi_get_U and mppi_get_seed_counter, and restored on a fresh handle (mppi_set_noise_model, mppi_set_noise_adapt,
+ * mppi_set_U, mppi_set_seed_counter), it continues any stream bit for bit.
+ * mppi_get_noise_adapt: the settings (*rate = 0 while off); each pointer may be NULL.
+ * mppi_get_noise_law: the law solve `step` drew its noise from, sigma_u [nu] and rho (each may be NULL); waits for the
+ * stream.  step as for mppi_get_stats: 0 after a plain or chained solve, 0..n_solves-1 after a graph launch;
+ * MPPI_E_STATE if no adapting solve has run, MPPI_E_ARG for a step beyond that solve / graph. */
+int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigma_max, float rho_max);
+int mppi_get_noise_adapt(mppi_handle* h, float* rate, float* sigma_min, float* sigma_max, float* rho_max);
+int mppi_get_noise_law(mppi_handle* h, int step, float* sigma_u, float* rho);
 
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
