@@ -179,7 +179,7 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
   float beta = red[0];
   for (int i = 1; i < nw; ++i) beta = fminf(beta, red[i]);
   __syncthreads();
-  const float inv_lam = 1.0f / a.lambda;
+  const float inv_lam = 1.0f / (a.lambda_dev ? a.lambda_dev[b] : a.lambda);  // (ESS targeting: the solve's own)
   float s = 0.0f;
   for (int k = tid; k < a.Kp; k += nt) {
     float wk = 0.0f;

@@ -104,7 +104,8 @@ __global__ __launch_bounds__(kStatsCostThreads) void stats_cost_kernel(StatsArgs
   const int n = (int)cnt;
   const float beta = (float)mn;  // (exact: the minimum of floats)
   const double mean = n > 0 ? sum / cnt : (double)INFINITY;
-  const float inv_lam = 1.0f / a.lambda;
+  const float lambda = a.lambda_dev ? a.lambda_dev[b] : a.lambda;  // (ESS targeting: the solve's own)
+  const float inv_lam = 1.0f / lambda;
   double S = 0.0, S2 = 0.0, SC = 0.0, SX = 0.0, V = 0.0, kb = (double)INT_MAX;
   each([&](int k, float ck) {
     if (isfinite(ck)) {  // (n > 0 here, so beta is finite)
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(kStatsCostThreads) void stats_cost_kernel(StatsArgs
       st.cost_weighted = (float)(SC * (double)inv_S);
       st.ess = (float)(S * S / S2);
       st.entropy = (float)fmax(log(S) + SX / S, 0.0);
-      st.free_energy = (float)((double)beta - (double)a.lambda * log(S / cnt));
+      st.free_energy = (float)((double)beta - (double)lambda * log(S / cnt));
       st.n_finite = n;
       st.k_best = (int)kb;
     } else {

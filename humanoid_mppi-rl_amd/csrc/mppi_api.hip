@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "costs.h"
+#include "ess_target.h"  // EssTarget
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
 #include "noise_adapt.h"  // NoiseAdapt
@@ -41,8 +42,8 @@ static int fail(int code, const std::string& msg) {
 
 namespace {
 
-enum KernelId { kNoise = 0, kRollout = 1, kReduce = 2, kUpdate = 3, kStats = 4, kNumKernels = 5 };
-const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats"};
+enum KernelId { kNoise = 0, kRollout = 1, kReduce = 2, kUpdate = 3, kStats = 4, kLambda = 5, kNumKernels = 6 };
+const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda"};
 
 struct PendingEvt {
   int id;
@@ -128,6 +129,16 @@ struct mppi_handle {
   int hist_slots = 0;
   int law_n = 0;             // history rows of the last adapting solve / graph launch (0: none ran)
   bool graph_adapt = false;  // the captured graph adapts
+  // ESS targeting (mppi_set_ess_target; ess_target.h, kernels_lambda.hip).  While ess_on, every solve runs
+  // lambda_search_kernel between its rollout and its reduce; the reduce and the statistics read the solve's lambda from
+  // d_lambda [lambda_slots + 1][max_batch], slot-major like the statistics (a graph's solve i writes slot i; the last
+  // slot is mppi_lambda_eval's), allocated by ensure_lambda before the first such solve or capture.
+  bool ess_on = false;
+  EssTarget ess{0.0f, 1e-3f, 1e3f};
+  float* d_lambda = nullptr;
+  int lambda_slots = 0;
+  int lam_B = 0, lam_n = 0;  // batch and slot count of the last targeting solve / graph launch (0: none ran)
+  bool graph_ess = false;    // the captured graph targets
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -251,7 +262,8 @@ void mppi_destroy(mppi_handle* h) {
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
-                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist};
+                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist,
+                  h->d_lambda};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -637,6 +649,27 @@ static int ensure_stats(mppi_handle* h, int slots) {
   return MPPI_OK;
 }
 
+// The per-solve lambdas of ESS targeting for `slots` solve slots (+ 1 for mppi_lambda_eval).  Growing them waits for the
+// stream and forgets the values held so far.  Never called inside a capture.
+static int ensure_lambda(mppi_handle* h, int slots) {
+  if (slots <= h->lambda_slots) return MPPI_OK;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->d_lambda) (void)hipFree(h->d_lambda);
+  h->d_lambda = nullptr;
+  h->lambda_slots = 0;
+  h->lam_B = h->lam_n = 0;
+  const size_t n = (size_t)(slots + 1) * h->cfg.max_batch * 4;
+  HIP_TRY(hipMalloc(&h->d_lambda, n));
+  HIP_TRY(hipMemsetAsync(h->d_lambda, 0, n, h->stream));  // in stream order, ahead of the kernels that write slots
+  h->lambda_slots = slots;
+  return MPPI_OK;
+}
+
+// slot `slot` of the targeting handle's lambdas (nullptr while targeting is off: the by-value lambda)
+static float* lambda_slot(const mppi_handle* h, int slot) {
+  return h->ess_on ? h->d_lambda + (size_t)slot * h->cfg.max_batch : nullptr;
+}
+
 // the generators' law argument: the device law of an adapting handle, else nullptr (the by-value model)
 static const float* gen_law(const mppi_handle* h) { return h->adapt_on ? h->d_law : nullptr; }
 
@@ -649,11 +682,13 @@ static hipError_t enqueue_adapt(mppi_handle* h, int B, int slot) {
 }
 
 // The diagnostics of B solves from costs [B][Kp] and noise [B][nu][H][Kp] (or nullptr) into output slot `slot`.
-static hipError_t enqueue_stats(mppi_handle* h, int B, const float* costs, const float* noise, int slot) {
+// lambda_dev: the solves' own lambdas (ESS targeting), or nullptr: cfg.lambda.
+static hipError_t enqueue_stats(mppi_handle* h, int B, const float* costs, const float* noise, int slot,
+                                const float* lambda_dev = nullptr) {
   const mppi_config& c = h->cfg;
   const size_t off = (size_t)slot * c.max_batch;
   const StatsArgs sa{B, c.nu, c.H, c.K, h->Kp, c.lambda, c.norm_eps, costs, noise, h->d_stats_w, h->d_stats_part,
-                     h->d_stats + off, h->d_stats_m2 + off * c.nu, h->d_stats_m11 + off * c.nu};
+                     h->d_stats + off, h->d_stats_m2 + off * c.nu, h->d_stats_m11 + off * c.nu, lambda_dev};
   return launch_stats(sa, h->stream);
 }
 
@@ -748,8 +783,13 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   a.seed_ctr = (flags & MPPI_FLAG_SEED_COUNTER) ? h->d_seed_ctr : nullptr;
   a.seed_bump = ns ? nullptr : a.seed_ctr;  // graph mode: reduce_kernel<GEN> advances the counter instead
   a.xout = nullptr;
-  // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths)
-  a.kclock = (h->kclock && a.seed_ctr) ? h->d_kclock : nullptr;
+  // ESS targeting: the solve's slot of lambdas, written by the search between the rollout and the reduce (below)
+  float* const lam = lambda_slot(h, stats_slot);
+  a.lambda_dev = lam;
+  const bool cart_unfused = lam && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths); the cartpole's unfused
+  // rollout carries no stamp
+  a.kclock = (h->kclock && a.seed_ctr && !cart_unfused) ? h->d_kclock : nullptr;
   a.kclock_ctr = h->d_kclock ? h->d_kclock + 2 * (size_t)kClockSlots : nullptr;
   a.kclock_ticket = h->d_kclock ? reinterpret_cast<unsigned*>(h->d_kclock + 2 * (size_t)kClockSlots + 1) : nullptr;
   if (a.kclock && !h->capturing) h->kclock_launches += 1;  // graph replays count graph_n each (mppi_graph_launch)
@@ -810,20 +850,24 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // reduce order) cannot give: the next noise then comes from its own launch behind the reduce (below)
   const bool gen_after = ns && ns->next && h->noise_model.active;
   const NoiseGen* pg = ns && ns->next && !gen_after ? &gen : nullptr;
-  if (h->dyn_kind == MPPI_DYN_CARTPOLE) {  // one launch: the rollout blocks finish the solve (fused epilogue)
+  if (h->dyn_kind == MPPI_DYN_CARTPOLE && !lam) {  // one launch: the rollout blocks finish the solve (fused epilogue)
     a.part = h->d_part;
     HIP_TRY(timed(h, kRollout, [&] { return launch_cartpole_rollout(a, h->cart, pg, s); }));
     h->rollout_kernel = g_rollout_kernel;
   } else {
+    // (a targeting cartpole too: its fused epilogue forms the softmin partials with lambda before all costs exist, so
+    // it runs the unfused rollout of the env step, a.part == nullptr, then the search and reduce_kernel: 3 launches)
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
     h->rollout_kernel = g_rollout_kernel;
+    if (lam)
+      HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(a.costs, B, K, Kp, h->ess, c.lambda, lam, s); }));
     HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(a, pg, s); }));
   }
   // diagnostics (MPPI_FLAG_STATS): read-only on this solve's costs and noise, behind the reduce (or the cartpole's fused
   // epilogue) and ahead of everything that may write a.noise -- the next solve's generators, on this stream or ordered
   // behind it (ev_red), only ever write the OTHER buffer of the pair before this point
   if (flags & MPPI_FLAG_STATS)
-    HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, a.costs, a.noise, stats_slot); }));
+    HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, a.costs, a.noise, stats_slot, lam); }));
   // the adapted law (mppi_set_noise_adapt; every such solve carries the flag): one wave directly behind the statistics
   // and ahead of the launch below that draws the next solve's noise, so chained and captured streams draw solve i + 1
   // from the law adapted on solve i, as a loop of plain solves does
@@ -960,6 +1004,10 @@ static void note_stats(mppi_handle* h, int B, int flags) {
     h->stats_n = 1;
   }
   if (h->adapt_on) h->law_n = 1;
+  if (h->ess_on) {
+    h->lam_B = B;
+    h->lam_n = 1;
+  }
 }
 
 // MPPI_FLAG_CHAIN: one solve of a graph stream, launched on the stream (rollout -> reduce_kernel<GEN>, or with
@@ -1184,6 +1232,7 @@ int mppi_solve_ex(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int f
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;
   if (h->adapt_on) flags |= MPPI_FLAG_STATS;  // the adaptation reads the solve's moments
   if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, 1)) != MPPI_OK) return rc;
+  if (h->ess_on && (rc = ensure_lambda(h, 1)) != MPPI_OK) return rc;
   if (flags & MPPI_FLAG_CHAIN) return chain_solve(h, B, io, seed, flags);
   HIP_TRY(drop_prefetch(h));  // a plain solve generates its own noise into d_noise
   rc = enqueue_solve(h, B, io, seed, flags);
@@ -1222,6 +1271,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   if (const int e = ensure_stream_buffers(h); e != MPPI_OK) return e;
   // the statistics' slots exist before the capture begins: solve i's launches carry slot i's pointers
   if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, n_solves)) != MPPI_OK) return rc;
+  if (h->ess_on && (rc = ensure_lambda(h, n_solves)) != MPPI_OK) return rc;  // ... and the lambdas' slots
   float* buf[2] = {h->d_noise, h->d_noise2};
   const bool prof = h->prof;
   h->prof = false;  // no event nodes inside the graph
@@ -1258,6 +1308,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->graph_kclock = h->kclock;
   h->graph_stats = (flags & MPPI_FLAG_STATS) != 0;
   h->graph_adapt = h->adapt_on;
+  h->graph_ess = h->ess_on;
   h->graph_B = B;
   h->graph_n = n_solves;
   h->graph_seed = seed;
@@ -1282,6 +1333,10 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
     h->stats_n = h->graph_n;
   }
   if (h->graph_adapt) h->law_n = h->graph_n;
+  if (h->graph_ess) {
+    h->lam_B = h->graph_B;
+    h->lam_n = h->graph_n;
+  }
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1448,6 +1503,69 @@ int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active
     for (int u = 0; u < h->cfg.nu; ++u) sigma_u[u] = m.active ? m.sigma_u[u] : h->cfg.sigma;
   if (rho) *rho = m.rho;
   if (active) *active = m.active;
+  return MPPI_OK;
+}
+
+int mppi_set_ess_target(mppi_handle* h, float ess_frac, float lambda_min, float lambda_max) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_ess_target: null handle");
+  if (!(ess_frac >= 0.0f && ess_frac <= 1.0f)) return fail(MPPI_E_ARG, "mppi_set_ess_target: ess_frac must be in [0, 1]");
+  if (!(lambda_min > 0.0f && lambda_min <= lambda_max && std::isfinite(lambda_max)))
+    return fail(MPPI_E_ARG, "mppi_set_ess_target: need 0 < lambda_min <= lambda_max < inf");
+  const bool on = ess_frac > 0.0f;
+  const EssTarget t{ess_frac, lambda_min, lambda_max};
+  if (!on && !h->ess_on) {  // nothing to disable: only the limits are kept
+    h->ess = t;
+    return MPPI_OK;
+  }
+  if (on && h->ess_on && std::memcmp(&t, &h->ess, sizeof(t)) == 0) return MPPI_OK;  // no change
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state: the captured graphs hold the settings (or their absence) in their launches; a launch still in flight
+  // finishes first.  A prefetched noise is kept: lambda does not enter the noise, the key sequence is unchanged
+  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
+  for (hipGraphExec_t& g : h->graph_exec)
+    if (g) {
+      HIP_TRY(hipGraphExecDestroy(g));
+      g = nullptr;
+    }
+  h->ess = t;
+  h->ess_on = on;
+  return MPPI_OK;
+}
+
+int mppi_get_ess_target(mppi_handle* h, float* ess_frac, float* lambda_min, float* lambda_max) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_ess_target: null handle");
+  if (ess_frac) *ess_frac = h->ess_on ? h->ess.ess_frac : 0.0f;
+  if (lambda_min) *lambda_min = h->ess.lambda_min;
+  if (lambda_max) *lambda_max = h->ess.lambda_max;
+  return MPPI_OK;
+}
+
+int mppi_get_lambda(mppi_handle* h, int B, int step, float* lambda) {
+  if (!h || !lambda) return fail(MPPI_E_ARG, "mppi_get_lambda: null argument");
+  if (h->lam_n == 0) return fail(MPPI_E_STATE, "mppi_get_lambda: no solve with ESS targeting has run on the handle");
+  if (B < 1 || B > h->lam_B) return fail(MPPI_E_ARG, "mppi_get_lambda: B beyond the batch of the last targeting solve");
+  if (step < 0 || step >= h->lam_n)
+    return fail(MPPI_E_ARG, "mppi_get_lambda: step beyond the solves of the last targeting solve or graph");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(lambda, h->d_lambda + (size_t)step * h->cfg.max_batch, (size_t)B * 4, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_lambda_eval(mppi_handle* h, int B, const float* costs, float* lambda) {
+  if (!h || !costs || !lambda) return fail(MPPI_E_ARG, "mppi_lambda_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_lambda_eval: B out of range [1, max_batch]");
+  if (!h->ess_on) return fail(MPPI_E_STATE, "mppi_lambda_eval: call mppi_set_ess_target first");
+  HIP_TRY(hipSetDevice(h->device));
+  if (const int rc = ensure_lambda(h, 1); rc != MPPI_OK) return rc;
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp;
+  HIP_TRY(hipMemcpy2DAsync(h->d_costs, Kp * 4, costs, K * 4, K * 4, B, hipMemcpyHostToDevice, s));
+  float* out = h->d_lambda + (size_t)h->lambda_slots * c.max_batch;  // the evaluation's own slot
+  HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(h->d_costs, B, c.K, h->Kp, h->ess, c.lambda, out, s); }));
+  HIP_TRY(hipMemcpyAsync(lambda, out, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return MPPI_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "../../include/mppi.h"
 
 struct NoiseAdapt;  // noise_adapt.h: the settings of mppi_set_noise_adapt
+struct EssTarget;   // ess_target.h: the settings of mppi_set_ess_target
 
 namespace mppi {
 
@@ -44,6 +45,9 @@ struct SolveArgs {
   unsigned long long* kclock;
   unsigned long long* kclock_ctr;  // stamped launches since the reset (advanced by the launch's last block)
   unsigned* kclock_ticket;         // block arrivals of the current stamped launch (zero between launches)
+  // ESS targeting (mppi_set_ess_target): [B] the solve's own lambda, written by lambda_search_kernel ahead of the
+  // reduce; nullptr (every handle that never enables it): `lambda` above.  Last, so no other field moves.
+  const float* lambda_dev;
 };
 
 // Rollout launch clock (mppi_kernel_clock): every block's leader folds its start / end stamps (s_memrealtime,
@@ -326,9 +330,14 @@ struct StatsArgs {
   mppi_solve_stats* stats;  // [B] out
   float* m2;                // [B][nu] out
   float* m11;               // [B][nu] out
+  const float* lambda_dev;  // [B] the solve's own lambda (ESS targeting), or nullptr: `lambda`
 };
 size_t stats_part_floats(int B, int nu, int H, int Kp);
 hipError_t launch_stats(const StatsArgs& a, hipStream_t stream);  // cost part, moment part, fixed-order finish
+// kernels_lambda.hip: per solve b, lambda_out[b] = the lambda in [lambda_min, lambda_max] at which costs [B][Kp] give
+// the target effective sample size (the rule: ess_target.h); one block per solve, read-only on the costs, capturable
+hipError_t launch_lambda_search(const float* costs, int B, int K, int Kp, const EssTarget& s, float cfg_lambda,
+                                float* lambda_out, hipStream_t stream);
 hipError_t launch_record(const float* x, const float* u, float* rx, float* ru, int nxB, int nuB, hipStream_t stream);
 
 }  // namespace mppi

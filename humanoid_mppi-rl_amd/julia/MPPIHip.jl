@@ -261,6 +261,58 @@ function noise_law(c::Controller; step::Integer = 0)
 end
 
 """
+    set_ess_target!(c, ess_frac; lambda_min = 1e-3, lambda_max = 1e3)
+
+Choose the softmin temperature on the device, per solve, so that the solve's own costs give the effective sample size
+max(1, ess_frac * n_finite), within [lambda_min, lambda_max] (mppi_set_ess_target): `ess_frac` in (0, 1] enables, 0
+disables and the configured lambda runs again.
+"""
+function set_ess_target!(c::Controller, ess_frac::Real; lambda_min::Real = 1e-3, lambda_max::Real = 1e3)
+    check(ccall((:mppi_set_ess_target, LIB), Cint, (Ptr{Cvoid}, Cfloat, Cfloat, Cfloat), c.handle, ess_frac,
+                lambda_min, lambda_max))
+    return c
+end
+
+"""
+    ess_target(c) -> (ess_frac, lambda_min, lambda_max)
+
+The settings of `set_ess_target!` (mppi_get_ess_target); `ess_frac` is 0 while targeting is off.
+"""
+function ess_target(c::Controller)
+    v = [Ref{Cfloat}(0) for _ in 1:3]
+    check(ccall((:mppi_get_ess_target, LIB), Cint, (Ptr{Cvoid}, Ref{Cfloat}, Ref{Cfloat}, Ref{Cfloat}), c.handle,
+                v[1], v[2], v[3]))
+    return (v[1][], v[2][], v[3][])
+end
+
+"""
+    solve_lambda(c; step = 0) -> Float32
+
+The lambda the targeting solve `step` updated with (mppi_get_lambda; waits for the stream).
+"""
+function solve_lambda(c::Controller; step::Integer = 0)
+    lam = zeros(Float32, 1)
+    GC.@preserve lam check(ccall((:mppi_get_lambda, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float32}), c.handle, 1,
+                                 step, pointer(lam)))
+    return lam[1]
+end
+
+"""
+    lambda_eval(c, costs) -> Float32
+
+The search kernel on a given cost vector (length K; non-finite entries allowed) (mppi_lambda_eval); needs targeting
+enabled.
+"""
+function lambda_eval(c::Controller, costs)
+    cs = Float32.(vec(collect(costs)))
+    length(cs) == c.cfg.K || throw(ArgumentError("costs must have K = $(c.cfg.K) entries"))
+    lam = zeros(Float32, 1)
+    GC.@preserve cs lam check(ccall((:mppi_lambda_eval, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}),
+                                    c.handle, 1, pointer(cs), pointer(lam)))
+    return lam[1]
+end
+
+"""
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 
 The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and

@@ -63,15 +63,28 @@ class MPPIModel:
               same rule in fp32 in a kernel behind each solve's statistics; no statistics are requested and no law is
               set per step, chained solves and graph streams on the engine adapt step by step and stay captured, and
               noise_sigma / noise_rho read the engine's live law.
+    ess_target: above 0, the engine chooses the softmin temperature per solve so that the solve's own costs give the
+              effective sample size max(1, ess_target * n_finite), within lambda_limits = (lambda_min, lambda_max)
+              (Engine.set_ess_target); 0 (default) keeps the preset's lambda.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
                  noise: str = "device", seed: int = 0, precision: int = L.PREC_BF16, ctx=None,
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
-                 adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", **overrides):
+                 adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
+                 lambda_limits=(1e-3, 1e3), **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
+        self.ess_target = float(ess_target)
+        if not 0.0 <= self.ess_target <= 1.0:  # (NaN included)
+            raise ValueError("MPPIModel: ess_target must be in [0, 1]")
+        try:
+            self.lambda_limits = tuple(float(v) for v in lambda_limits)
+        except TypeError:
+            raise ValueError("MPPIModel: lambda_limits must be (lambda_min, lambda_max)") from None
+        if len(self.lambda_limits) != 2 or not (0.0 < self.lambda_limits[0] <= self.lambda_limits[1] < np.inf):
+            raise ValueError("MPPIModel: lambda_limits needs 0 < lambda_min <= lambda_max < inf")
         self.preset = preset
         self.body_ids = dict(HUMANOID_BODY_IDS if body_ids is None else body_ids)
         self.u0_before = bool(u0_before)
@@ -111,6 +124,8 @@ class MPPIModel:
             self.engine.set_noise_model(self._noise_sigma, self._noise_rho)
         if self.device_adapt:
             self.engine.set_noise_adapt(self.adapt_noise, *self.adapt_limits)
+        if self.ess_target > 0.0:
+            self.engine.set_ess_target(self.ess_target, *self.lambda_limits)
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0

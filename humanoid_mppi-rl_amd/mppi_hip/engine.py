@@ -155,6 +155,38 @@ class Engine:
         L.check(self.lib.mppi_get_noise_law(self._h, step, s.ctypes.data_as(L._fp), ctypes.byref(rho)))
         return s, float(rho.value)
 
+    # -- ESS targeting (mppi_set_ess_target; mppi_hip.stats.ess_lambda_ref states the rule)
+    def set_ess_target(self, ess_frac: float, lambda_min: float = 1e-3, lambda_max: float = 1e3):
+        """Choose the softmin temperature on the device, per solve, so that the solve's own costs give the effective
+        sample size max(1, ess_frac * n_finite), within [lambda_min, lambda_max] (mppi_set_ess_target): ess_frac in
+        (0, 1] enables, 0 disables and config.lambda_ runs again.  Works in every stream form with no host round trip;
+        the analytic cartpole then takes three launches per solve instead of one.  Any change destroys captured graphs;
+        a prefetched noise is kept."""
+        L.check(self.lib.mppi_set_ess_target(self._h, ctypes.c_float(ess_frac), ctypes.c_float(lambda_min),
+                                             ctypes.c_float(lambda_max)))
+        return self
+
+    def ess_target(self) -> tuple[float, float, float]:
+        """(ess_frac, lambda_min, lambda_max) of mppi_get_ess_target; ess_frac 0.0 while targeting is off."""
+        v = [ctypes.c_float() for _ in range(3)]
+        L.check(self.lib.mppi_get_ess_target(self._h, *(ctypes.byref(x) for x in v)))
+        return tuple(float(x.value) for x in v)
+
+    def lambdas(self, B: int = 1, step: int = 0) -> np.ndarray:
+        """lambda [B] the targeting solve `step` updated with (mppi_get_lambda; waits for the stream): step 0 after a
+        plain or chained solve, 0..n_solves-1 after graph_launch."""
+        out = np.empty(B, np.float32)
+        L.check(self.lib.mppi_get_lambda(self._h, B, step, _ptr(out)))
+        return out
+
+    def lambda_eval(self, costs) -> np.ndarray:
+        """The search kernel on host costs [B, K] (or [K]; non-finite entries allowed) -> lambda [B] (mppi_lambda_eval).
+        Needs targeting enabled; no dynamics or cost need be loaded."""
+        costs = _f32(costs).reshape(-1, self.config.K)
+        out = np.empty(costs.shape[0], np.float32)
+        L.check(self.lib.mppi_lambda_eval(self._h, costs.shape[0], _ptr(costs), _ptr(out)))
+        return out
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,

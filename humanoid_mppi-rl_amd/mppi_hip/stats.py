@@ -15,6 +15,18 @@ S = sum wt and w_k = wt_k / (S + norm_eps) -- the weights of the update itself:
 The device computes these in fp32 (fp64 for the cost sums); solve_stats_ref is the float64 restatement: the reference
 of the tests, and for users.  adapt_noise_model turns the moments into the next sampling law; adapt_noise_model_f32 is
 the same step as the device takes it (mppi_set_noise_adapt), float32 operation by operation.
+
+ESS targeting (mppi_set_ess_target; csrc/ess_target.h is the fp32 rule): per solve the device chooses lambda_b in
+[lambda_min, lambda_max] so that the solve's own costs give a requested effective sample size.  With F, beta and wt as
+above, n = |F|, ESS(lambda) = (sum wt)^2 / sum wt^2 and the target T = max(1, ess_frac * n):
+
+    n == 0:                 lambda_b = the configured lambda (the solve reports MPPI_E_NONFINITE)
+    ESS(lambda_min) >= T:   lambda_b = lambda_min    (ties at the minimum, n == 1, all costs equal)
+    ESS(lambda_max) <  T:   lambda_b = lambda_max
+    otherwise               the root of ESS(lambda) = T; the device returns the upper end hi of an fp32 bracket
+                            ESS(lo) < T <= ESS(hi) with hi / lo <= 1 + 2e-6
+
+ess_ref and ess_lambda_ref are the float64 restatement (the true root by bisection to convergence).
 """
 from __future__ import annotations
 
@@ -193,3 +205,59 @@ def adapt_noise_model_f32(sigma_u, rho, eps_m2, eps_m11, rate, sigma_min=1e-3, s
             rho_hat = rho_max if rho_hat > rho_max else rho_hat
         r = _fma32(rate, rho_hat, f(keep * rho))
     return s, (r if np.isfinite(r) else rho)
+
+
+def ess_ref(costs, lam) -> float:
+    """ESS(lam) of one solve's costs [K] in float64: non-finite costs carry weight 0; 0.0 when no cost is finite."""
+    c = np.asarray(costs, np.float64).ravel()
+    cf = c[np.isfinite(c)]
+    if cf.size == 0:
+        return 0.0
+    with np.errstate(under="ignore"):
+        wt = np.exp(-(cf - cf.min()) / float(lam))
+    S = wt.sum()
+    return float(S * S / np.sum(wt * wt))
+
+
+def ess_target_ref(costs, ess_frac: float) -> float:
+    """The target T = max(1, ess_frac * n_finite) of one solve's costs [K]."""
+    n = int(np.isfinite(np.asarray(costs, np.float64)).sum())
+    return max(1.0, float(ess_frac) * n)
+
+
+def ess_lambda_ref(costs, ess_frac: float, lambda_min: float, lambda_max: float, lam_default: float = 1.0):
+    """The lambda of ESS targeting in float64 (the rule of csrc/ess_target.h with the true root): costs [B, K] -> [B]
+    (or [K] -> a float).  ESS(lambda_min) >= T gives lambda_min, ESS(lambda_max) < T gives lambda_max, otherwise the
+    root of ESS(lambda) = T by bisection in log lambda until the bracket stops shrinking; a row without a finite cost
+    gives lam_default (the handle's configured lambda).  ValueError on ess_frac outside (0, 1] or bounds that are not
+    0 < lambda_min <= lambda_max < inf."""
+    ess_frac, lo0, hi0 = float(ess_frac), float(lambda_min), float(lambda_max)
+    if not 0.0 < ess_frac <= 1.0:
+        raise ValueError("ess_lambda_ref: ess_frac must be in (0, 1]")
+    if not 0.0 < lo0 <= hi0 < np.inf:
+        raise ValueError("ess_lambda_ref: need 0 < lambda_min <= lambda_max < inf")
+    c = np.asarray(costs, np.float64)
+    single = c.ndim == 1
+    c = c.reshape(-1, c.shape[-1])
+    out = np.empty(c.shape[0])
+    for b, row in enumerate(c):
+        if not np.isfinite(row).any():
+            out[b] = lam_default
+            continue
+        T = ess_target_ref(row, ess_frac)
+        if ess_ref(row, lo0) >= T:
+            out[b] = lo0
+        elif ess_ref(row, hi0) < T:
+            out[b] = hi0
+        else:
+            lo, hi = np.log(lo0), np.log(hi0)
+            while True:
+                mid = 0.5 * (lo + hi)
+                if not lo < mid < hi:
+                    break
+                if ess_ref(row, np.exp(mid)) >= T:
+                    hi = mid
+                else:
+                    lo = mid
+            out[b] = np.exp(hi)
+    return float(out[0]) if single else out

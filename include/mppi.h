@@ -69,7 +69,11 @@ extern "C" {
  *      mppi_kernel_time.  A solve without the flag launches exactly the kernels it launched before.
  *      Additive, version unchanged: mppi_set_noise_adapt / mppi_get_noise_adapt / mppi_get_noise_law (the sampling
  *      law adapted on the device behind each solve's statistics).  A handle that never enables it launches exactly
- *      the kernels it launched before, with the same arguments. */
+ *      the kernels it launched before, with the same arguments.
+ *      Additive, version unchanged: mppi_set_ess_target / mppi_get_ess_target / mppi_get_lambda / mppi_lambda_eval
+ *      (the softmin temperature chosen on the device, per solve, to hold a requested effective sample size); kernel
+ *      name "lambda" in mppi_kernel_time.  A handle that never enables it launches exactly the kernels it launched
+ *      before, with the same grids. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -301,6 +305,42 @@ int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigm
 int mppi_get_noise_adapt(mppi_handle* h, float* rate, float* sigma_min, float* sigma_max, float* rho_max);
 int mppi_get_noise_law(mppi_handle* h, int step, float* sigma_u, float* rho);
 
+/* ESS targeting: the softmin temperature chosen ON THE DEVICE, per solve, so that the solve's own costs give a requested
+ * effective sample size -- lambda made scale-free, with no host round trip: plain solves (host or device pointers),
+ * MPPI_FLAG_ASYNC, chained solves, captured graph streams and trajectory logging all choose it step by step and give
+ * bit for bit what a loop of plain solves gives.
+ * With targeting on, every solve runs one more kernel between its rollout and its reduce (one block per solve;
+ * csrc/kernels_lambda.hip).  For solve b with costs c[0..K), F = {k : isfinite(c_k)}, n = |F|, beta = min_F c and
+ *     wt_k(lambda) = exp(-(c_k - beta) / lambda) on F, 0 elsewhere        (the update's own weights)
+ *     ESS(lambda)  = (sum wt)^2 / sum wt^2,      T = max(1, ess_frac * n)
+ * it writes lambda_b in [lambda_min, lambda_max] (the fp32 rule is csrc/ess_target.h; mppi_hip.stats.ess_lambda_ref is
+ * its float64 restatement):
+ *     ESS(lambda_min) >= T: lambda_min (ties at the minimum, n == 1, all costs equal);  ESS(lambda_max) < T: lambda_max;
+ *     otherwise the upper end of a bracket ESS(lo) < T <= ESS(hi) with hi / lo <= 1 + 2e-6;
+ *     n == 0: cfg.lambda (the solve returns MPPI_E_NONFINITE as before).
+ * The reduce, the `weights` output, U, u0 and the statistics of MPPI_FLAG_STATS (ess, entropy, free_energy, the
+ * weighted moments) all describe the update made with lambda_b; the costs are those of the same solve without
+ * targeting.  lambda_b depends on nothing but that solve's costs and the settings: a saved stream resumes with
+ * nothing new to restore.  The analytic cartpole leaves its fused one-launch form while targeting is on (its epilogue
+ * needs lambda before all costs exist) and takes three launches per solve: rollout, search, reduce; its rollouts are
+ * then not stamped by mppi_kernel_clock.  mppi_stats_eval keeps using cfg.lambda.  Env MPPI_LAMBDA_SEARCH=bisect (read
+ * per launch; an A/B arm) searches with one candidate per pass instead of 15.
+ * mppi_set_ess_target: ess_frac in (0, 1] enables, ess_frac == 0 disables and the by-value lambda runs again;
+ * 0 < lambda_min <= lambda_max < inf; anything else (NaN included) is MPPI_E_ARG and changes nothing.  Any change of
+ * the settings, enabling and disabling included, destroys captured graphs (mppi_graph_launch returns MPPI_E_STATE until
+ * the next capture); a prefetched noise is kept, because lambda does not enter the noise: the key sequence is unchanged.
+ * mppi_get_ess_target: the settings (*ess_frac = 0 while off); each pointer may be NULL.
+ * mppi_get_lambda: lambda [B] of solve `step`; waits for the stream.  step as for mppi_get_stats: 0 after a plain or
+ * chained solve, 0..n_solves-1 after a graph launch (solve i writes slot i; the slots are allocated before the capture
+ * begins); MPPI_E_STATE if no targeting solve has run, MPPI_E_ARG for a step or B beyond that solve / graph.
+ * mppi_lambda_eval: the same kernel on host costs [B][K] -> lambda [B]: the entry that can be fed non-finite, tied or
+ * huge-K costs without a rollout.  Needs only mppi_create and targeting enabled (MPPI_E_STATE otherwise).  It goes
+ * through the handle's staging costs and its own output slot: the lambdas of the last solve stay readable. */
+int mppi_set_ess_target(mppi_handle* h, float ess_frac, float lambda_min, float lambda_max);
+int mppi_get_ess_target(mppi_handle* h, float* ess_frac, float* lambda_min, float* lambda_max);
+int mppi_get_lambda(mppi_handle* h, int B, int step, float* lambda /* [B] */);
+int mppi_lambda_eval(mppi_handle* h, int B, const float* costs /* [B][K] host */, float* lambda /* [B] */);
+
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
  *     eps_m2 [b][u] = 1/H     sum_{t=0..H-1} sum_k w_k eps[b][u][t][k]^2
@@ -351,7 +391,8 @@ int mppi_sync(mppi_handle* h);
 
 /* Per-kernel timing with hipEvents recorded on the handle's stream around each launch.
  * enable != 0 starts accumulating; mppi_kernel_times returns {count, total_ms} per kernel
- * name. names: "noise", "rollout", "reduce", "update", "stats" (the launches of MPPI_FLAG_STATS). */
+ * name. names: "noise", "rollout", "reduce", "update", "stats" (the launches of MPPI_FLAG_STATS), "lambda" (the
+ * search of mppi_set_ess_target). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
