@@ -42,8 +42,17 @@ static int fail(int code, const std::string& msg) {
 
 namespace {
 
-enum KernelId { kNoise = 0, kRollout = 1, kReduce = 2, kUpdate = 3, kStats = 4, kLambda = 5, kNumKernels = 6 };
-const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda"};
+enum KernelId {
+  kNoise = 0,
+  kRollout = 1,
+  kReduce = 2,
+  kUpdate = 3,
+  kStats = 4,
+  kLambda = 5,
+  kCtrl = 6,
+  kNumKernels = 7
+};
+const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost"};
 
 struct PendingEvt {
   int id;
@@ -139,6 +148,19 @@ struct mppi_handle {
   int lambda_slots = 0;
   int lam_B = 0, lam_n = 0;  // batch and slot count of the last targeting solve / graph launch (0: none ran)
   bool graph_ess = false;    // the captured graph targets
+  // the control-cost term (mppi_set_control_cost; control_cost.h, kernels_ctrl_cost.hip).  While ctrl_gamma > 0 every
+  // solve runs ctrl_lin_kernel + the term kernel between its rollout and everything that weighs its costs; the lambda
+  // search, the reduce and the statistics then read d_wcost = d_costs + term where they read d_costs otherwise.  All
+  // buffers are allocated by mppi_set_control_cost, two slots each where an evaluation must not disturb a solve's:
+  // slot 0 the last solve's (no per-step slots), slot 1 mppi_control_term_eval's.
+  float ctrl_gamma = 0.0f;        // 0: off
+  float* d_wcost = nullptr;       // [2][max_batch][Kp]
+  float* d_term = nullptr;        // [2][max_batch][Kp]
+  float* d_lin = nullptr;         // [2][max_batch][nu][H]
+  float* d_ctrl_part = nullptr;   // [ctrl_part_floats] the split form's partials (scratch)
+  float* d_ctrl_U = nullptr;      // [max_batch][nu][H] mppi_control_term_eval's U (the resident d_U stays as it is)
+  int ctrl_B = 0;                 // batch of the last solve / graph launch with the term (0: none ran)
+  bool graph_ctrl = false;        // the captured graph carries the term
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -263,7 +285,7 @@ void mppi_destroy(mppi_handle* h) {
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
                   h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist,
-                  h->d_lambda};
+                  h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -692,6 +714,36 @@ static hipError_t enqueue_stats(mppi_handle* h, int B, const float* costs, const
   return launch_stats(sa, h->stream);
 }
 
+// The control-cost launches of B solves into output slot `slot` (0: a solve, 1: mppi_control_term_eval): lin from U
+// and the law, the term from lin and the noise, wcost = costs + term.
+static hipError_t enqueue_ctrl(mppi_handle* h, int B, const float* U, const float* noise, const float* costs,
+                               int slot) {
+  const mppi_config& c = h->cfg;
+  const size_t ok = (size_t)slot * c.max_batch * h->Kp, ol = (size_t)slot * c.max_batch * c.nu * c.H;
+  CtrlArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.B = B;
+  ca.nu = c.nu;
+  ca.H = c.H;
+  ca.K = c.K;
+  ca.Kp = h->Kp;
+  ca.U = U;
+  ca.noise = noise;
+  ca.costs = costs;
+  ca.lin = h->d_lin + ol;
+  ca.term = h->d_term + ok;
+  ca.wcost = h->d_wcost + ok;
+  ca.part = h->d_ctrl_part;
+  ca.law.gamma = h->ctrl_gamma;
+  ca.law.sigma = c.sigma;
+  const NoiseModel& m = h->noise_model;
+  ca.law.rho = m.active ? m.rho : 0.0f;
+  ca.law.per_u = m.active;
+  if (m.active) std::memcpy(ca.law.sigma_u, m.sigma_u, sizeof(ca.law.sigma_u));
+  ca.d_law = gen_law(h);
+  return launch_ctrl_cost(ca, h->stream);
+}
+
 // Validate one solve request against the handle.
 static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if (!h || !io) return fail(MPPI_E_ARG, "mppi_solve: null argument");
@@ -786,7 +838,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // ESS targeting: the solve's slot of lambdas, written by the search between the rollout and the reduce (below)
   float* const lam = lambda_slot(h, stats_slot);
   a.lambda_dev = lam;
-  const bool cart_unfused = lam && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  const bool ctrl = h->ctrl_gamma > 0.0f;  // the control-cost term: the softmin weighs d_wcost = costs + term (below)
+  const bool cart_unfused = (lam || ctrl) && h->dyn_kind == MPPI_DYN_CARTPOLE;
   // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths); the cartpole's unfused
   // rollout carries no stamp
   a.kclock = (h->kclock && a.seed_ctr && !cart_unfused) ? h->d_kclock : nullptr;
@@ -850,24 +903,36 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // reduce order) cannot give: the next noise then comes from its own launch behind the reduce (below)
   const bool gen_after = ns && ns->next && h->noise_model.active;
   const NoiseGen* pg = ns && ns->next && !gen_after ? &gen : nullptr;
-  if (h->dyn_kind == MPPI_DYN_CARTPOLE && !lam) {  // one launch: the rollout blocks finish the solve (fused epilogue)
+  const float* wcost = a.costs;  // what the search, the reduce and the statistics weigh
+  if (h->dyn_kind == MPPI_DYN_CARTPOLE && !cart_unfused) {  // one launch: the rollout blocks finish the solve (fused)
     a.part = h->d_part;
     HIP_TRY(timed(h, kRollout, [&] { return launch_cartpole_rollout(a, h->cart, pg, s); }));
     h->rollout_kernel = g_rollout_kernel;
   } else {
     // (a targeting cartpole too: its fused epilogue forms the softmin partials with lambda before all costs exist, so
-    // it runs the unfused rollout of the env step, a.part == nullptr, then the search and reduce_kernel: 3 launches)
+    // it runs the unfused rollout of the env step, a.part == nullptr, then the search and reduce_kernel: 3 launches;
+    // and a cartpole with the control-cost term, whose epilogue would weigh costs the term has not reached yet)
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
     h->rollout_kernel = g_rollout_kernel;
+    SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
+    if (ctrl) {
+      // the control-cost term, behind the rollout (its costs exist) and ahead of the reduce (a.U is still the nominal the
+      // rollout perturbed).  An adapting handle's ctrl_lin_kernel reads d_law on the stream: at this point it still
+      // holds the law that drew THIS solve's noise -- the adapt kernel runs behind the reduce and the statistics
+      // (below), and the generators of the next solve's noise behind that
+      HIP_TRY(timed(h, kCtrl, [&] { return enqueue_ctrl(h, B, a.U, a.noise, a.costs, 0); }));
+      wcost = h->d_wcost;
+      r.costs = h->d_wcost;
+    }
     if (lam)
-      HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(a.costs, B, K, Kp, h->ess, c.lambda, lam, s); }));
-    HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(a, pg, s); }));
+      HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
+    HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s); }));
   }
   // diagnostics (MPPI_FLAG_STATS): read-only on this solve's costs and noise, behind the reduce (or the cartpole's fused
   // epilogue) and ahead of everything that may write a.noise -- the next solve's generators, on this stream or ordered
   // behind it (ev_red), only ever write the OTHER buffer of the pair before this point
   if (flags & MPPI_FLAG_STATS)
-    HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, a.costs, a.noise, stats_slot, lam); }));
+    HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, wcost, a.noise, stats_slot, lam); }));
   // the adapted law (mppi_set_noise_adapt; every such solve carries the flag): one wave directly behind the statistics
   // and ahead of the launch below that draws the next solve's noise, so chained and captured streams draw solve i + 1
   // from the law adapted on solve i, as a loop of plain solves does
@@ -1008,6 +1073,7 @@ static void note_stats(mppi_handle* h, int B, int flags) {
     h->lam_B = B;
     h->lam_n = 1;
   }
+  if (h->ctrl_gamma > 0.0f) h->ctrl_B = B;
 }
 
 // MPPI_FLAG_CHAIN: one solve of a graph stream, launched on the stream (rollout -> reduce_kernel<GEN>, or with
@@ -1309,6 +1375,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->graph_stats = (flags & MPPI_FLAG_STATS) != 0;
   h->graph_adapt = h->adapt_on;
   h->graph_ess = h->ess_on;
+  h->graph_ctrl = h->ctrl_gamma > 0.0f;
   h->graph_B = B;
   h->graph_n = n_solves;
   h->graph_seed = seed;
@@ -1337,6 +1404,7 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
     h->lam_B = h->graph_B;
     h->lam_n = h->graph_n;
   }
+  if (h->graph_ctrl) h->ctrl_B = h->graph_B;  // (no per-step slots: the chain's last solve)
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1567,6 +1635,92 @@ int mppi_lambda_eval(mppi_handle* h, int B, const float* costs, float* lambda) {
   HIP_TRY(hipMemcpyAsync(lambda, out, (size_t)B * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return MPPI_OK;
+}
+
+int mppi_set_control_cost(mppi_handle* h, float gamma) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_control_cost: null handle");
+  if (!(gamma >= 0.0f && std::isfinite(gamma)))
+    return fail(MPPI_E_ARG, "mppi_set_control_cost: gamma must be finite and >= 0");
+  if (gamma == h->ctrl_gamma) return MPPI_OK;  // no change: captured graphs stay
+  HIP_TRY(hipSetDevice(h->device));
+  const mppi_config& c = h->cfg;
+  if (gamma > 0.0f && !h->d_wcost) {  // all of the term's buffers, once, or none (every entry is written before it is read)
+    const size_t nk = (size_t)2 * c.max_batch * h->Kp * 4, nl = (size_t)c.max_batch * c.nu * c.H * 4;
+    const size_t np = ctrl_part_floats(c.max_batch, c.nu, c.H, h->Kp) * 4;
+    float *w = nullptr, *t = nullptr, *l = nullptr, *p = nullptr, *u = nullptr;
+    hipError_t e = hipMalloc(&w, nk);
+    if (e == hipSuccess) e = hipMalloc(&t, nk);
+    if (e == hipSuccess) e = hipMalloc(&l, 2 * nl);
+    if (e == hipSuccess) e = hipMalloc(&p, np < 16 ? 16 : np);
+    if (e == hipSuccess) e = hipMalloc(&u, nl);
+    if (e != hipSuccess) {
+      for (float* x : {w, t, l, p, u})
+        if (x) (void)hipFree(x);
+      return fail(MPPI_E_HIP, std::string("mppi_set_control_cost: ") + hipGetErrorString(e));
+    }
+    h->d_wcost = w;
+    h->d_term = t;
+    h->d_lin = l;
+    h->d_ctrl_part = p;
+    h->d_ctrl_U = u;
+  }
+  // stale state: the captured graphs hold gamma (or the term's absence) in their launches; a launch still in flight
+  // finishes first.  A prefetched noise is kept: gamma does not enter the noise, the key sequence is unchanged
+  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
+  for (hipGraphExec_t& g : h->graph_exec)
+    if (g) {
+      HIP_TRY(hipGraphExecDestroy(g));
+      g = nullptr;
+    }
+  h->ctrl_gamma = gamma;
+  return MPPI_OK;
+}
+
+int mppi_get_control_cost(mppi_handle* h, float* gamma) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_control_cost: null handle");
+  if (gamma) *gamma = h->ctrl_gamma;
+  return MPPI_OK;
+}
+
+// slot `slot` of the term's outputs -> host (the stream is idle)
+static int copy_ctrl(mppi_handle* h, int B, int slot, float* term, float* lin) {
+  const mppi_config& c = h->cfg;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)c.nu * c.H;
+  if (term)
+    HIP_TRY(hipMemcpy2D(term, K * 4, h->d_term + (size_t)slot * c.max_batch * Kp, Kp * 4, K * 4, B,
+                        hipMemcpyDeviceToHost));
+  if (lin)
+    HIP_TRY(hipMemcpy(lin, h->d_lin + (size_t)slot * c.max_batch * rows, (size_t)B * rows * 4, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_get_control_term(mppi_handle* h, int B, float* term, float* lin) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_control_term: null handle");
+  if (h->ctrl_B == 0)
+    return fail(MPPI_E_STATE, "mppi_get_control_term: no solve with the control-cost term has run on the handle");
+  if (B < 1 || B > h->ctrl_B)
+    return fail(MPPI_E_ARG, "mppi_get_control_term: B beyond the batch of the last solve with the term");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_ctrl(h, B, 0, term, lin);
+}
+
+int mppi_control_term_eval(mppi_handle* h, int B, const float* U, const float* noise, float* term, float* lin) {
+  if (!h || !U || !noise) return fail(MPPI_E_ARG, "mppi_control_term_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_control_term_eval: B out of range [1, max_batch]");
+  if (!(h->ctrl_gamma > 0.0f)) return fail(MPPI_E_STATE, "mppi_control_term_eval: call mppi_set_control_cost first");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  HIP_TRY(hipMemcpyAsync(h->d_ctrl_U, U, rows * 4, hipMemcpyHostToDevice, s));
+  if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, s));
+  HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, noise, K * 4, K * 4, rows, hipMemcpyHostToDevice, s));
+  // (the evaluation's own slot; its wcost adds the term to whatever the staging costs hold and is never read)
+  HIP_TRY(timed(h, kCtrl, [&] { return enqueue_ctrl(h, B, h->d_ctrl_U, h->d_noise, h->d_costs, 1); }));
+  HIP_TRY(hipStreamSynchronize(s));
+  return copy_ctrl(h, B, 1, term, lin);
 }
 
 // slot `slot` of the diagnostics' buffers -> host (the stream is idle)

@@ -338,6 +338,27 @@ hipError_t launch_stats(const StatsArgs& a, hipStream_t stream);  // cost part, 
 // the target effective sample size (the rule: ess_target.h); one block per solve, read-only on the costs, capturable
 hipError_t launch_lambda_search(const float* costs, int B, int K, int Kp, const EssTarget& s, float cfg_lambda,
                                 float* lambda_out, hipStream_t stream);
+// kernels_ctrl_cost.hip: the control-cost term (mppi_set_control_cost; the rule for lin: control_cost.h), by value
+// like SolveArgs: read-only on the solve's U, noise and costs, so the launches can sit in a captured graph.
+struct CtrlLaw {
+  float gamma, sigma, rho;  // sigma: every actuator's (per_u == 0: the default law, cfg.sigma with rho 0)
+  int per_u;                // sigma_u below is the law's (an active noise model: nu <= kMaxNu)
+  float sigma_u[kMaxNu];
+};
+struct CtrlArgs {
+  int B, nu, H, K, Kp;
+  const float* U;       // [B][nu][H] the nominal the rollout perturbed
+  const float* noise;   // [B][nu][H][Kp] the raw eps
+  const float* costs;   // [B][Kp]
+  float* lin;           // [B][nu][H] out
+  float* term;          // [B][Kp] out (pads K..Kp: 0)
+  float* wcost;         // [B][Kp] out: costs + term (pads K..Kp: costs)
+  float* part;          // [ctrl_part_floats] scratch: the split form's per-cell partial sums
+  CtrlLaw law;
+  const float* d_law;   // the device law [kLawFloats] of an adapting handle, or nullptr: `law`
+};
+size_t ctrl_part_floats(int B, int nu, int H, int Kp);
+hipError_t launch_ctrl_cost(const CtrlArgs& a, hipStream_t stream);  // lin, then the term and wcost (one of two forms)
 hipError_t launch_record(const float* x, const float* u, float* rx, float* ru, int nxB, int nuB, hipStream_t stream);
 
 }  // namespace mppi

@@ -313,6 +313,64 @@ function lambda_eval(c::Controller, costs)
 end
 
 """
+    set_control_cost!(c, gamma)
+
+Add the control-cost term of information-theoretic MPPI, `gamma * sum U Sigma^-1 eps`, to the costs the softmin weighs
+(mppi_set_control_cost): a finite `gamma > 0` (cost units, absolute) enables, 0 disables.  Any change destroys captured
+graphs; a prefetched noise is kept.
+"""
+function set_control_cost!(c::Controller, gamma::Real)
+    check(ccall((:mppi_set_control_cost, LIB), Cint, (Ptr{Cvoid}, Cfloat), c.handle, gamma))
+    return c
+end
+
+"""
+    control_cost(c) -> Float32
+
+`gamma` of `set_control_cost!` (mppi_get_control_cost); 0 while the term is off.
+"""
+function control_cost(c::Controller)
+    g = Ref{Cfloat}(0)
+    check(ccall((:mppi_get_control_cost, LIB), Cint, (Ptr{Cvoid}, Ref{Cfloat}), c.handle, g))
+    return g[]
+end
+
+"""
+    control_term(c) -> (term::Vector{Float32}, lin::Matrix{Float32})
+
+The term (length K) and its coefficients `lin` (nu, H) of the last solve made with the term on
+(mppi_get_control_term; waits for the stream).
+"""
+function control_term(c::Controller)
+    term = zeros(Float32, c.cfg.K)
+    lin = zeros(Float32, c.cfg.H, c.cfg.nu)  # the library's [nu][H], row-major
+    GC.@preserve term lin check(ccall((:mppi_get_control_term, LIB), Cint,
+                                      (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}), c.handle, 1, pointer(term),
+                                      pointer(lin)))
+    return (term, permutedims(lin))
+end
+
+"""
+    control_term_eval(c, U, noise) -> (term::Vector{Float32}, lin::Matrix{Float32})
+
+The term's kernels on a given `U` (nu, H) and `noise` (nu, H, K) with the handle's current law and gamma
+(mppi_control_term_eval); needs the term enabled.
+"""
+function control_term_eval(c::Controller, U, noise)
+    nu, H, K = c.cfg.nu, c.cfg.H, c.cfg.K
+    size(U) == (nu, H) || throw(ArgumentError("U must be ($nu, $H)"))
+    size(noise) == (nu, H, K) || throw(ArgumentError("noise must be ($nu, $H, $K)"))
+    Ur = Float32.(permutedims(U))                  # (H, nu) column-major = the library's [nu][H]
+    nz = Float32.(permutedims(noise, (3, 2, 1)))   # (K, H, nu) column-major = the library's [nu][H][K]
+    term = zeros(Float32, K)
+    lin = zeros(Float32, H, nu)
+    GC.@preserve Ur nz term lin check(ccall((:mppi_control_term_eval, LIB), Cint,
+                                            (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                                            c.handle, 1, pointer(Ur), pointer(nz), pointer(term), pointer(lin)))
+    return (term, permutedims(lin))
+end
+
+"""
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 
 The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and

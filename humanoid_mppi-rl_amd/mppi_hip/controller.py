@@ -66,13 +66,16 @@ class MPPIModel:
     ess_target: above 0, the engine chooses the softmin temperature per solve so that the solve's own costs give the
               effective sample size max(1, ess_target * n_finite), within lambda_limits = (lambda_min, lambda_max)
               (Engine.set_ess_target); 0 (default) keeps the preset's lambda.
+    control_cost: above 0, the engine adds the control-cost term of information-theoretic MPPI, gamma = control_cost
+              (cost units, absolute; Williams' choice is lambda * (1 - alpha)), to the costs the softmin weighs
+              (Engine.set_control_cost); 0 (default) weighs the rollout's costs alone.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
                  noise: str = "device", seed: int = 0, precision: int = L.PREC_BF16, ctx=None,
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
-                 lambda_limits=(1e-3, 1e3), **overrides):
+                 lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -85,6 +88,9 @@ class MPPIModel:
             raise ValueError("MPPIModel: lambda_limits must be (lambda_min, lambda_max)") from None
         if len(self.lambda_limits) != 2 or not (0.0 < self.lambda_limits[0] <= self.lambda_limits[1] < np.inf):
             raise ValueError("MPPIModel: lambda_limits needs 0 < lambda_min <= lambda_max < inf")
+        self.control_cost = float(control_cost)
+        if not 0.0 <= self.control_cost < np.inf:  # (NaN included)
+            raise ValueError("MPPIModel: control_cost must be finite and >= 0")
         self.preset = preset
         self.body_ids = dict(HUMANOID_BODY_IDS if body_ids is None else body_ids)
         self.u0_before = bool(u0_before)
@@ -126,6 +132,8 @@ class MPPIModel:
             self.engine.set_noise_adapt(self.adapt_noise, *self.adapt_limits)
         if self.ess_target > 0.0:
             self.engine.set_ess_target(self.ess_target, *self.lambda_limits)
+        if self.control_cost > 0.0:
+            self.engine.set_control_cost(self.control_cost)
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0

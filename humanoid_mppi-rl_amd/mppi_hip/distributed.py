@@ -240,7 +240,10 @@ def combine_k_shards(costs: np.ndarray, dU_r: np.ndarray, lam: float, norm_eps: 
     Non-finite costs get weight 0, as in the engine.  A shard with no finite cost contributes
     S_r = 0 and P_r = 0 without reading its dU_r (an engine reports such a solve as MPPI_E_NONFINITE and its dU_r
     is undefined, e.g. NaN), so the combine equals the unsharded solve over the finite samples.  If no rank has a
-    finite cost every rank raises ValueError after the MIN allreduce (collectively, so no rank is left waiting)."""
+    finite cost every rank raises ValueError after the MIN allreduce (collectively, so no rank is left waiting).
+
+    With the control-cost term on (Engine.set_control_cost) a rank's dU_r was weighed with costs + term, so it passes
+    that sum here too: `costs + engine.control_term(1)[0]` of its shard."""
     import torch
     import torch.distributed as dist
 

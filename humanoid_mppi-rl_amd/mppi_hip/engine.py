@@ -187,6 +187,44 @@ class Engine:
         L.check(self.lib.mppi_lambda_eval(self._h, costs.shape[0], _ptr(costs), _ptr(out)))
         return out
 
+    # -- the control-cost term (mppi_set_control_cost; mppi_hip.stats.control_term_ref states the definitions)
+    def set_control_cost(self, gamma: float):
+        """Add the control-cost term of information-theoretic MPPI to the costs the softmin weighs
+        (mppi_set_control_cost): gamma * sum U Sigma^-1 eps with Sigma the covariance of the law that drew the solve's
+        noise.  A finite gamma > 0 (cost units, absolute) enables, 0 disables.  Works in every stream form; the `costs`
+        output stays the rollout's.  The analytic cartpole leaves its fused one-launch form while it is on.  Any change
+        destroys captured graphs; a prefetched noise is kept."""
+        L.check(self.lib.mppi_set_control_cost(self._h, ctypes.c_float(gamma)))
+        return self
+
+    def control_cost(self) -> float:
+        """gamma of mppi_get_control_cost; 0.0 while the term is off."""
+        g = ctypes.c_float()
+        L.check(self.lib.mppi_get_control_cost(self._h, ctypes.byref(g)))
+        return float(g.value)
+
+    def control_term(self, B: int = 1) -> tuple[np.ndarray, np.ndarray]:
+        """(term [B, K], lin [B, nu, H]) of the last solve enqueued with the term on (mppi_get_control_term; waits for
+        the stream) -- after graph_launch the chain's last solve."""
+        c = self.config
+        term = np.empty((B, c.K), np.float32)
+        lin = np.empty((B, c.nu, c.H), np.float32)
+        L.check(self.lib.mppi_get_control_term(self._h, B, _ptr(term), _ptr(lin)))
+        return term, lin
+
+    def control_term_eval(self, U, noise) -> tuple[np.ndarray, np.ndarray]:
+        """The term's kernels on host arrays U [B, nu, H] and noise [B, nu, H, K] with the handle's current law and
+        gamma -> (term [B, K], lin [B, nu, H]) (mppi_control_term_eval).  Needs the term enabled; no dynamics or cost
+        need be loaded."""
+        c = self.config
+        U = _f32(U).reshape(-1, c.nu, c.H)
+        B = U.shape[0]
+        nz = _f32(noise).reshape(B, c.nu, c.H, c.K)
+        term = np.empty((B, c.K), np.float32)
+        lin = np.empty((B, c.nu, c.H), np.float32)
+        L.check(self.lib.mppi_control_term_eval(self._h, B, _ptr(U), _ptr(nz), _ptr(term), _ptr(lin)))
+        return term, lin
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,

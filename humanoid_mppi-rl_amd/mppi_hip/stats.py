@@ -27,6 +27,14 @@ above, n = |F|, ESS(lambda) = (sum wt)^2 / sum wt^2 and the target T = max(1, es
                             ESS(lo) < T <= ESS(hi) with hi / lo <= 1 + 2e-6
 
 ess_ref and ess_lambda_ref are the float64 restatement (the true root by bisection to convergence).
+
+The control-cost term (mppi_set_control_cost; csrc/control_cost.h is the fp32 rule for lin): the softmin weighs
+costs + term with
+
+    lin[b, u, t] = gamma / sigma_u[u]^2 * (P U[b, u, :])[t]       (sigma_u[u] == 0: 0)
+    term[b, k]   = sum_{u,t} lin[b, u, t] * eps[b, u, t, k]
+
+P the precision matrix of the unit-variance AR(1) row (ar1_precision).  control_term_ref is the float64 restatement.
 """
 from __future__ import annotations
 
@@ -261,3 +269,61 @@ def ess_lambda_ref(costs, ess_frac: float, lambda_min: float, lambda_max: float,
                     lo = mid
             out[b] = np.exp(hi)
     return float(out[0]) if single else out
+
+
+def ar1_precision(H: int, rho: float) -> np.ndarray:
+    """P [H, H], the inverse of the unit-variance AR(1) covariance C[t, s] = rho^|t-s|: tridiagonal,
+    1/(1 - rho^2) * tridiag(-rho; [1, 1 + rho^2, ..., 1 + rho^2, 1]; -rho) for H >= 2 and [1] for H == 1."""
+    H, rho = int(H), float(rho)
+    if H < 1 or not 0.0 <= rho < 1.0:
+        raise ValueError("ar1_precision: need H >= 1 and rho in [0, 1)")
+    if H == 1:
+        return np.ones((1, 1))
+    d = np.full(H, 1.0 + rho * rho)
+    d[0] = d[-1] = 1.0
+    P = np.diag(d) - rho * (np.eye(H, k=1) + np.eye(H, k=-1))
+    return P / (1.0 - rho * rho)
+
+
+def control_term_ref(U, noise, sigma_u, rho: float, gamma: float):
+    """The control-cost term in float64 (include/mppi.h mppi_set_control_cost): U [B, nu, H] (or [nu, H]), noise
+    [B, nu, H, K] (or [nu, H, K]), sigma_u [nu] (or a scalar: every actuator's), rho in [0, 1), gamma >= 0 ->
+    (term [B, K], lin [B, nu, H], majorant [B, nu, H]).
+
+        lin  = gamma / sigma_u^2 * P U      along t, P = ar1_precision(H, rho); a frozen actuator (sigma_u == 0): 0
+        term = sum_{u,t} lin * noise        every row, lin == 0 included: a non-finite noise entry makes its sample's
+                                            term non-finite (0 * inf = NaN), as on the device
+        majorant = gamma / sigma_u^2 * |P| |U|: the absolute-value bound of lin that the fp32 rule's rounding error is
+                   stated against (csrc/control_cost.h: |lin_f32 - lin| <= 8 * 2^-24 * majorant)
+
+    ValueError on gamma negative or non-finite, rho outside [0, 1), negative or non-finite sigma_u, or shapes that do
+    not agree."""
+    U = np.asarray(U, np.float64)
+    e = np.asarray(noise, np.float64)
+    single = U.ndim == 2
+    if U.ndim not in (2, 3) or e.ndim != U.ndim + 1:
+        raise ValueError("control_term_ref: U must be [B, nu, H] (or [nu, H]) and noise [B, nu, H, K] (or [nu, H, K])")
+    if single:
+        U, e = U[None], e[None]
+    B, nu, H = U.shape
+    if e.shape[:3] != (B, nu, H):
+        raise ValueError(f"control_term_ref: noise must be [{B}, {nu}, {H}, K], got {list(e.shape)}")
+    gamma, rho = float(gamma), float(rho)
+    if not 0.0 <= gamma < np.inf:
+        raise ValueError("control_term_ref: gamma must be finite and >= 0")
+    if not 0.0 <= rho < 1.0:
+        raise ValueError("control_term_ref: rho must be in [0, 1)")
+    s = np.asarray(sigma_u, np.float64)
+    s = np.full(nu, float(s)) if s.ndim == 0 else s.ravel()
+    if s.size != nu or not (np.all(np.isfinite(s)) and np.all(s >= 0.0)):
+        raise ValueError(f"control_term_ref: sigma_u must be {nu} finite entries >= 0")
+    P = ar1_precision(H, rho)
+    scale = np.zeros(nu)
+    scale[s > 0.0] = gamma / s[s > 0.0] ** 2
+    lin = scale[None, :, None] * np.einsum("ts,bus->but", P, U)
+    majorant = scale[None, :, None] * np.einsum("ts,bus->but", np.abs(P), np.abs(U))
+    with np.errstate(invalid="ignore"):  # (a non-finite noise entry makes its sample's term non-finite, as on the device)
+        term = np.einsum("but,butk->bk", lin, e)
+    if single:
+        return term[0], lin[0], majorant[0]
+    return term, lin, majorant

@@ -73,7 +73,11 @@ extern "C" {
  *      Additive, version unchanged: mppi_set_ess_target / mppi_get_ess_target / mppi_get_lambda / mppi_lambda_eval
  *      (the softmin temperature chosen on the device, per solve, to hold a requested effective sample size); kernel
  *      name "lambda" in mppi_kernel_time.  A handle that never enables it launches exactly the kernels it launched
- *      before, with the same grids. */
+ *      before, with the same grids.
+ *      Additive, version unchanged: mppi_set_control_cost / mppi_get_control_cost / mppi_get_control_term /
+ *      mppi_control_term_eval (the control-cost term of information-theoretic MPPI added to the costs the softmin
+ *      weighs); kernel name "ctrl_cost" in mppi_kernel_time.  A handle that never enables it launches exactly the
+ *      kernels it launched before, with the same grids and arguments. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -341,6 +345,55 @@ int mppi_get_ess_target(mppi_handle* h, float* ess_frac, float* lambda_min, floa
 int mppi_get_lambda(mppi_handle* h, int B, int step, float* lambda /* [B] */);
 int mppi_lambda_eval(mppi_handle* h, int B, const float* costs /* [B][K] host */, float* lambda /* [B] */);
 
+/* The control-cost term of information-theoretic MPPI (Williams et al. 2017/2018; pytorch_mppi's perturbation cost):
+ * the importance-sampling correction for sampling around a non-zero nominal U, added ON THE DEVICE to the costs the
+ * softmin weighs,
+ *     S~_k = S_k + gamma * sum_{u,t} U[u][t] * (Sigma^-1 eps_k)[u][t]
+ * with Sigma the covariance of the law that drew the solve's noise.  With the term on, every solve runs two more
+ * kernels between its rollout and its reduce (csrc/kernels_ctrl_cost.hip; one streaming pass over the solve's noise).
+ * For solve b with nominal U (the U the rollout perturbed, before the update), sigma_u[u] and rho of the law that drew
+ * this solve's noise (cfg.sigma and 0 for the default law, the by-value model of mppi_set_noise_model, or the device
+ * law while mppi_set_noise_adapt is on) and P the precision matrix of the unit-variance AR(1) row (H x H, tridiagonal:
+ * H >= 2: P = 1/(1-rho^2) * tridiag(-rho; [1, 1+rho^2, ..., 1+rho^2, 1]; -rho);  H == 1: P = [1]):
+ *     lin[b][u][t] = gamma / sigma_u[u]^2 * (P U[b][u][:])[t]       (sigma_u[u] == 0, a frozen actuator: lin = 0)
+ *     term[b][k]   = sum_u sum_t lin[b][u][t] * eps[b][u][t][k]     (the raw eps, before ctrl_clamp; injected noise as given)
+ *     wcost[b][k]  = costs[b][k] + term[b][k]                       (non-finite costs stay non-finite)
+ * Every row enters the sum as fmaf(lin, eps, .), a row whose lin is 0 (a frozen actuator) included: a non-finite
+ * injected eps on ANY row makes that sample's term, and so its wcost, non-finite (0 * inf is NaN) and its weight 0.
+ * Such noise is outside what a solve supports in any case: the reduce forms sum_k w_k eps_k over the same values.
+ * (the fp32 rule for lin is csrc/control_cost.h; mppi_hip.stats.control_term_ref is the float64 restatement; the sum
+ * over (u, t) is fp32 in an order fixed by the shape: bitwise repeatable, and the same whichever of the kernel's two
+ * grid forms ran -- env MPPI_CTRL_COST_FORM=block|split and MPPI_CTRL_COST_NT=0|1, read per launch, force a form / the
+ * nontemporal loads).  Every consumer of the solve's costs behind the rollout reads wcost: the lambda search of
+ * mppi_set_ess_target, the reduce's softmin, the `weights` output, MPPI_FLAG_STATS (its cost_* fields then describe
+ * wcost, the update that was applied) and, through the statistics, the noise adaptation.  The `costs` output,
+ * mppi_device_buffers' dcosts, the env step, the MPPI_PREC_BF16X3 probe, the seed counter and the noise are bit for bit
+ * what they are without the term; mppi_stats_eval and mppi_lambda_eval never add it.  The analytic cartpole leaves its
+ * fused one-launch form while the term is on, exactly as for ESS targeting (rollout, term, [search,] reduce; its
+ * rollouts are then not stamped by mppi_kernel_clock).  A K-sharded solve (mppi_hip.distributed.combine_k_shards)
+ * passes costs + control term from each rank.
+ * mppi_set_control_cost: a finite gamma > 0 enables, gamma == 0 disables; anything else (NaN included) is MPPI_E_ARG
+ * and changes nothing.  gamma is in cost units and absolute (Williams' choice is lambda * (1 - alpha)); it is
+ * deliberately not tied to lambda: with ESS targeting lambda is chosen from these very costs.  Enabling, disabling or
+ * changing gamma destroys captured graphs (mppi_graph_launch returns MPPI_E_STATE until the next capture; a captured
+ * graph replays the gamma it was captured with); setting the gamma already in effect is a no-op that keeps them.  A
+ * prefetched noise is kept, because gamma does not enter the noise: the key sequence is unchanged.  The term's
+ * buffers are allocated here, none inside a solve.
+ * mppi_get_control_cost: *gamma (0 while off).
+ * mppi_get_control_term: term [B][K] and lin [B][nu][H] (each may be NULL) of the last solve enqueued -- after a graph
+ * launch the chain's last solve; there are no per-step slots.  Waits for the stream.  MPPI_E_STATE if no solve with
+ * the term has run, MPPI_E_ARG for B beyond that solve.
+ * mppi_control_term_eval: the same kernels on host arrays U [B][nu][H] and noise [B][nu][H][K] with the handle's
+ * current law and gamma: the entry that needs no rollout.  Needs only mppi_create and the term enabled (MPPI_E_STATE
+ * otherwise).  It goes through the handle's staging noise: a prefetched noise is dropped as by mppi_stats_eval (key
+ * sequence unchanged); its outputs have their own slot, so the last solve's term stays readable, and the resident U
+ * is untouched. */
+int mppi_set_control_cost(mppi_handle* h, float gamma);
+int mppi_get_control_cost(mppi_handle* h, float* gamma); /* 0 while off */
+int mppi_get_control_term(mppi_handle* h, int B, float* term /* [B][K] or NULL */, float* lin /* [B][nu][H] or NULL */);
+int mppi_control_term_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
+                           const float* noise /* [B][nu][H][K] host */, float* term, float* lin);
+
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
  *     eps_m2 [b][u] = 1/H     sum_{t=0..H-1} sum_k w_k eps[b][u][t][k]^2
@@ -392,7 +445,7 @@ int mppi_sync(mppi_handle* h);
 /* Per-kernel timing with hipEvents recorded on the handle's stream around each launch.
  * enable != 0 starts accumulating; mppi_kernel_times returns {count, total_ms} per kernel
  * name. names: "noise", "rollout", "reduce", "update", "stats" (the launches of MPPI_FLAG_STATS), "lambda" (the
- * search of mppi_set_ess_target). */
+ * search of mppi_set_ess_target), "ctrl_cost" (the launches of mppi_set_control_cost, counted as one). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
