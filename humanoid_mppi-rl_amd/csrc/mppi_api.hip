@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "costs.h"
+#include "ctrl_bounds.h"  // ctrl_bounds_valid
 #include "ess_target.h"  // EssTarget
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
@@ -50,13 +51,16 @@ enum KernelId {
   kStats = 4,
   kLambda = 5,
   kCtrl = 6,
-  kNumKernels = 7
+  kBounds = 7,
+  kNumKernels = 8
 };
-const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost"};
+const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost",
+                                         "bounds"};
 
 struct PendingEvt {
   int id;
   hipEvent_t a, b;
+  int n;  // what the group adds to the kernel's count (0: its time joins a group already counted)
 };
 
 }  // namespace
@@ -161,6 +165,18 @@ struct mppi_handle {
   float* d_ctrl_U = nullptr;      // [max_batch][nu][H] mppi_control_term_eval's U (the resident d_U stays as it is)
   int ctrl_B = 0;                 // batch of the last solve / graph launch with the term (0: none ran)
   bool graph_ctrl = false;        // the captured graph carries the term
+  // per-actuator control bounds (mppi_set_control_bounds; ctrl_bounds.h, kernels_bounds.hip).  While bounds_on every
+  // solve projects its noise in place ahead of its rollout (the buffer then holds clip(U + eps, lo, hi) - U) and clips
+  // U, the Umirror copy and u0 behind its update; the box travels by value in the launches.  The buffers are allocated
+  // by mppi_set_control_bounds: the counts in two slots (0: the last solve's, 1: mppi_bounds_eval's), summed by the
+  // clip's launch from the per-row counts the projection leaves in d_bpart.
+  bool bounds_on = false;
+  float bounds_lo[kMaxNu] = {0}, bounds_hi[kMaxNu] = {0};
+  unsigned* d_bcounts = nullptr;  // [2][max_batch][nu]
+  unsigned* d_bpart = nullptr;    // [max_batch nu H][bounds_chunks(Kp)] the projection's per-row counts (scratch)
+  float* d_bounds_U = nullptr;    // [max_batch][nu][H] mppi_bounds_eval's U (the resident d_U stays as it is)
+  int bounds_B = 0;               // batch of the last bounded solve / graph launch (0: none ran)
+  bool graph_bounds = false;      // the captured graph carries the bounds
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -178,7 +194,7 @@ static void harvest_events(mppi_handle* h) {
   for (auto& p : h->pending) {
     float ms = 0.0f;
     if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-      h->prof_count[p.id] += 1;
+      h->prof_count[p.id] += p.n;
       h->prof_ms[p.id] += ms;
     }
     h->evt_pool.push_back(p.a);
@@ -187,12 +203,13 @@ static void harvest_events(mppi_handle* h) {
   h->pending.clear();
 }
 
-// Enqueue `launch` on the handle's stream, bracketed by events when profiling.
+// Enqueue `launch` on the handle's stream, bracketed by events when profiling.  count = 0: the group's time is added
+// to a kernel name whose launches of this solve were counted already (the bounds' second launch group).
 template <class F>
-static hipError_t timed(mppi_handle* h, int id, F&& launch) {
+static hipError_t timed(mppi_handle* h, int id, F&& launch, int count = 1) {
   if (!h->prof) return launch();
   if (h->pending.size() > 4096) harvest_events(h);
-  PendingEvt p{id, take_event(h), take_event(h)};
+  PendingEvt p{id, take_event(h), take_event(h), count};
   (void)hipEventRecord(p.a, h->stream);
   hipError_t e = launch();
   (void)hipEventRecord(p.b, h->stream);
@@ -285,7 +302,8 @@ void mppi_destroy(mppi_handle* h) {
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
                   h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist,
-                  h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U};
+                  h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U, h->d_bcounts,
+                  h->d_bpart, h->d_bounds_U};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -744,6 +762,32 @@ static hipError_t enqueue_ctrl(mppi_handle* h, int B, const float* U, const floa
   return launch_ctrl_cost(ca, h->stream);
 }
 
+// The bounds' launches of B solves.  Projection: noise [B][nu][H][Kp] in place against the nominal U.  Clip: the
+// projection's counts summed into slot `slot` (0: a solve, 1: mppi_bounds_eval), and U, its mirror and u0 clipped
+// behind the update (an evaluation passes none).
+static BoundsArgs bounds_args(const mppi_handle* h, int B, int slot = 0) {
+  const mppi_config& c = h->cfg;
+  BoundsArgs ba;
+  std::memset(&ba, 0, sizeof(ba));
+  ba.B = B;
+  ba.nu = c.nu;
+  ba.H = c.H;
+  ba.K = c.K;
+  ba.Kp = h->Kp;
+  ba.part = h->d_bpart;
+  ba.counts = h->d_bcounts + (size_t)slot * c.max_batch * c.nu;
+  std::memcpy(ba.lo, h->bounds_lo, sizeof(ba.lo));
+  std::memcpy(ba.hi, h->bounds_hi, sizeof(ba.hi));
+  return ba;
+}
+
+static hipError_t enqueue_bounds_project(mppi_handle* h, int B, const float* U, float* noise) {
+  BoundsArgs ba = bounds_args(h, B);
+  ba.noise = noise;
+  ba.U = U;
+  return launch_bounds_project(ba, h->stream);
+}
+
 // Validate one solve request against the handle.
 static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if (!h || !io) return fail(MPPI_E_ARG, "mppi_solve: null argument");
@@ -897,6 +941,11 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     }));
   }
 
+  // per-actuator bounds: the solve's noise -- drawn above, prefetched by the previous solve's generator, or the copy of
+  // an injected io.noise (never the caller's array) -- projected in place against the nominal U, ahead of the rollout
+  // and of every other reader of this solve's noise
+  if (h->bounds_on) HIP_TRY(timed(h, kBounds, [&] { return enqueue_bounds_project(h, B, a.U, a.noise); }));
+
   // ---- a2-a6: rollout + cost; a7-a9: softmin + weighted-noise reduce + update + shift
   const NoiseGen gen{ns ? ns->next : nullptr, seed, c.sigma, h->d_gticket};
   // an active noise model's rows depend on the row before them, which the fused generators (one row at a time, in
@@ -928,6 +977,13 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
     HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s); }));
   }
+  // per-actuator bounds: behind the update and shift (the cartpole's fused epilogue included), ahead of the env step,
+  // the trajectory record and the output copies, U, its mirror and u0 are clipped: this removes the last rounding of
+  // U + sum w (v - U), brings a shift-filled last column into a box that excludes zero, and makes lo <= U, u0 <= hi
+  // hold exactly whatever the update mode and flags; the same launch sums the projection's counts (its time joins
+  // "bounds", counted once per solve above)
+  if (h->bounds_on)
+    HIP_TRY(timed(h, kBounds, [&] { return launch_bounds_clip(bounds_args(h, B), a.U, a.Umirror, a.u0, s); }, 0));
   // diagnostics (MPPI_FLAG_STATS): read-only on this solve's costs and noise, behind the reduce (or the cartpole's fused
   // epilogue) and ahead of everything that may write a.noise -- the next solve's generators, on this stream or ordered
   // behind it (ev_red), only ever write the OTHER buffer of the pair before this point
@@ -1074,6 +1130,7 @@ static void note_stats(mppi_handle* h, int B, int flags) {
     h->lam_n = 1;
   }
   if (h->ctrl_gamma > 0.0f) h->ctrl_B = B;
+  if (h->bounds_on) h->bounds_B = B;
 }
 
 // MPPI_FLAG_CHAIN: one solve of a graph stream, launched on the stream (rollout -> reduce_kernel<GEN>, or with
@@ -1376,6 +1433,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->graph_adapt = h->adapt_on;
   h->graph_ess = h->ess_on;
   h->graph_ctrl = h->ctrl_gamma > 0.0f;
+  h->graph_bounds = h->bounds_on;
   h->graph_B = B;
   h->graph_n = n_solves;
   h->graph_seed = seed;
@@ -1405,6 +1463,7 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
     h->lam_n = h->graph_n;
   }
   if (h->graph_ctrl) h->ctrl_B = h->graph_B;  // (no per-step slots: the chain's last solve)
+  if (h->graph_bounds) h->bounds_B = h->graph_B;  // (likewise)
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1721,6 +1780,105 @@ int mppi_control_term_eval(mppi_handle* h, int B, const float* U, const float* n
   HIP_TRY(timed(h, kCtrl, [&] { return enqueue_ctrl(h, B, h->d_ctrl_U, h->d_noise, h->d_costs, 1); }));
   HIP_TRY(hipStreamSynchronize(s));
   return copy_ctrl(h, B, 1, term, lin);
+}
+
+int mppi_set_control_bounds(mppi_handle* h, const float* lo, const float* hi) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_control_bounds: null handle");
+  const mppi_config& c = h->cfg;
+  const bool on = lo != nullptr || hi != nullptr;
+  if (!on && !h->bounds_on) return MPPI_OK;  // nothing to disable
+  if (on && c.nu > kMaxNu)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_control_bounds: the box travels as a kernel argument (nu <= 32)");
+  float nlo[kMaxNu] = {0}, nhi[kMaxNu] = {0};
+  if (on) {
+    for (int u = 0; u < c.nu; ++u) {
+      nlo[u] = lo ? lo[u] : -INFINITY;
+      nhi[u] = hi ? hi[u] : INFINITY;
+    }
+    if (!ctrl_bounds_valid(nlo, nhi, c.nu))
+      return fail(MPPI_E_ARG, "mppi_set_control_bounds: need lo[u] <= hi[u], neither a NaN, for every actuator");
+    if (h->bounds_on && std::memcmp(nlo, h->bounds_lo, sizeof(nlo)) == 0 &&
+        std::memcmp(nhi, h->bounds_hi, sizeof(nhi)) == 0)
+      return MPPI_OK;  // no change: captured graphs stay
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (on && !h->d_bcounts) {  // all three buffers, once, or none (every entry is written before it is read)
+    const size_t nc = (size_t)2 * c.max_batch * c.nu * sizeof(unsigned), nU = (size_t)c.max_batch * c.nu * c.H * 4;
+    const size_t np = (size_t)c.max_batch * c.nu * c.H * bounds_chunks(h->Kp) * sizeof(unsigned);
+    unsigned *cnt = nullptr, *part = nullptr;
+    float* u = nullptr;
+    hipError_t e = hipMalloc(&cnt, nc < 16 ? 16 : nc);
+    if (e == hipSuccess) e = hipMalloc(&part, np < 16 ? 16 : np);
+    if (e == hipSuccess) e = hipMalloc(&u, nU < 16 ? 16 : nU);
+    if (e != hipSuccess) {
+      if (cnt) (void)hipFree(cnt);
+      if (part) (void)hipFree(part);
+      if (u) (void)hipFree(u);
+      return fail(MPPI_E_HIP, std::string("mppi_set_control_bounds: ") + hipGetErrorString(e));
+    }
+    h->d_bcounts = cnt;
+    h->d_bpart = part;
+    h->d_bounds_U = u;
+  }
+  // stale state: the captured graphs hold the box (or its absence) in their launches; a launch still in flight finishes
+  // first.  A prefetched noise is kept: it is projected at the start of the solve that consumes it, with the box in
+  // effect then, so the key sequence is unchanged
+  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
+  for (hipGraphExec_t& g : h->graph_exec)
+    if (g) {
+      HIP_TRY(hipGraphExecDestroy(g));
+      g = nullptr;
+    }
+  std::memcpy(h->bounds_lo, nlo, sizeof(nlo));
+  std::memcpy(h->bounds_hi, nhi, sizeof(nhi));
+  h->bounds_on = on;
+  return MPPI_OK;
+}
+
+int mppi_get_control_bounds(mppi_handle* h, float* lo, float* hi, int* active) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_control_bounds: null handle");
+  for (int u = 0; u < h->cfg.nu; ++u) {
+    if (lo) lo[u] = h->bounds_on ? h->bounds_lo[u] : -INFINITY;
+    if (hi) hi[u] = h->bounds_on ? h->bounds_hi[u] : INFINITY;
+  }
+  if (active) *active = h->bounds_on ? 1 : 0;
+  return MPPI_OK;
+}
+
+int mppi_get_bound_counts(mppi_handle* h, int B, uint32_t* counts) {
+  if (!h || !counts) return fail(MPPI_E_ARG, "mppi_get_bound_counts: null argument");
+  if (h->bounds_B == 0) return fail(MPPI_E_STATE, "mppi_get_bound_counts: no solve with control bounds has run on the handle");
+  if (B < 1 || B > h->bounds_B)
+    return fail(MPPI_E_ARG, "mppi_get_bound_counts: B beyond the batch of the last bounded solve");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(counts, h->d_bcounts, (size_t)B * h->cfg.nu * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_bounds_eval(mppi_handle* h, int B, const float* U, const float* noise_in, float* noise_out, uint32_t* counts) {
+  if (!h || !U || !noise_in) return fail(MPPI_E_ARG, "mppi_bounds_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_bounds_eval: B out of range [1, max_batch]");
+  if (!h->bounds_on) return fail(MPPI_E_STATE, "mppi_bounds_eval: call mppi_set_control_bounds first");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  HIP_TRY(hipMemcpyAsync(h->d_bounds_U, U, rows * 4, hipMemcpyHostToDevice, s));
+  if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, s));
+  HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, noise_in, K * 4, K * 4, rows, hipMemcpyHostToDevice, s));
+  HIP_TRY(timed(h, kBounds, [&] {  // the projection, then its counts into the evaluation's own slot (no U to clip)
+    const hipError_t e = enqueue_bounds_project(h, B, h->d_bounds_U, h->d_noise);
+    return e != hipSuccess ? e : launch_bounds_clip(bounds_args(h, B, 1), nullptr, nullptr, nullptr, s);
+  }));
+  if (noise_out)
+    HIP_TRY(hipMemcpy2DAsync(noise_out, K * 4, h->d_noise, Kp * 4, K * 4, rows, hipMemcpyDeviceToHost, s));
+  if (counts)
+    HIP_TRY(hipMemcpyAsync(counts, h->d_bcounts + (size_t)c.max_batch * c.nu, (size_t)B * c.nu * sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MPPI_OK;
 }
 
 // slot `slot` of the diagnostics' buffers -> host (the stream is idle)

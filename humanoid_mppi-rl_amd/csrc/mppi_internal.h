@@ -359,6 +359,21 @@ struct CtrlArgs {
 };
 size_t ctrl_part_floats(int B, int nu, int H, int Kp);
 hipError_t launch_ctrl_cost(const CtrlArgs& a, hipStream_t stream);  // lin, then the term and wcost (one of two forms)
+// kernels_bounds.hip: per-actuator control bounds (mppi_set_control_bounds; the rule: ctrl_bounds.h), by value like
+// SolveArgs (the box travels as a kernel argument: nu <= kMaxNu), so the launches can sit in a captured graph.
+struct BoundsArgs {
+  int B, nu, H, K, Kp;
+  float* noise;         // [B][nu][H][Kp] projected in place (launch_bounds_project only)
+  const float* U;       // [B][nu][H] the nominal the rollout will perturb (launch_bounds_project only)
+  unsigned* part;       // [B nu H][bounds_chunks(Kp)] the projection's counts per row and 256-k chunk (scratch)
+  unsigned* counts;     // [B][nu] out: the (t, k < K) elements projected (launch_bounds_clip sums part)
+  float lo[kMaxNu], hi[kMaxNu];
+};
+int bounds_chunks(int Kp);  // 256-k chunks of a noise row
+hipError_t launch_bounds_project(const BoundsArgs& a, hipStream_t stream);  // the projection; part written
+// counts from part; U [B][nu][H] (or nullptr: the counts alone), Umirror (or nullptr: no copy) and u0 [B][nu] (or
+// nullptr) clipped to the box
+hipError_t launch_bounds_clip(const BoundsArgs& a, float* U, float* Umirror, float* u0, hipStream_t stream);
 hipError_t launch_record(const float* x, const float* u, float* rx, float* ru, int nxB, int nuB, hipStream_t stream);
 
 }  // namespace mppi

@@ -371,6 +371,73 @@ function control_term_eval(c::Controller, U, noise)
 end
 
 """
+    set_control_bounds!(c, lo, hi)
+
+Keep every sampled control `U + eps` and the nominal `U` inside the box `[lo[u], hi[u]]` (mppi_set_control_bounds): the
+solve's noise is projected on the device ahead of the rollout, `U` and `u0` are clipped behind the update.  `lo`, `hi`:
+numbers or length-nu vectors (the columns of a model's `actuator_ctrlrange`); `nothing` leaves that side unbounded,
+`(nothing, nothing)` disables.  Any change destroys captured graphs; a prefetched noise is kept.  Needs nu <= 32.
+"""
+function set_control_bounds!(c::Controller, lo, hi)
+    nu = c.cfg.nu
+    side(v) = v === nothing ? nothing : (v isa Real ? fill(Float32(v), nu) : Float32.(vec(collect(v))))
+    l, h = side(lo), side(hi)
+    (l === nothing || length(l) == nu) && (h === nothing || length(h) == nu) ||
+        throw(ArgumentError("lo and hi must be numbers or have nu = $nu entries"))
+    GC.@preserve l h check(ccall((:mppi_set_control_bounds, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}),
+                                 c.handle, l === nothing ? Ptr{Float32}(C_NULL) : pointer(l),
+                                 h === nothing ? Ptr{Float32}(C_NULL) : pointer(h)))
+    return c
+end
+
+"""
+    control_bounds(c) -> (lo::Vector{Float32}, hi::Vector{Float32}, active::Bool)
+
+The box of `set_control_bounds!` (mppi_get_control_bounds); -Inf / Inf while the bounds are off.
+"""
+function control_bounds(c::Controller)
+    lo, hi = zeros(Float32, c.cfg.nu), zeros(Float32, c.cfg.nu)
+    active = Ref{Cint}(0)
+    GC.@preserve lo hi check(ccall((:mppi_get_control_bounds, LIB), Cint,
+                                   (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ref{Cint}), c.handle, pointer(lo),
+                                   pointer(hi), active))
+    return (lo, hi, active[] != 0)
+end
+
+"""
+    bound_counts(c) -> Vector{UInt32}
+
+Per actuator, the number of (t, k) noise elements the last bounded solve projected (mppi_get_bound_counts; waits for the
+stream).
+"""
+function bound_counts(c::Controller)
+    n = zeros(UInt32, c.cfg.nu)
+    GC.@preserve n check(ccall((:mppi_get_bound_counts, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt32}), c.handle, 1,
+                               pointer(n)))
+    return n
+end
+
+"""
+    bounds_eval(c, U, noise) -> (noise_out::Array{Float32,3}, counts::Vector{UInt32})
+
+The projection kernel alone on a given `U` (nu, H) and `noise` (nu, H, K) with the handle's box (mppi_bounds_eval);
+needs the bounds set.
+"""
+function bounds_eval(c::Controller, U, noise)
+    nu, H, K = c.cfg.nu, c.cfg.H, c.cfg.K
+    size(U) == (nu, H) || throw(ArgumentError("U must be ($nu, $H)"))
+    size(noise) == (nu, H, K) || throw(ArgumentError("noise must be ($nu, $H, $K)"))
+    Ur = Float32.(permutedims(U))                  # (H, nu) column-major = the library's [nu][H]
+    nz = Float32.(permutedims(noise, (3, 2, 1)))   # (K, H, nu) column-major = the library's [nu][H][K]
+    out = zeros(Float32, K, H, nu)
+    n = zeros(UInt32, nu)
+    GC.@preserve Ur nz out n check(ccall((:mppi_bounds_eval, LIB), Cint,
+                                         (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{UInt32}),
+                                         c.handle, 1, pointer(Ur), pointer(nz), pointer(out), pointer(n)))
+    return (permutedims(out, (3, 2, 1)), n)
+end
+
+"""
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 
 The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and

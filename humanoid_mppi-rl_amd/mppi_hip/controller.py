@@ -69,13 +69,16 @@ class MPPIModel:
     control_cost: above 0, the engine adds the control-cost term of information-theoretic MPPI, gamma = control_cost
               (cost units, absolute; Williams' choice is lambda * (1 - alpha)), to the costs the softmin weighs
               (Engine.set_control_cost); 0 (default) weighs the rollout's costs alone.
+    u_min, u_max: per-actuator control bounds, scalars or [nu] (a MuJoCo model's actuator_ctrlrange columns); the
+              engine keeps every sampled control and the nominal inside the box (Engine.set_control_bounds).  None
+              (default) leaves that side unbounded; both None: no bounds.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
                  noise: str = "device", seed: int = 0, precision: int = L.PREC_BF16, ctx=None,
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
-                 lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, **overrides):
+                 lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -91,6 +94,7 @@ class MPPIModel:
         self.control_cost = float(control_cost)
         if not 0.0 <= self.control_cost < np.inf:  # (NaN included)
             raise ValueError("MPPIModel: control_cost must be finite and >= 0")
+        self.u_min, self.u_max = self._check_bounds(u_min, u_max)
         self.preset = preset
         self.body_ids = dict(HUMANOID_BODY_IDS if body_ids is None else body_ids)
         self.u0_before = bool(u0_before)
@@ -134,10 +138,39 @@ class MPPIModel:
             self.engine.set_ess_target(self.ess_target, *self.lambda_limits)
         if self.control_cost > 0.0:
             self.engine.set_control_cost(self.control_cost)
+        if self.u_min is not None or self.u_max is not None:
+            for name, v in (("u_min", self.u_min), ("u_max", self.u_max)):
+                if v is not None and v.size not in (1, self.config.nu):
+                    raise ValueError(f"MPPIModel: {name} must be a scalar or have nu = {self.config.nu} entries")
+            self.engine.set_control_bounds(None if self.u_min is None else np.broadcast_to(self.u_min, self.config.nu),
+                                           None if self.u_max is None else np.broadcast_to(self.u_max, self.config.nu))
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0
         self.last = None  # SolveResult of the last mppi_step (costs, weights) for inspection
+
+    @staticmethod
+    def _check_bounds(u_min, u_max):
+        """u_min / u_max as float32 vectors (or None): no NaN, u_min <= u_max where both are given."""
+        out = []
+        for name, v in (("u_min", u_min), ("u_max", u_max)):
+            if v is None:
+                out.append(None)
+                continue
+            try:
+                a = np.asarray(v, dtype=np.float32).ravel()
+            except (TypeError, ValueError):
+                raise ValueError(f"MPPIModel: {name} must be a scalar or a sequence of numbers") from None
+            if a.size == 0 or np.isnan(a).any():
+                raise ValueError(f"MPPIModel: {name} must be non-empty and hold no NaN")
+            out.append(a)
+        lo, hi = out
+        if lo is not None and hi is not None:
+            if lo.size != hi.size and 1 not in (lo.size, hi.size):
+                raise ValueError("MPPIModel: u_min and u_max must have matching sizes")
+            if (lo > hi).any():
+                raise ValueError("MPPIModel: u_min must be <= u_max for every actuator")
+        return lo, hi
 
     @property
     def device_adapt(self) -> bool:

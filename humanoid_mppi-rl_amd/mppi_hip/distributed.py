@@ -243,7 +243,12 @@ def combine_k_shards(costs: np.ndarray, dU_r: np.ndarray, lam: float, norm_eps: 
     finite cost every rank raises ValueError after the MIN allreduce (collectively, so no rank is left waiting).
 
     With the control-cost term on (Engine.set_control_cost) a rank's dU_r was weighed with costs + term, so it passes
-    that sum here too: `costs + engine.control_term(1)[0]` of its shard."""
+    that sum here too: `costs + engine.control_term(1)[0]` of its shard.
+
+    With control bounds on (Engine.set_control_bounds) a rank's replace-mode U is np.clip of its dU_r to the box, which
+    is not the weighted noise sum: K-sharding with bounds is not supported on the device; the caller projects its
+    noise itself (stats.project_noise_ref), injects it into unbounded shard engines and clips the combined U on the
+    host."""
     import torch
     import torch.distributed as dist
 

@@ -225,6 +225,57 @@ class Engine:
         L.check(self.lib.mppi_control_term_eval(self._h, B, _ptr(U), _ptr(nz), _ptr(term), _ptr(lin)))
         return term, lin
 
+    # -- per-actuator control bounds (mppi_set_control_bounds; mppi_hip.stats.project_noise_ref states the rule)
+    def _bound(self, v, name):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float32)
+        a = np.full(self.config.nu, a, np.float32) if a.ndim == 0 else np.ascontiguousarray(a).ravel()
+        if a.size != self.config.nu:
+            raise ValueError(f"set_control_bounds: {name} must be a scalar or have nu = {self.config.nu} entries, "
+                             f"got {a.size}")
+        return a
+
+    def set_control_bounds(self, lo=None, hi=None):
+        """Keep every sampled control U + eps and the nominal U inside the box [lo[u], hi[u]] (mppi_set_control_bounds):
+        the solve's noise is projected on the device ahead of the rollout (eps' = clip(U + eps, lo, hi) - U), U and u0
+        are clipped behind the update.  lo, hi: scalars or [nu] (a model's actuator_ctrlrange columns); None leaves
+        that side unbounded, (None, None) disables.  Works in every stream form; costs, weights, the control-cost term
+        and the statistics describe the projected noise.  Any change destroys captured graphs; a prefetched noise is
+        kept.  Needs nu <= 32."""
+        lo, hi = self._bound(lo, "lo"), self._bound(hi, "hi")
+        L.check(self.lib.mppi_set_control_bounds(self._h, None if lo is None else lo.ctypes.data_as(L._fp),
+                                                 None if hi is None else hi.ctypes.data_as(L._fp)))
+        return self
+
+    def control_bounds(self) -> tuple[np.ndarray, np.ndarray, bool]:
+        """(lo [nu], hi [nu], active) of mppi_get_control_bounds; -inf / +inf while the bounds are off."""
+        lo, hi = np.empty(self.config.nu, np.float32), np.empty(self.config.nu, np.float32)
+        active = ctypes.c_int()
+        L.check(self.lib.mppi_get_control_bounds(self._h, lo.ctypes.data_as(L._fp), hi.ctypes.data_as(L._fp),
+                                                 ctypes.byref(active)))
+        return lo, hi, bool(active.value)
+
+    def bound_counts(self, B: int = 1) -> np.ndarray:
+        """counts [B, nu] (uint32): the (t, k) noise elements of each actuator the last enqueued bounded solve
+        projected (mppi_get_bound_counts; waits for the stream) -- after graph_launch the chain's last solve."""
+        out = np.empty((B, self.config.nu), np.uint32)
+        L.check(self.lib.mppi_get_bound_counts(self._h, B, _ptr(out)))
+        return out
+
+    def bounds_eval(self, U, noise) -> tuple[np.ndarray, np.ndarray]:
+        """The projection kernel alone on host arrays U [B, nu, H] and noise [B, nu, H, K] with the handle's box ->
+        (projected noise [B, nu, H, K], counts [B, nu]) (mppi_bounds_eval).  Needs the bounds set; no dynamics or cost
+        need be loaded."""
+        c = self.config
+        U = _f32(U).reshape(-1, c.nu, c.H)
+        B = U.shape[0]
+        nz = _f32(noise).reshape(B, c.nu, c.H, c.K)
+        out = np.empty_like(nz)
+        counts = np.empty((B, c.nu), np.uint32)
+        L.check(self.lib.mppi_bounds_eval(self._h, B, _ptr(U), _ptr(nz), _ptr(out), _ptr(counts)))
+        return out, counts
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,

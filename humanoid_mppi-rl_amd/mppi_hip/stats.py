@@ -35,6 +35,10 @@ costs + term with
     term[b, k]   = sum_{u,t} lin[b, u, t] * eps[b, u, t, k]
 
 P the precision matrix of the unit-variance AR(1) row (ar1_precision).  control_term_ref is the float64 restatement.
+
+Per-actuator control bounds (mppi_set_control_bounds; csrc/ctrl_bounds.h is the rule): ahead of the rollout the
+solve's noise becomes eps' = clip(U + eps, lo, hi) - U, element by element in float32 and only where the box binds.
+project_noise_ref is the numpy restatement: a select and one subtract, so it equals the device bit for bit.
 """
 from __future__ import annotations
 
@@ -327,3 +331,40 @@ def control_term_ref(U, noise, sigma_u, rho: float, gamma: float):
     if single:
         return term[0], lin[0], majorant[0]
     return term, lin, majorant
+
+
+def project_noise_ref(U, noise, lo=None, hi=None):
+    """The projection of mppi_set_control_bounds in float32 (csrc/ctrl_bounds.h), bitwise what the device computes:
+    U [B, nu, H] (or [nu, H]), noise [B, nu, H, K] (or [nu, H, K]), lo / hi scalars or [nu] (None: that side unbounded).
+    With s = U + eps (one float32 add):  s < lo: eps' = lo - U;  s > hi: eps' = hi - U;  else eps' = eps, untouched
+    (a NaN s lands here).  Returns (eps' float32, same shape as noise; counts uint32 [B, nu] (or [nu]): the projected
+    elements per actuator).  lo > hi or a NaN bound raises ValueError."""
+    U = np.asarray(U, np.float32)
+    eps = np.asarray(noise, np.float32)
+    single = U.ndim == 2
+    if single:
+        U, eps = U[None], eps[None]
+    if U.ndim != 3 or eps.ndim != 4 or eps.shape[:3] != U.shape:
+        raise ValueError("project_noise_ref: need U [B, nu, H] and noise [B, nu, H, K]")
+    nu = U.shape[1]
+
+    def side(v, default, name):
+        if v is None:
+            return np.full(nu, default, np.float32)
+        a = np.asarray(v, np.float32)
+        a = np.full(nu, a, np.float32) if a.ndim == 0 else a.ravel()
+        if a.size != nu:
+            raise ValueError(f"project_noise_ref: {name} must be a scalar or have nu = {nu} entries")
+        return a
+
+    lo, hi = side(lo, -np.inf, "lo"), side(hi, np.inf, "hi")
+    if not (lo <= hi).all():  # (a NaN fails the comparison)
+        raise ValueError("project_noise_ref: need lo <= hi, neither a NaN, for every actuator")
+    Ue, lo_e, hi_e = U[..., None], lo[None, :, None, None], hi[None, :, None, None]
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = (Ue + eps).astype(np.float32)
+        below, above = s < lo_e, s > hi_e
+        out = np.where(below, (lo_e - Ue).astype(np.float32), np.where(above, (hi_e - Ue).astype(np.float32), eps))
+    counts = (below | above).sum(axis=(2, 3)).astype(np.uint32)
+    out = out.astype(np.float32, copy=False)
+    return (out[0], counts[0]) if single else (out, counts)

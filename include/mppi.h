@@ -77,7 +77,12 @@ extern "C" {
  *      Additive, version unchanged: mppi_set_control_cost / mppi_get_control_cost / mppi_get_control_term /
  *      mppi_control_term_eval (the control-cost term of information-theoretic MPPI added to the costs the softmin
  *      weighs); kernel name "ctrl_cost" in mppi_kernel_time.  A handle that never enables it launches exactly the
- *      kernels it launched before, with the same grids and arguments. */
+ *      kernels it launched before, with the same grids and arguments.
+ *      Additive, version unchanged: mppi_set_control_bounds / mppi_get_control_bounds / mppi_get_bound_counts /
+ *      mppi_bounds_eval (a per-actuator box that the sampled controls and the nominal stay inside: the solve's noise
+ *      projected ahead of the rollout, U and u0 clipped behind the update); kernel name "bounds" in mppi_kernel_time.
+ *      A handle that never enables them launches exactly the kernels it launched before, with the same grids and
+ *      arguments. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -216,8 +221,8 @@ typedef struct mppi_handle mppi_handle;
 /* Fill *cfg with the reference constants of a named preset:
  * "cartpole_py", "cartpole_jl", "cartpole_collect", "quad_mppi_jl", "humanoid_v3", "humanoid_v1",
  * "humanoid_collect_v2", "cartpole_est", "quad_est".  (src/quadruped_datacollection.py has no preset: its cost
- * reads the rollout's simulation time and weighs each actuator differently, and it clips to the Go1's per-actuator
- * ctrlrange; DESIGN.md §7.  Its apply-before-update convention is MPPI_FLAG_U0_BEFORE.) */
+ * reads the rollout's simulation time and weighs each actuator differently, and its update clips U + sum w eps with
+ * the raw eps to the Go1's per-actuator ctrlrange (the box itself: mppi_set_control_bounds); DESIGN.md §7.  Its apply-before-update convention is MPPI_FLAG_U0_BEFORE.) */
 int mppi_preset(const char* name, mppi_config* cfg);
 
 int mppi_create(const mppi_config* cfg, int device, mppi_handle** out);
@@ -394,6 +399,57 @@ int mppi_get_control_term(mppi_handle* h, int B, float* term /* [B][K] or NULL *
 int mppi_control_term_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
                            const float* noise /* [B][nu][H][K] host */, float* term, float* lin);
 
+/* Per-actuator control bounds, projected ON THE DEVICE: a box [lo[u], hi[u]] per actuator (a MuJoCo model's
+ * actuator_ctrlrange; u_min / u_max of pytorch_mppi) that every sampled control and the nominal itself stay inside.
+ * With bounds on, every solve runs a streaming pass over its noise ahead of its rollout and one small kernel behind its
+ * update (the clip; it also sums the projection's counts) (csrc/kernels_bounds.hip; the rule is csrc/ctrl_bounds.h, mppi_hip.stats.project_noise_ref its numpy
+ * restatement, bitwise equal).  For each element, with U = U[b][u][t] the nominal the rollout perturbs, in fp32:
+ *     s = U + eps;   s < lo[u]: eps' = lo[u] - U;   s > hi[u]: eps' = hi[u] - U;   else eps' = eps (untouched)
+ * i.e. the solve's noise becomes eps' = clip(U + eps, lo, hi) - U in place, in the engine's own buffer (the caller's
+ * io.noise is never written), and the rollouts -- unchanged, routed exactly as without bounds -- evaluate U + eps'.
+ * An element inside the box is never rewritten: a solve whose box never binds is bit for bit the solve without bounds.
+ * Consequently U + eps' is within one rounding of the bound, not always equal to it.  +inf noise projects to hi - U; a
+ * NaN stays a NaN (a non-finite sample, as without bounds).  lo[u] = -inf / hi[u] = +inf leave that side unbounded;
+ * lo[u] == hi[u] pins the actuator.
+ * Injected noise is projected too.  Everything behind the projection sees eps': the `costs` and `weights` outputs,
+ * the reduce, the control-cost term of mppi_set_control_cost, the moments of MPPI_FLAG_STATS and therefore the law
+ * adapted by mppi_set_noise_adapt (a saturating actuator's adapted sigma shrinks).  The update is
+ *     U = clip(U + sum_k w_k (clip(U + eps_k) - U))         (MPPI_UPDATE_REPLACE: clip(sum_k w_k (clip(U + eps_k) - U)))
+ * -- deliberately not src/quadruped_datacollection.py's clip(U + sum w eps) with the raw eps.  The outer
+ * clip runs behind the update and the shift (the analytic cartpole keeps its fused one-launch form) and ahead of the env
+ * step, the trajectory record and the output copies, over U, the io.U copy of MPPI_FLAG_RESIDENT_U and u0: after a
+ * solve with bounds every entry of U and u0 satisfies lo <= . <= hi exactly, in both update modes, with MPPI_FLAG_SHIFT
+ * (a shift-filled last column is brought into a box that excludes zero) and MPPI_FLAG_U0_BEFORE (a nominal that
+ * started outside the box gives a clipped u0).  cfg.ctrl_clamp and cfg.U_clamp keep working and compose with the box.
+ * Plain, ASYNC, chained, captured-graph and trajectory-logging solves agree bit for bit; nothing is allocated inside a
+ * solve.  A K-sharded caller (mppi_hip.distributed.combine_k_shards) clips the combined U on the host.
+ * mppi_set_control_bounds: lo, hi [nu] each; (NULL, NULL) disables, one of them NULL leaves that side unbounded for
+ * every actuator.  lo[u] > hi[u] or a NaN is MPPI_E_ARG and changes nothing; bounds need nu <= 32 (MPPI_E_UNSUPPORTED
+ * otherwise: the box travels as a kernel argument, as an active noise model does).  Allowed any time after
+ * mppi_create.  Any change, enabling and disabling included, destroys captured graphs (mppi_graph_launch returns
+ * MPPI_E_STATE until the next capture); setting the bounds already in effect is a no-op that keeps them.  A prefetched
+ * noise is KEPT: the projection runs at the start of the solve that consumes it, so the key sequence is unchanged.
+ * mppi_get_control_bounds: lo, hi [nu] (-inf / +inf while off) and *active; each pointer may be NULL.
+ * mppi_get_bound_counts: counts [B][nu], the number of (t, k < K) elements of actuator u the last enqueued solve
+ * projected (pad lanes K..Kp never count; integer sums: exactly repeatable) -- after a graph launch the chain's last
+ * solve; there are no per-step slots.  Waits for the stream.  MPPI_E_STATE before any bounded solve, MPPI_E_ARG for B
+ * beyond it.
+ * mppi_bounds_eval: the projection kernel alone on host arrays U [B][nu][H] and noise_in [B][nu][H][K] -> noise_out
+ * (same shape) and counts [B][nu] (each output may be NULL).  Needs only mppi_create and bounds set (MPPI_E_STATE
+ * otherwise).  It goes through the handle's staging noise: a prefetched noise is dropped as by mppi_stats_eval (key
+ * sequence unchanged); its counts have their own slot, so the last solve's stay readable, and the resident U is
+ * untouched.  Env MPPI_BOUNDS_NT=0|1 (read per launch; an A/B arm) forces the cached / the nontemporal loads of the
+ * projection; default: nontemporal above 128 MB of noise.  Env MPPI_BOUNDS_STORE=quad|line (likewise) forces its store
+ * form: a lane stores its 16-B quad only if one of the four elements changed, or (the default) the eight lanes of a
+ * 128-B line store the whole line if one of its quads changed, the unchanged ones bit for bit as read; no wholly
+ * unchanged line is written either way, and the results are bitwise the same.  Env MPPI_BOUNDS_ROWS=1|2|4|8
+ * (likewise; a test knob) forces the rows of noise one wave of the projection takes. */
+int mppi_set_control_bounds(mppi_handle* h, const float* lo /* [nu] or NULL */, const float* hi /* [nu] or NULL */);
+int mppi_get_control_bounds(mppi_handle* h, float* lo, float* hi, int* active);
+int mppi_get_bound_counts(mppi_handle* h, int B, uint32_t* counts /* [B][nu] */);
+int mppi_bounds_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
+                     const float* noise_in /* [B][nu][H][K] host */, float* noise_out, uint32_t* counts);
+
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
  *     eps_m2 [b][u] = 1/H     sum_{t=0..H-1} sum_k w_k eps[b][u][t][k]^2
@@ -445,7 +501,8 @@ int mppi_sync(mppi_handle* h);
 /* Per-kernel timing with hipEvents recorded on the handle's stream around each launch.
  * enable != 0 starts accumulating; mppi_kernel_times returns {count, total_ms} per kernel
  * name. names: "noise", "rollout", "reduce", "update", "stats" (the launches of MPPI_FLAG_STATS), "lambda" (the
- * search of mppi_set_ess_target), "ctrl_cost" (the launches of mppi_set_control_cost, counted as one). */
+ * search of mppi_set_ess_target), "ctrl_cost" (the launches of mppi_set_control_cost, counted as one), "bounds" (the
+ * launches of mppi_set_control_bounds ahead of the rollout and behind the update, counted as one per solve). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
