@@ -16,6 +16,7 @@
 #include "ess_target.h"  // EssTarget
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
+#include "rate_cost.h"  // rate_cost_valid
 #include "noise_adapt.h"  // NoiseAdapt
 #include "noise_model.h"  // ar1_innovation_scale
 
@@ -52,10 +53,11 @@ enum KernelId {
   kLambda = 5,
   kCtrl = 6,
   kBounds = 7,
-  kNumKernels = 8
+  kRate = 8,
+  kNumKernels = 9
 };
 const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost",
-                                         "bounds"};
+                                         "bounds", "rate_cost"};
 
 struct PendingEvt {
   int id;
@@ -177,6 +179,23 @@ struct mppi_handle {
   float* d_bounds_U = nullptr;    // [max_batch][nu][H] mppi_bounds_eval's U (the resident d_U stays as it is)
   int bounds_B = 0;               // batch of the last bounded solve / graph launch (0: none ran)
   bool graph_bounds = false;      // the captured graph carries the bounds
+  // the control-rate cost term (mppi_set_rate_cost; rate_cost.h, kernels_rate_cost.hip).  While rate_on every solve runs
+  // the term kernel between its rollout (and the control-cost term) and everything that weighs its costs; the lambda
+  // search, the reduce and the statistics then read d_rate_wcost = (costs [+ control term]) + rate term.  The weights
+  // travel by value in the launch.  d_uprev is the control applied the step before: zeros until mppi_set_prev_control
+  // writes it or a MPPI_FLAG_SHIFT solve with the anchor on stores its u0 there.  All buffers are allocated by the two
+  // setters, two slots each where an evaluation must not disturb a solve's: slot 0 the last solve's / the handle's,
+  // slot 1 mppi_rate_term_eval's.
+  bool rate_on = false;
+  int rate_anchor = 0;
+  float rate_r[kMaxNu] = {0};
+  float* d_rate_wcost = nullptr;  // [2][max_batch][Kp]
+  float* d_rate_term = nullptr;   // [2][max_batch][Kp]
+  float* d_rate_part = nullptr;   // [rate_part_floats] the split form's partials (scratch)
+  float* d_rate_U = nullptr;      // [max_batch][nu][H] mppi_rate_term_eval's U (the resident d_U stays as it is)
+  float* d_uprev = nullptr;       // [2][max_batch][nu]
+  int rate_B = 0;                 // batch of the last solve / graph launch with the term (0: none ran)
+  bool graph_rate = false;        // the captured graph carries the term
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -303,7 +322,7 @@ void mppi_destroy(mppi_handle* h) {
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
                   h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist,
                   h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U, h->d_bcounts,
-                  h->d_bpart, h->d_bounds_U};
+                  h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -788,6 +807,32 @@ static hipError_t enqueue_bounds_project(mppi_handle* h, int B, const float* U, 
   return launch_bounds_project(ba, h->stream);
 }
 
+// The rate term's launch of B solves into output slot `slot` (0: a solve, 1: mppi_rate_term_eval): the term from U, the
+// noise and u_prev, wcost = costs + term.
+static hipError_t enqueue_rate(mppi_handle* h, int B, const float* U, const float* noise, const float* u_prev,
+                               const float* costs, int slot) {
+  const mppi_config& c = h->cfg;
+  const size_t ok = (size_t)slot * c.max_batch * h->Kp;
+  RateArgs ra;
+  std::memset(&ra, 0, sizeof(ra));
+  ra.B = B;
+  ra.nu = c.nu;
+  ra.H = c.H;
+  ra.K = c.K;
+  ra.Kp = h->Kp;
+  ra.anchor = h->rate_anchor;
+  ra.clamp = c.ctrl_clamp;
+  ra.U = U;
+  ra.noise = noise;
+  ra.u_prev = u_prev;
+  ra.costs = costs;
+  ra.term = h->d_rate_term + ok;
+  ra.wcost = h->d_rate_wcost + ok;
+  ra.part = h->d_rate_part;
+  std::memcpy(ra.r, h->rate_r, sizeof(ra.r));
+  return launch_rate_cost(ra, h->stream);
+}
+
 // Validate one solve request against the handle.
 static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if (!h || !io) return fail(MPPI_E_ARG, "mppi_solve: null argument");
@@ -883,7 +928,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   float* const lam = lambda_slot(h, stats_slot);
   a.lambda_dev = lam;
   const bool ctrl = h->ctrl_gamma > 0.0f;  // the control-cost term: the softmin weighs d_wcost = costs + term (below)
-  const bool cart_unfused = (lam || ctrl) && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  const bool rate = h->rate_on;  // the rate term: the softmin weighs d_rate_wcost = (costs [+ control term]) + rate term
+  const bool cart_unfused = (lam || ctrl || rate) && h->dyn_kind == MPPI_DYN_CARTPOLE;
   // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths); the cartpole's unfused
   // rollout carries no stamp
   a.kclock = (h->kclock && a.seed_ctr && !cart_unfused) ? h->d_kclock : nullptr;
@@ -960,7 +1006,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   } else {
     // (a targeting cartpole too: its fused epilogue forms the softmin partials with lambda before all costs exist, so
     // it runs the unfused rollout of the env step, a.part == nullptr, then the search and reduce_kernel: 3 launches;
-    // and a cartpole with the control-cost term, whose epilogue would weigh costs the term has not reached yet)
+    // and a cartpole with the control-cost or the rate term, whose epilogue would weigh costs the term has not reached yet)
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
     h->rollout_kernel = g_rollout_kernel;
     SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
@@ -973,6 +1019,14 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       wcost = h->d_wcost;
       r.costs = h->d_wcost;
     }
+    if (rate) {
+      // the rate term, behind the control-cost term (wcost = (costs + control term) + rate term, in this order) and ahead
+      // of the reduce: a.U is still the nominal the rollout perturbed, a.noise what the rollout saw (projected, with
+      // bounds on), d_uprev the control the previous step applied (its store sits behind that step's update, below)
+      HIP_TRY(timed(h, kRate, [&] { return enqueue_rate(h, B, a.U, a.noise, h->d_uprev, wcost, 0); }));
+      wcost = h->d_rate_wcost;
+      r.costs = h->d_rate_wcost;
+    }
     if (lam)
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
     HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s); }));
@@ -984,6 +1038,12 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // "bounds", counted once per solve above)
   if (h->bounds_on)
     HIP_TRY(timed(h, kBounds, [&] { return launch_bounds_clip(bounds_args(h, B), a.U, a.Umirror, a.u0, s); }, 0));
+  // the rate term's anchor: the u0 this solve returns (clipped above; the pre-update column with MPPI_FLAG_U0_BEFORE) is
+  // what the next step differences its t = 0 against -- one small launch behind the update and the clip, ahead of the
+  // env step, so chained and captured streams anchor step i + 1 to step i with no host round trip (its time joins
+  // "rate_cost", counted once per solve above)
+  if (rate && h->rate_anchor && (flags & MPPI_FLAG_SHIFT))
+    HIP_TRY(timed(h, kRate, [&] { return launch_rate_store_prev(a.u0, h->d_uprev, B * nu, s); }, 0));
   // diagnostics (MPPI_FLAG_STATS): read-only on this solve's costs and noise, behind the reduce (or the cartpole's fused
   // epilogue) and ahead of everything that may write a.noise -- the next solve's generators, on this stream or ordered
   // behind it (ev_red), only ever write the OTHER buffer of the pair before this point
@@ -1131,6 +1191,7 @@ static void note_stats(mppi_handle* h, int B, int flags) {
   }
   if (h->ctrl_gamma > 0.0f) h->ctrl_B = B;
   if (h->bounds_on) h->bounds_B = B;
+  if (h->rate_on) h->rate_B = B;
 }
 
 // MPPI_FLAG_CHAIN: one solve of a graph stream, launched on the stream (rollout -> reduce_kernel<GEN>, or with
@@ -1434,6 +1495,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->graph_ess = h->ess_on;
   h->graph_ctrl = h->ctrl_gamma > 0.0f;
   h->graph_bounds = h->bounds_on;
+  h->graph_rate = h->rate_on;
   h->graph_B = B;
   h->graph_n = n_solves;
   h->graph_seed = seed;
@@ -1464,6 +1526,7 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
   }
   if (h->graph_ctrl) h->ctrl_B = h->graph_B;  // (no per-step slots: the chain's last solve)
   if (h->graph_bounds) h->bounds_B = h->graph_B;  // (likewise)
+  if (h->graph_rate) h->rate_B = h->graph_B;      // (likewise)
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1879,6 +1942,149 @@ int mppi_bounds_eval(mppi_handle* h, int B, const float* U, const float* noise_i
                            hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return MPPI_OK;
+}
+
+// u_prev [2][max_batch][nu], zeroed: by whichever of mppi_set_rate_cost / mppi_set_prev_control comes first
+static int ensure_uprev(mppi_handle* h) {
+  if (h->d_uprev) return MPPI_OK;
+  const size_t n = (size_t)2 * h->cfg.max_batch * h->cfg.nu * 4;
+  float* p = nullptr;
+  HIP_TRY(hipMalloc(&p, n < 16 ? 16 : n));
+  // zeroed ON THE HANDLE'S STREAM and waited for: a memset on the null stream is not ordered against the copies and
+  // launches the (non-blocking) stream receives next, and could land behind mppi_set_prev_control's values
+  hipError_t e = hipMemsetAsync(p, 0, n, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(p);
+    return fail(MPPI_E_HIP, std::string("u_prev: ") + hipGetErrorString(e));
+  }
+  h->d_uprev = p;
+  return MPPI_OK;
+}
+
+int mppi_set_rate_cost(mppi_handle* h, const float* r, int anchor) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_rate_cost: null handle");
+  const mppi_config& c = h->cfg;
+  const bool on = r != nullptr;
+  if (!on && !h->rate_on) return MPPI_OK;  // nothing to disable
+  if (on && c.nu > kMaxNu)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_rate_cost: the weights travel as a kernel argument (nu <= 32)");
+  float nr[kMaxNu] = {0};
+  const int na = on && anchor ? 1 : 0;
+  if (on) {
+    std::memcpy(nr, r, (size_t)c.nu * 4);
+    if (!rate_cost_valid(nr, c.nu))
+      return fail(MPPI_E_ARG, "mppi_set_rate_cost: r must be finite, every entry >= 0 and at least one > 0");
+    if (h->rate_on && na == h->rate_anchor && std::memcmp(nr, h->rate_r, sizeof(nr)) == 0)
+      return MPPI_OK;  // no change: captured graphs stay
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (on) {
+    if (const int rc = ensure_uprev(h); rc != MPPI_OK) return rc;
+  }
+  if (on && !h->d_rate_wcost) {  // the term's buffers, once, all or none (every entry is written before it is read)
+    const size_t nk = (size_t)2 * c.max_batch * h->Kp * 4, nl = (size_t)c.max_batch * c.nu * c.H * 4;
+    const size_t np = rate_part_floats(c.max_batch, c.nu, c.H, h->Kp) * 4;
+    float *w = nullptr, *t = nullptr, *p = nullptr, *u = nullptr;
+    hipError_t e = hipMalloc(&w, nk);
+    if (e == hipSuccess) e = hipMalloc(&t, nk);
+    if (e == hipSuccess) e = hipMalloc(&p, np < 16 ? 16 : np);
+    if (e == hipSuccess) e = hipMalloc(&u, nl);
+    if (e != hipSuccess) {
+      for (float* x : {w, t, p, u})
+        if (x) (void)hipFree(x);
+      return fail(MPPI_E_HIP, std::string("mppi_set_rate_cost: ") + hipGetErrorString(e));
+    }
+    h->d_rate_wcost = w;
+    h->d_rate_term = t;
+    h->d_rate_part = p;
+    h->d_rate_U = u;
+  }
+  // stale state: the captured graphs hold r and the anchor (or the term's absence) in their launches; a launch still in
+  // flight finishes first.  A prefetched noise is kept: the term does not enter the noise, the key sequence is unchanged
+  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
+  for (hipGraphExec_t& g : h->graph_exec)
+    if (g) {
+      HIP_TRY(hipGraphExecDestroy(g));
+      g = nullptr;
+    }
+  std::memcpy(h->rate_r, nr, sizeof(nr));
+  h->rate_anchor = na;
+  h->rate_on = on;
+  return MPPI_OK;
+}
+
+int mppi_get_rate_cost(mppi_handle* h, float* r, int* anchor, int* active) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_rate_cost: null handle");
+  if (r)
+    for (int u = 0; u < h->cfg.nu; ++u) r[u] = h->rate_on ? h->rate_r[u] : 0.0f;
+  if (anchor) *anchor = h->rate_on ? h->rate_anchor : 0;
+  if (active) *active = h->rate_on ? 1 : 0;
+  return MPPI_OK;
+}
+
+int mppi_set_prev_control(mppi_handle* h, int B, const float* u_prev) {
+  if (!h || !u_prev) return fail(MPPI_E_ARG, "mppi_set_prev_control: null argument");
+  if (B < 1 || B > h->cfg.max_batch) return fail(MPPI_E_ARG, "mppi_set_prev_control: B out of range [1, max_batch]");
+  HIP_TRY(hipSetDevice(h->device));
+  if (const int rc = ensure_uprev(h); rc != MPPI_OK) return rc;
+  // data, not a launch argument: ordered on the stream behind every solve enqueued so far, captured graphs stay
+  HIP_TRY(hipMemcpyAsync(h->d_uprev, u_prev, (size_t)B * h->cfg.nu * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));  // (the caller's array may go)
+  return MPPI_OK;
+}
+
+int mppi_get_prev_control(mppi_handle* h, int B, float* u_prev) {
+  if (!h || !u_prev) return fail(MPPI_E_ARG, "mppi_get_prev_control: null argument");
+  if (B < 1 || B > h->cfg.max_batch) return fail(MPPI_E_ARG, "mppi_get_prev_control: B out of range [1, max_batch]");
+  const size_t n = (size_t)B * h->cfg.nu;
+  if (!h->d_uprev) {  // never set, never stored: zeros
+    std::memset(u_prev, 0, n * 4);
+    return MPPI_OK;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipMemcpy(u_prev, h->d_uprev, n * 4, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+// slot `slot` of the rate term -> host (the stream is idle)
+static int copy_rate(mppi_handle* h, int B, int slot, float* term) {
+  const size_t K = (size_t)h->cfg.K, Kp = (size_t)h->Kp;
+  HIP_TRY(hipMemcpy2D(term, K * 4, h->d_rate_term + (size_t)slot * h->cfg.max_batch * Kp, Kp * 4, K * 4, B,
+                      hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_get_rate_term(mppi_handle* h, int B, float* term) {
+  if (!h || !term) return fail(MPPI_E_ARG, "mppi_get_rate_term: null argument");
+  if (h->rate_B == 0) return fail(MPPI_E_STATE, "mppi_get_rate_term: no solve with the rate term has run on the handle");
+  if (B < 1 || B > h->rate_B) return fail(MPPI_E_ARG, "mppi_get_rate_term: B beyond the batch of the last solve with the term");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_rate(h, B, 0, term);
+}
+
+int mppi_rate_term_eval(mppi_handle* h, int B, const float* U, const float* noise, const float* u_prev, float* term) {
+  if (!h || !U || !noise || !term) return fail(MPPI_E_ARG, "mppi_rate_term_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_rate_term_eval: B out of range [1, max_batch]");
+  if (!h->rate_on) return fail(MPPI_E_STATE, "mppi_rate_term_eval: call mppi_set_rate_cost first");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  float* const up = h->d_uprev + (size_t)c.max_batch * c.nu;  // the evaluation's own u_prev (the handle's stays)
+  HIP_TRY(hipMemcpyAsync(h->d_rate_U, U, rows * 4, hipMemcpyHostToDevice, s));
+  if (u_prev) HIP_TRY(hipMemcpyAsync(up, u_prev, (size_t)B * c.nu * 4, hipMemcpyHostToDevice, s));
+  if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, s));
+  HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, noise, K * 4, K * 4, rows, hipMemcpyHostToDevice, s));
+  // (the evaluation's own slot; its wcost adds the term to whatever the staging costs hold and is never read)
+  HIP_TRY(timed(h, kRate, [&] {
+    return enqueue_rate(h, B, h->d_rate_U, h->d_noise, u_prev ? up : h->d_uprev, h->d_costs, 1);
+  }));
+  HIP_TRY(hipStreamSynchronize(s));
+  return copy_rate(h, B, 1, term);
 }
 
 // slot `slot` of the diagnostics' buffers -> host (the stream is idle)

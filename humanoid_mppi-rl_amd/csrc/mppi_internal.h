@@ -374,6 +374,25 @@ hipError_t launch_bounds_project(const BoundsArgs& a, hipStream_t stream);  // t
 // counts from part; U [B][nu][H] (or nullptr: the counts alone), Umirror (or nullptr: no copy) and u0 [B][nu] (or
 // nullptr) clipped to the box
 hipError_t launch_bounds_clip(const BoundsArgs& a, float* U, float* Umirror, float* u0, hipStream_t stream);
+// kernels_rate_cost.hip: the control-rate cost term (mppi_set_rate_cost; the rule: rate_cost.h), by value like
+// SolveArgs (the weights travel as a kernel argument: nu <= kMaxNu), read-only on the solve's U, noise and costs, so
+// the launches can sit in a captured graph.
+struct RateArgs {
+  int B, nu, H, K, Kp;
+  int anchor;           // 1: t = 0 differences against u_prev
+  float clamp;          // cfg.ctrl_clamp (<= 0: none)
+  const float* U;       // [B][nu][H] the nominal the rollout perturbed
+  const float* noise;   // [B][nu][H][Kp] the noise as the rollout saw it
+  const float* u_prev;  // [B][nu] the control applied the step before (read with anchor only)
+  const float* costs;   // [B][Kp] what the term is added to: the rollout's costs, or costs + control-cost term
+  float* term;          // [B][Kp] out (pads K..Kp: 0)
+  float* wcost;         // [B][Kp] out: costs + term (pads K..Kp: costs)
+  float* part;          // [rate_part_floats] scratch: the split form's per-cell partial sums
+  float r[kMaxNu];
+};
+size_t rate_part_floats(int B, int nu, int H, int Kp);
+hipError_t launch_rate_cost(const RateArgs& a, hipStream_t stream);  // the term and wcost (one of two forms)
+hipError_t launch_rate_store_prev(const float* u0, float* u_prev, int n, hipStream_t stream);  // u_prev <- u0 [n]
 hipError_t launch_record(const float* x, const float* u, float* rx, float* ru, int nxB, int nuB, hipStream_t stream);
 
 }  // namespace mppi

@@ -438,6 +438,101 @@ function bounds_eval(c::Controller, U, noise)
 end
 
 """
+    set_rate_cost!(c, weights; anchor = true)
+
+Add a penalty on the rate of the sampled controls, `sum_u r[u] sum_t (v[u, t] - v[u, t-1])^2` with `v = clamp(U + eps)`,
+to the costs the softmin weighs (mppi_set_rate_cost).  `weights`: a number or a length-nu vector, finite, >= 0, not all
+zero; `nothing` disables.  With `anchor` the first control is differenced against the previously applied one
+(`set_prev_control!`, or the u0 of the last shift solve).  Any change destroys captured graphs; a prefetched noise is
+kept.  Needs nu <= 32.
+"""
+function set_rate_cost!(c::Controller, weights; anchor::Bool = true)
+    nu = c.cfg.nu
+    if weights === nothing
+        check(ccall((:mppi_set_rate_cost, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cint), c.handle, Ptr{Float32}(C_NULL), 0))
+        return c
+    end
+    r = weights isa Real ? fill(Float32(weights), nu) : Float32.(vec(collect(weights)))
+    length(r) == nu || throw(ArgumentError("weights must be a number or have nu = $nu entries"))
+    GC.@preserve r check(ccall((:mppi_set_rate_cost, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Cint), c.handle, pointer(r),
+                               anchor ? 1 : 0))
+    return c
+end
+
+"""
+    rate_cost(c) -> (weights::Vector{Float32}, anchor::Bool, active::Bool)
+
+The settings of `set_rate_cost!` (mppi_get_rate_cost); zeros and false while the term is off.
+"""
+function rate_cost(c::Controller)
+    r = zeros(Float32, c.cfg.nu)
+    anchor, active = Ref{Cint}(0), Ref{Cint}(0)
+    GC.@preserve r check(ccall((:mppi_get_rate_cost, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ref{Cint}, Ref{Cint}),
+                               c.handle, pointer(r), anchor, active))
+    return (r, anchor[] != 0, active[] != 0)
+end
+
+"""
+    set_prev_control!(c, u)
+
+The control applied the step before (length nu) -> the handle's `u_prev` (mppi_set_prev_control), which the anchored
+rate term differences t = 0 against.  Data, not a setting: captured graphs stay.
+"""
+function set_prev_control!(c::Controller, u)
+    v = Float32.(vec(collect(u)))
+    length(v) == c.cfg.nu || throw(ArgumentError("u must have nu = $(c.cfg.nu) entries"))
+    GC.@preserve v check(ccall((:mppi_set_prev_control, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle, 1,
+                               pointer(v)))
+    return c
+end
+
+"""
+    prev_control(c) -> Vector{Float32}
+
+The handle's `u_prev` (mppi_get_prev_control; waits for the stream): zeros until set or stored by a shift solve.
+"""
+function prev_control(c::Controller)
+    v = zeros(Float32, c.cfg.nu)
+    GC.@preserve v check(ccall((:mppi_get_prev_control, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle, 1,
+                               pointer(v)))
+    return v
+end
+
+"""
+    rate_term(c) -> Vector{Float32}
+
+The rate term (length K) of the last solve made with the term on (mppi_get_rate_term; waits for the stream).
+"""
+function rate_term(c::Controller)
+    term = zeros(Float32, c.cfg.K)
+    GC.@preserve term check(ccall((:mppi_get_rate_term, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle, 1,
+                                  pointer(term)))
+    return term
+end
+
+"""
+    rate_term_eval(c, U, noise; u_prev = nothing) -> Vector{Float32}
+
+The term's kernel on a given `U` (nu, H), `noise` (nu, H, K) as the rollout would see it and `u_prev` (length nu;
+`nothing`: the handle's) with the handle's weights, anchor and ctrl_clamp (mppi_rate_term_eval); needs the term enabled.
+"""
+function rate_term_eval(c::Controller, U, noise; u_prev = nothing)
+    nu, H, K = c.cfg.nu, c.cfg.H, c.cfg.K
+    size(U) == (nu, H) || throw(ArgumentError("U must be ($nu, $H)"))
+    size(noise) == (nu, H, K) || throw(ArgumentError("noise must be ($nu, $H, $K)"))
+    Ur = Float32.(permutedims(U))                  # (H, nu) column-major = the library's [nu][H]
+    nz = Float32.(permutedims(noise, (3, 2, 1)))   # (K, H, nu) column-major = the library's [nu][H][K]
+    up = u_prev === nothing ? Float32[] : Float32.(vec(collect(u_prev)))
+    u_prev === nothing || length(up) == nu || throw(ArgumentError("u_prev must have nu = $nu entries"))
+    term = zeros(Float32, K)
+    GC.@preserve Ur nz up term check(ccall((:mppi_rate_term_eval, LIB), Cint,
+                                           (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+                                           c.handle, 1, pointer(Ur), pointer(nz),
+                                           u_prev === nothing ? Ptr{Float32}(C_NULL) : pointer(up), pointer(term)))
+    return term
+end
+
+"""
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 
 The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and

@@ -72,13 +72,19 @@ class MPPIModel:
     u_min, u_max: per-actuator control bounds, scalars or [nu] (a MuJoCo model's actuator_ctrlrange columns); the
               engine keeps every sampled control and the nominal inside the box (Engine.set_control_bounds).  None
               (default) leaves that side unbounded; both None: no bounds.
+    rate_cost, rate_anchor: per-actuator weights, a scalar or [nu] (finite, >= 0, not all zero), of a penalty on the
+              rate of the sampled controls, sum_u r[u] sum_t (v[u, t] - v[u, t-1])^2, added to the costs the softmin
+              weighs (Engine.set_rate_cost).  With rate_anchor (default) the first control is differenced against the
+              control the environment applied last: mppi_step / mppi_controller pass data.ctrl to the engine before
+              each solve.  None (default): no term.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
                  noise: str = "device", seed: int = 0, precision: int = L.PREC_BF16, ctx=None,
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
-                 lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, **overrides):
+                 lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, rate_cost=None,
+                 rate_anchor: bool = True, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -95,10 +101,14 @@ class MPPIModel:
         if not 0.0 <= self.control_cost < np.inf:  # (NaN included)
             raise ValueError("MPPIModel: control_cost must be finite and >= 0")
         self.u_min, self.u_max = self._check_bounds(u_min, u_max)
+        self.rate_cost = self._check_rate(rate_cost)
+        self.rate_anchor = bool(rate_anchor)
         self.preset = preset
         self.body_ids = dict(HUMANOID_BODY_IDS if body_ids is None else body_ids)
         self.u0_before = bool(u0_before)
         self.config = Config.preset(preset, precision=precision, **overrides)
+        if self.rate_cost is not None and self.rate_cost.size not in (1, self.config.nu):
+            raise ValueError(f"MPPIModel: rate_cost must be a scalar or have nu = {self.config.nu} entries")
         self.engine = Engine(self.config, device)
         if isinstance(dynamics, str) and dynamics == "cartpole":
             self.engine.load_dynamics(L.DYN_CARTPOLE)
@@ -144,6 +154,8 @@ class MPPIModel:
                     raise ValueError(f"MPPIModel: {name} must be a scalar or have nu = {self.config.nu} entries")
             self.engine.set_control_bounds(None if self.u_min is None else np.broadcast_to(self.u_min, self.config.nu),
                                            None if self.u_max is None else np.broadcast_to(self.u_max, self.config.nu))
+        if self.rate_cost is not None:
+            self.engine.set_rate_cost(np.broadcast_to(self.rate_cost, self.config.nu), self.rate_anchor)
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0
@@ -171,6 +183,19 @@ class MPPIModel:
             if (lo > hi).any():
                 raise ValueError("MPPIModel: u_min must be <= u_max for every actuator")
         return lo, hi
+
+    @staticmethod
+    def _check_rate(rate_cost):
+        """rate_cost as a float32 vector (or None): finite, every entry >= 0, not all zero."""
+        if rate_cost is None:
+            return None
+        try:
+            a = np.asarray(rate_cost, dtype=np.float32).ravel()
+        except (TypeError, ValueError):
+            raise ValueError("MPPIModel: rate_cost must be a scalar or a sequence of numbers") from None
+        if a.size == 0 or not np.isfinite(a).all() or (a < 0.0).any() or not (a > 0.0).any():
+            raise ValueError("MPPIModel: rate_cost must be finite, every entry >= 0 and at least one > 0")
+        return a
 
     @property
     def device_adapt(self) -> bool:
@@ -331,6 +356,13 @@ def _stats_kw(model) -> dict:
     return {"stats": True} if getattr(model, "adapt_noise", 0.0) > 0.0 and not _device_adapt(model) else {}
 
 
+def _pass_prev_control(model, data):
+    """With the anchored rate term on, the control the environment applied last (data.ctrl) becomes the engine's
+    previous control ahead of the solve; a model without the term makes no call."""
+    if getattr(model, "rate_cost", None) is not None and getattr(model, "rate_anchor", False):
+        model.engine.set_prev_control(np.asarray(data.ctrl, np.float32).ravel())
+
+
 def _adapt(model, res):
     if getattr(model, "adapt_noise", 0.0) > 0.0 and res.status == L.MPPI_OK and not _device_adapt(model):
         model.adapt(res.stats)
@@ -341,6 +373,7 @@ def mppi_step(model: MPPIModel, data, ctx=None):
     data's real-env kinematics for the humanoid costs (env_context), as the reference reads them per call."""
     ctx = env_context(model, data) if ctx is None else ctx
     noise = model.draw_noise()
+    _pass_prev_control(model, data)
     res = model.engine.solve(_state(data), model.U_global, noise=noise, seed=model.next_seed(), ctx=ctx,
                              want_costs=True, want_weights=True, **_stats_kw(model))
     model.U_global = res.U.astype(np.float64)
@@ -353,6 +386,7 @@ def mppi_controller(model: MPPIModel, data, ctx=None):
     """mppi_step, then data.ctrl = U[:,0] and the receding-horizon shift (fill = preset's 0.1 or 0)."""
     ctx = env_context(model, data) if ctx is None else ctx
     noise = model.draw_noise()
+    _pass_prev_control(model, data)
     res = model.engine.solve(_state(data), model.U_global, noise=noise, seed=model.next_seed(), ctx=ctx,
                              want_costs=True, want_weights=True, shift=True, u0_before=model.u0_before,
                              **_stats_kw(model))

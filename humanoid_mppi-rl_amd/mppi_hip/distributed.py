@@ -243,7 +243,10 @@ def combine_k_shards(costs: np.ndarray, dU_r: np.ndarray, lam: float, norm_eps: 
     finite cost every rank raises ValueError after the MIN allreduce (collectively, so no rank is left waiting).
 
     With the control-cost term on (Engine.set_control_cost) a rank's dU_r was weighed with costs + term, so it passes
-    that sum here too: `costs + engine.control_term(1)[0]` of its shard.
+    that sum here too: `costs + engine.control_term(1)[0]` of its shard.  With the rate term on as well
+    (Engine.set_rate_cost) each rank passes costs + control term + rate term, added in float32 in this order as the
+    engine adds them: `(costs + engine.control_term(1)[0]) + engine.rate_term(1)` (the rate term depends on the
+    sample's own controls alone, so every shard computes its own; all ranks hold the same u_prev).
 
     With control bounds on (Engine.set_control_bounds) a rank's replace-mode U is np.clip of its dU_r to the box, which
     is not the weighted noise sum: K-sharding with bounds is not supported on the device; the caller projects its

@@ -276,6 +276,68 @@ class Engine:
         L.check(self.lib.mppi_bounds_eval(self._h, B, _ptr(U), _ptr(nz), _ptr(out), _ptr(counts)))
         return out, counts
 
+    # -- the control-rate cost term (mppi_set_rate_cost; mppi_hip.stats.rate_term_ref states the definitions)
+    def set_rate_cost(self, weights, anchor: bool = True):
+        """Add a penalty on the rate of the sampled controls to the costs the softmin weighs (mppi_set_rate_cost):
+        sum_u r[u] sum_t (v[u, t] - v[u, t-1])^2 with v = clamp(U + eps) the control the rollout applied and, with
+        `anchor`, v[u, -1] the control applied the step before (set_prev_control, or the u0 of the last shift solve).
+        weights: a scalar (every actuator's) or [nu], finite, >= 0, not all zero; None disables.  Works in every stream
+        form; the `costs` output stays the rollout's.  The analytic cartpole leaves its fused one-launch form while it
+        is on.  Any change destroys captured graphs; a prefetched noise is kept.  Needs nu <= 32."""
+        if weights is None:
+            L.check(self.lib.mppi_set_rate_cost(self._h, None, 0))
+            return self
+        r = np.asarray(weights, dtype=np.float32)
+        r = np.full(self.config.nu, r, np.float32) if r.ndim == 0 else np.ascontiguousarray(r).ravel()
+        if r.size != self.config.nu:
+            raise ValueError(f"set_rate_cost: weights must be a scalar or have nu = {self.config.nu} entries, "
+                             f"got {r.size}")
+        L.check(self.lib.mppi_set_rate_cost(self._h, r.ctypes.data_as(L._fp), int(bool(anchor))))
+        return self
+
+    def rate_cost(self) -> tuple[np.ndarray, bool, bool]:
+        """(weights [nu], anchor, active) of mppi_get_rate_cost; zeros and False while the term is off."""
+        r = np.empty(self.config.nu, np.float32)
+        anchor, active = ctypes.c_int(), ctypes.c_int()
+        L.check(self.lib.mppi_get_rate_cost(self._h, r.ctypes.data_as(L._fp), ctypes.byref(anchor),
+                                            ctypes.byref(active)))
+        return r, bool(anchor.value), bool(active.value)
+
+    def set_prev_control(self, u):
+        """The control applied the step before, u [B, nu] (or [nu]) -> the handle's u_prev (mppi_set_prev_control):
+        what the anchored rate term differences t = 0 against.  Data, not a setting: captured graphs stay."""
+        u = _f32(u).reshape(-1, self.config.nu)
+        L.check(self.lib.mppi_set_prev_control(self._h, u.shape[0], _ptr(u)))
+        return self
+
+    def prev_control(self, B: int = 1) -> np.ndarray:
+        """The handle's u_prev [B, nu] (mppi_get_prev_control; waits for the stream): zeros until set, then what was
+        set or the u0 of the last shift solve made with the anchored term."""
+        out = np.empty((B, self.config.nu), np.float32)
+        L.check(self.lib.mppi_get_prev_control(self._h, B, _ptr(out)))
+        return out
+
+    def rate_term(self, B: int = 1) -> np.ndarray:
+        """term [B, K] of the last solve enqueued with the term on (mppi_get_rate_term; waits for the stream) -- after
+        graph_launch the chain's last solve."""
+        term = np.empty((B, self.config.K), np.float32)
+        L.check(self.lib.mppi_get_rate_term(self._h, B, _ptr(term)))
+        return term
+
+    def rate_term_eval(self, U, noise, u_prev=None) -> np.ndarray:
+        """The term's kernel on host arrays U [B, nu, H], noise [B, nu, H, K] (as the rollout would see it: no
+        projection here) and u_prev [B, nu] (None: the handle's) with the handle's weights, anchor and ctrl_clamp ->
+        term [B, K] (mppi_rate_term_eval).  Needs the term enabled; no dynamics or cost need be loaded."""
+        c = self.config
+        U = _f32(U).reshape(-1, c.nu, c.H)
+        B = U.shape[0]
+        nz = _f32(noise).reshape(B, c.nu, c.H, c.K)
+        up = None if u_prev is None else _f32(u_prev).reshape(B, c.nu)
+        term = np.empty((B, c.K), np.float32)
+        L.check(self.lib.mppi_rate_term_eval(self._h, B, _ptr(U), _ptr(nz), None if up is None else _ptr(up),
+                                             _ptr(term)))
+        return term
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,

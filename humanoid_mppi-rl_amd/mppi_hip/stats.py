@@ -39,6 +39,14 @@ P the precision matrix of the unit-variance AR(1) row (ar1_precision).  control_
 Per-actuator control bounds (mppi_set_control_bounds; csrc/ctrl_bounds.h is the rule): ahead of the rollout the
 solve's noise becomes eps' = clip(U + eps, lo, hi) - U, element by element in float32 and only where the box binds.
 project_noise_ref is the numpy restatement: a select and one subtract, so it equals the device bit for bit.
+
+The control-rate cost term (mppi_set_rate_cost; csrc/rate_cost.h is the fp32 rule): the softmin weighs costs
+(+ control term) + rate term with
+
+    v[b, u, t, k] = clamp(U[b, u, t] + eps'[b, u, t, k])          the control the rollout applied, float32
+    rate[b, k]    = sum_u r[u] sum_t (v[u, t] - v[u, t-1])^2      v[u, -1] = u_prev[b, u] with the anchor, else t >= 1
+
+rate_term_ref is the float64 restatement.
 """
 from __future__ import annotations
 
@@ -368,3 +376,44 @@ def project_noise_ref(U, noise, lo=None, hi=None):
     counts = (below | above).sum(axis=(2, 3)).astype(np.uint32)
     out = out.astype(np.float32, copy=False)
     return (out[0], counts[0]) if single else (out, counts)
+
+
+def rate_term_ref(U, noise, r, u_prev=None, ctrl_clamp: float = 0.0):
+    """The control-rate cost term in float64 (include/mppi.h mppi_set_rate_cost; csrc/rate_cost.h): U [B, nu, H] (or
+    [nu, H]), noise [B, nu, H, K] (or [nu, H, K]) as the rollout sees it, r a scalar or [nu] (>= 0), u_prev None (no
+    anchor) or [B, nu] (or [nu]), ctrl_clamp as in the config (<= 0: none) -> term [B, K] (or [K]).
+
+        v    = float32(U + noise), then clipped to +-ctrl_clamp     formed in float32 exactly as the device forms it
+        d    = v[t] - v[t-1], v[-1] = u_prev                        t = 0 only with u_prev; float64 from here on
+        term = sum_u r[u] sum_t d^2
+
+    Every row enters: a non-finite U + noise on any row (a row with r == 0, an unanchored t = 0 and a sum the clamp
+    would have made finite included) makes its sample's term NaN, as on the device.  ValueError on shapes that do not
+    agree, or r negative, non-finite or of the wrong size."""
+    U = np.asarray(U, np.float32)
+    eps = np.asarray(noise, np.float32)
+    single = U.ndim == 2
+    if U.ndim not in (2, 3) or eps.ndim != U.ndim + 1:
+        raise ValueError("rate_term_ref: U must be [B, nu, H] (or [nu, H]) and noise [B, nu, H, K] (or [nu, H, K])")
+    if single:
+        U, eps = U[None], eps[None]
+    B, nu, H = U.shape
+    if eps.shape[:3] != (B, nu, H):
+        raise ValueError(f"rate_term_ref: noise must be [{B}, {nu}, {H}, K], got {list(eps.shape)}")
+    w = np.asarray(r, np.float64)
+    w = np.full(nu, float(w)) if w.ndim == 0 else w.ravel()
+    if w.size != nu or not (np.all(np.isfinite(w)) and np.all(w >= 0.0)):
+        raise ValueError(f"rate_term_ref: r must be {nu} finite entries >= 0")
+    clamp = float(ctrl_clamp)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = (U[..., None] + eps).astype(np.float32)
+        v = np.clip(s, np.float32(-clamp), np.float32(clamp)) if clamp > 0.0 else s
+        v = np.where(np.isfinite(s), v, np.nan).astype(np.float64)
+        if u_prev is None:
+            first = v[:, :, :1] - v[:, :, :1]  # 0, or NaN for a non-finite row
+        else:
+            up = np.asarray(u_prev, np.float32).astype(np.float64).reshape(B, nu)
+            first = v[:, :, :1] - up[:, :, None, None]
+        d = np.concatenate([first, v[:, :, 1:] - v[:, :, :-1]], axis=2)
+        term = np.einsum("u,butk->bk", w, d * d)
+    return term[0] if single else term

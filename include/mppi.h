@@ -82,7 +82,12 @@ extern "C" {
  *      mppi_bounds_eval (a per-actuator box that the sampled controls and the nominal stay inside: the solve's noise
  *      projected ahead of the rollout, U and u0 clipped behind the update); kernel name "bounds" in mppi_kernel_time.
  *      A handle that never enables them launches exactly the kernels it launched before, with the same grids and
- *      arguments. */
+ *      arguments.
+ *      Additive, version unchanged: mppi_set_rate_cost / mppi_get_rate_cost / mppi_set_prev_control /
+ *      mppi_get_prev_control / mppi_get_rate_term / mppi_rate_term_eval (a per-actuator penalty on the rate of the
+ *      sampled controls, anchored to the previously applied control, added to the costs the softmin weighs); kernel
+ *      name "rate_cost" in mppi_kernel_time.  A handle that never enables it launches exactly the kernels it launched
+ *      before, with the same grids and arguments. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -450,6 +455,70 @@ int mppi_get_bound_counts(mppi_handle* h, int B, uint32_t* counts /* [B][nu] */)
 int mppi_bounds_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
                      const float* noise_in /* [B][nu][H][K] host */, float* noise_out, uint32_t* counts);
 
+/* The control-rate (smoothness) cost term: a penalty on how fast the SAMPLED control sequence changes, added ON THE
+ * DEVICE to the costs the softmin weighs.  (AR(1) noise makes the perturbations smooth; this makes the softmin prefer
+ * smooth controls, and with the anchor it also ties the first control to the one applied the step before.)  With the
+ * term on, every solve runs one more kernel (two in its split form) between its rollout and its reduce
+ * (csrc/kernels_rate_cost.hip; one streaming pass over the solve's noise).  For solve b and sample k, with eps' the
+ * solve's noise as the rollout sees it -- after the in-place projection of mppi_set_control_bounds when bounds are on;
+ * injected noise as given -- and r[u] >= 0 per-actuator weights in cost units per squared control unit:
+ *     v[u][t]  = U[b][u][t] + eps'[b][u][t][k]       fp32, one rounding; then, when cfg.ctrl_clamp > 0, clamped to
+ *                                                    +-ctrl_clamp: the control the rollout applied
+ *     v[u][-1] = u_prev[b][u]                        only with the anchor on; used as stored, not clamped again
+ *     d        = v[u][t] - v[u][t-1]                 t = t0..H-1, t0 = 0 with the anchor, 1 without
+ *     rate [b][k] = sum_u sum_t r[u] d^2             q = r[u] * d; acc = fmaf(q, d, acc)
+ *     wcost[b][k] = (costs[b][k] + control-cost term, if on) + rate[b][k]        fp32, in this order
+ * U is the nominal the rollout perturbed, before the update.  H == 1 without the anchor gives a term that is exactly
+ * 0.  Every row enters the sum, a row with r[u] == 0 included (and, without the anchor, an actuator's t = 0, which is
+ * differenced against itself: an exact 0): a non-finite eps' on ANY row makes that sample's term, and so its wcost,
+ * non-finite and its weight 0 -- also where ctrl_clamp would have clamped an infinite control to a finite one -- and
+ * affects no other sample.  Pad lanes K..Kp get term 0 and the cost copied through.  (the fp32 rule per element is
+ * csrc/rate_cost.h; mppi_hip.stats.rate_term_ref is the float64 restatement; the sum over (u, t) is fp32 in an order
+ * fixed by the shape: bitwise repeatable, and the same whichever of the kernel's two grid forms ran -- env
+ * MPPI_RATE_COST_FORM=block|split and MPPI_RATE_COST_NT=0|1, read per launch, force a form / the nontemporal loads.)
+ * Every consumer of the solve's costs behind the rollout reads wcost, exactly as for the control-cost term: the lambda
+ * search of mppi_set_ess_target, the reduce's softmin, the `weights` output, MPPI_FLAG_STATS (its cost_* fields then
+ * describe wcost) and, through the statistics, the noise adaptation.  The `costs` output, mppi_device_buffers' dcosts,
+ * the env step, the MPPI_PREC_BF16X3 probe, the seed counter and the noise are bit for bit what they are without the
+ * term; mppi_stats_eval, mppi_lambda_eval and mppi_control_term_eval never add it.  The analytic cartpole leaves its
+ * fused one-launch form while the term is on, exactly as for the control-cost term and ESS targeting.  A K-sharded
+ * solve (mppi_hip.distributed.combine_k_shards) passes costs + control term + rate term from each rank.
+ * The previously applied control u_prev [max_batch][nu] lives on the device, per handle.  It reads as zeros until it is
+ * set or stored (the reference controllers start from ctrl = 0).  mppi_set_prev_control writes it from the host.
+ * Every solve with MPPI_FLAG_SHIFT on a handle with the term and the anchor on stores the u0 it returns there -- after
+ * the bounds' clip; the pre-update column with MPPI_FLAG_U0_BEFORE -- with one small launch behind the update and the
+ * clip and ahead of the env step, so chained solves and captured graphs anchor step i + 1 to the control step i
+ * applied with no host round trip.  A solve without MPPI_FLAG_SHIFT leaves u_prev as it is.  A stream saved as (x, U,
+ * seed counter, law, the settings, u_prev) and restored on a fresh handle continues bit for bit.
+ * mppi_set_rate_cost: r [nu] finite, every entry >= 0 and at least one > 0 enables, with anchor != 0 the anchor too;
+ * r == NULL disables.  A NaN, a negative, an infinite or an all-zero r is MPPI_E_ARG and changes nothing.  The weights
+ * travel as a kernel argument: nu > 32 is MPPI_E_UNSUPPORTED.  Any change of r or anchor, enabling and disabling
+ * included, destroys captured graphs (mppi_graph_launch returns MPPI_E_STATE until the next capture); setting the
+ * values already in effect is a no-op that keeps them.  A prefetched noise is kept: the term does not enter the noise,
+ * the key sequence is unchanged.  The feature's buffers are allocated here and in mppi_set_prev_control, none inside a
+ * solve.
+ * mppi_get_rate_cost: r [nu], *anchor (both 0 while off) and *active; each pointer may be NULL.
+ * mppi_set_prev_control: u_prev [B][nu] host -> the handle's, ordered behind the solves enqueued so far.  It is data,
+ * not a launch argument: it destroys nothing and may be called between graph launches, with the term on or off.  B
+ * beyond max_batch is MPPI_E_ARG.
+ * mppi_get_prev_control: the handle's u_prev [B][nu]; waits for the stream.
+ * mppi_get_rate_term: term [B][K] of the last solve enqueued -- after a graph launch the chain's last solve; there are
+ * no per-step slots.  Waits for the stream.  MPPI_E_STATE before any solve with the term, MPPI_E_ARG for B beyond it.
+ * mppi_rate_term_eval: the same kernel on host arrays U [B][nu][H], noise [B][nu][H][K] and u_prev [B][nu] (NULL: the
+ * handle's) with the handle's r, anchor and cfg.ctrl_clamp: the entry that needs no rollout.  It does not project:
+ * the caller passes the noise as the rollout would see it.  Needs only mppi_create and the term enabled (MPPI_E_STATE
+ * otherwise).  It goes through the handle's staging noise: a prefetched noise is dropped as by mppi_stats_eval (key
+ * sequence unchanged); its output has its own slot, so the last solve's term stays readable, and the resident U and
+ * the handle's u_prev are untouched. */
+int mppi_set_rate_cost(mppi_handle* h, const float* r /* [nu] or NULL */, int anchor);
+int mppi_get_rate_cost(mppi_handle* h, float* r /* [nu] */, int* anchor, int* active);
+int mppi_set_prev_control(mppi_handle* h, int B, const float* u_prev /* [B][nu] host */);
+int mppi_get_prev_control(mppi_handle* h, int B, float* u_prev); /* waits for the stream */
+int mppi_get_rate_term(mppi_handle* h, int B, float* term /* [B][K] */); /* last solve enqueued; after a graph launch the chain's last */
+int mppi_rate_term_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
+                        const float* noise /* [B][nu][H][K] host */, const float* u_prev /* [B][nu] or NULL: the handle's */,
+                        float* term /* [B][K] */);
+
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
  *     eps_m2 [b][u] = 1/H     sum_{t=0..H-1} sum_k w_k eps[b][u][t][k]^2
@@ -502,7 +571,8 @@ int mppi_sync(mppi_handle* h);
  * enable != 0 starts accumulating; mppi_kernel_times returns {count, total_ms} per kernel
  * name. names: "noise", "rollout", "reduce", "update", "stats" (the launches of MPPI_FLAG_STATS), "lambda" (the
  * search of mppi_set_ess_target), "ctrl_cost" (the launches of mppi_set_control_cost, counted as one), "bounds" (the
- * launches of mppi_set_control_bounds ahead of the rollout and behind the update, counted as one per solve). */
+ * launches of mppi_set_control_bounds ahead of the rollout and behind the update, counted as one per solve),
+ * "rate_cost" (the term launches of mppi_set_rate_cost and the store of u_prev, counted as one per solve). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
