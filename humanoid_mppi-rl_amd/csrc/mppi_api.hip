@@ -13,6 +13,7 @@
 
 #include "costs.h"
 #include "ctrl_bounds.h"  // ctrl_bounds_valid
+#include "elite_select.h"  // (the rule of mppi_set_elites)
 #include "ess_target.h"  // EssTarget
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
@@ -54,10 +55,11 @@ enum KernelId {
   kCtrl = 6,
   kBounds = 7,
   kRate = 8,
-  kNumKernels = 9
+  kElites = 9,
+  kNumKernels = 10
 };
 const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost",
-                                         "bounds", "rate_cost"};
+                                         "bounds", "rate_cost", "elites"};
 
 struct PendingEvt {
   int id;
@@ -196,6 +198,18 @@ struct mppi_handle {
   float* d_uprev = nullptr;       // [2][max_batch][nu]
   int rate_B = 0;                 // batch of the last solve / graph launch with the term (0: none ran)
   bool graph_rate = false;        // the captured graph carries the term
+  // elite truncation (mppi_set_elites; elite_select.h, kernels_elite.hip).  While elite_n > 0 every solve runs
+  // elite_select_kernel behind its rollout and the cost terms and ahead of everything that weighs its costs; the lambda
+  // search, the reduce and the statistics then read d_elite_wcost = the end of the wcost chain on the elite set, +inf
+  // elsewhere.  All buffers are allocated by mppi_set_elites, two slots each: slot 0 the last solve's, slot 1
+  // mppi_elites_eval's.
+  int elite_n = 0;                   // n_elite (0: off)
+  float* d_elite_wcost = nullptr;    // [2][max_batch][Kp]
+  int32_t* d_elite_idx = nullptr;    // [2][max_batch][elite_n]
+  int32_t* d_elite_count = nullptr;  // [2][max_batch]
+  float* d_elite_tau = nullptr;      // [2][max_batch]
+  int elite_B = 0;                   // batch of the last solve / graph launch with elites (0: none ran)
+  bool graph_elite = false;          // the captured graph carries the selection
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -322,7 +336,8 @@ void mppi_destroy(mppi_handle* h) {
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
                   h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist,
                   h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U, h->d_bcounts,
-                  h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev};
+                  h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev,
+                  h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -833,6 +848,14 @@ static hipError_t enqueue_rate(mppi_handle* h, int B, const float* U, const floa
   return launch_rate_cost(ra, h->stream);
 }
 
+// The elite selection of B solves on `costs` [B][Kp] into output slot `slot` (0: a solve, 1: mppi_elites_eval).
+static hipError_t enqueue_elite(mppi_handle* h, int B, const float* costs, int slot) {
+  const mppi_config& c = h->cfg;
+  const size_t ob = (size_t)slot * c.max_batch;
+  return launch_elite_select(costs, B, c.K, h->Kp, h->elite_n, h->d_elite_wcost + ob * h->Kp,
+                             h->d_elite_idx + ob * h->elite_n, h->d_elite_count + ob, h->d_elite_tau + ob, h->stream);
+}
+
 // Validate one solve request against the handle.
 static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if (!h || !io) return fail(MPPI_E_ARG, "mppi_solve: null argument");
@@ -929,7 +952,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   a.lambda_dev = lam;
   const bool ctrl = h->ctrl_gamma > 0.0f;  // the control-cost term: the softmin weighs d_wcost = costs + term (below)
   const bool rate = h->rate_on;  // the rate term: the softmin weighs d_rate_wcost = (costs [+ control term]) + rate term
-  const bool cart_unfused = (lam || ctrl || rate) && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  const bool elite = h->elite_n > 0;  // elite truncation: the softmin weighs d_elite_wcost, the chain's end on the elite set
+  const bool cart_unfused = (lam || ctrl || rate || elite) && h->dyn_kind == MPPI_DYN_CARTPOLE;
   // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths); the cartpole's unfused
   // rollout carries no stamp
   a.kclock = (h->kclock && a.seed_ctr && !cart_unfused) ? h->d_kclock : nullptr;
@@ -1006,7 +1030,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   } else {
     // (a targeting cartpole too: its fused epilogue forms the softmin partials with lambda before all costs exist, so
     // it runs the unfused rollout of the env step, a.part == nullptr, then the search and reduce_kernel: 3 launches;
-    // and a cartpole with the control-cost or the rate term, whose epilogue would weigh costs the term has not reached yet)
+    // and a cartpole with the control-cost or the rate term, whose epilogue would weigh costs the term has not reached
+    // yet, or with elites, whose selection needs every cost of the solve)
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
     h->rollout_kernel = g_rollout_kernel;
     SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
@@ -1026,6 +1051,13 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       HIP_TRY(timed(h, kRate, [&] { return enqueue_rate(h, B, a.U, a.noise, h->d_uprev, wcost, 0); }));
       wcost = h->d_rate_wcost;
       r.costs = h->d_rate_wcost;
+    }
+    if (elite) {
+      // elite truncation, behind the terms (it selects on what the softmin would otherwise weigh) and ahead of the lambda
+      // search: the search, the reduce and the statistics see the cost on the elite set and +inf elsewhere
+      HIP_TRY(timed(h, kElites, [&] { return enqueue_elite(h, B, wcost, 0); }));
+      wcost = h->d_elite_wcost;
+      r.costs = h->d_elite_wcost;
     }
     if (lam)
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
@@ -1192,6 +1224,7 @@ static void note_stats(mppi_handle* h, int B, int flags) {
   if (h->ctrl_gamma > 0.0f) h->ctrl_B = B;
   if (h->bounds_on) h->bounds_B = B;
   if (h->rate_on) h->rate_B = B;
+  if (h->elite_n > 0) h->elite_B = B;
 }
 
 // MPPI_FLAG_CHAIN: one solve of a graph stream, launched on the stream (rollout -> reduce_kernel<GEN>, or with
@@ -1496,6 +1529,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->graph_ctrl = h->ctrl_gamma > 0.0f;
   h->graph_bounds = h->bounds_on;
   h->graph_rate = h->rate_on;
+  h->graph_elite = h->elite_n > 0;
   h->graph_B = B;
   h->graph_n = n_solves;
   h->graph_seed = seed;
@@ -1527,6 +1561,7 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
   if (h->graph_ctrl) h->ctrl_B = h->graph_B;  // (no per-step slots: the chain's last solve)
   if (h->graph_bounds) h->bounds_B = h->graph_B;  // (likewise)
   if (h->graph_rate) h->rate_B = h->graph_B;      // (likewise)
+  if (h->graph_elite) h->elite_B = h->graph_B;    // (likewise)
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2085,6 +2120,94 @@ int mppi_rate_term_eval(mppi_handle* h, int B, const float* U, const float* nois
   }));
   HIP_TRY(hipStreamSynchronize(s));
   return copy_rate(h, B, 1, term);
+}
+
+int mppi_set_elites(mppi_handle* h, int n_elite) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_elites: null handle");
+  const mppi_config& c = h->cfg;
+  if (n_elite < 0 || n_elite > c.K) return fail(MPPI_E_ARG, "mppi_set_elites: n_elite must be in [0, K] (0 disables)");
+  if (n_elite == h->elite_n) return MPPI_OK;  // no change: captured graphs stay
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state: the captured graphs hold n_elite (or the selection's absence) in their launches, and the set's rows
+  // have n_elite entries; everything in flight finishes first.  A prefetched noise is kept: the selection does not
+  // enter the noise, the key sequence is unchanged
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (n_elite > 0) {  // the feature's buffers (every entry is written before it is read); the set's by its row length
+    const size_t nb = (size_t)2 * c.max_batch;
+    int32_t* ni = nullptr;
+    hipError_t e = hipMalloc(&ni, nb * n_elite * 4);
+    float *w = nullptr, *t = nullptr;
+    int32_t* cn = nullptr;
+    if (!h->d_elite_wcost) {
+      if (e == hipSuccess) e = hipMalloc(&w, nb * h->Kp * 4);
+      if (e == hipSuccess) e = hipMalloc(&cn, nb * 4);
+      if (e == hipSuccess) e = hipMalloc(&t, nb * 4);
+    }
+    if (e != hipSuccess) {
+      for (void* x : {(void*)ni, (void*)w, (void*)cn, (void*)t})
+        if (x) (void)hipFree(x);
+      return fail(MPPI_E_HIP, std::string("mppi_set_elites: ") + hipGetErrorString(e));
+    }
+    if (h->d_elite_idx) (void)hipFree(h->d_elite_idx);
+    h->d_elite_idx = ni;
+    if (w) {
+      h->d_elite_wcost = w;
+      h->d_elite_count = cn;
+      h->d_elite_tau = t;
+    }
+  }
+  for (hipGraphExec_t& g : h->graph_exec)
+    if (g) {
+      HIP_TRY(hipGraphExecDestroy(g));
+      g = nullptr;
+    }
+  h->elite_n = n_elite;
+  h->elite_B = 0;  // the last set had another row length: none to read until the next solve
+  return MPPI_OK;
+}
+
+int mppi_get_elites(mppi_handle* h, int* n_elite) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_elites: null handle");
+  if (n_elite) *n_elite = h->elite_n;
+  return MPPI_OK;
+}
+
+// slot `slot` of the elite set -> host (the stream is idle); each pointer may be nullptr
+static int copy_elites(mppi_handle* h, int B, int slot, int32_t* idx, int32_t* count, float* tau, float* ecost) {
+  const size_t ob = (size_t)slot * h->cfg.max_batch, K = (size_t)h->cfg.K, Kp = (size_t)h->Kp;
+  if (idx)
+    HIP_TRY(hipMemcpy(idx, h->d_elite_idx + ob * h->elite_n, (size_t)B * h->elite_n * 4, hipMemcpyDeviceToHost));
+  if (count) HIP_TRY(hipMemcpy(count, h->d_elite_count + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (tau) HIP_TRY(hipMemcpy(tau, h->d_elite_tau + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (ecost)
+    HIP_TRY(hipMemcpy2D(ecost, K * 4, h->d_elite_wcost + ob * Kp, Kp * 4, K * 4, B, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_get_elite_set(mppi_handle* h, int B, int32_t* idx, int32_t* count, float* tau) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_elite_set: null handle");
+  if (h->elite_B == 0 || h->elite_n == 0)
+    return fail(MPPI_E_STATE, "mppi_get_elite_set: no solve with the current elites setting has run on the handle");
+  if (B < 1 || B > h->elite_B) return fail(MPPI_E_ARG, "mppi_get_elite_set: B beyond the batch of the last solve with elites");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_elites(h, B, 0, idx, count, tau, nullptr);
+}
+
+int mppi_elites_eval(mppi_handle* h, int B, const float* costs, int32_t* idx, int32_t* count, float* tau,
+                     float* ecost) {
+  if (!h || !costs) return fail(MPPI_E_ARG, "mppi_elites_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_elites_eval: B out of range [1, max_batch]");
+  if (h->elite_n == 0) return fail(MPPI_E_STATE, "mppi_elites_eval: call mppi_set_elites first");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp;
+  // through the staging costs, as mppi_lambda_eval (the pads keep whatever they hold: the kernel never counts them)
+  HIP_TRY(hipMemcpy2DAsync(h->d_costs, Kp * 4, costs, K * 4, K * 4, B, hipMemcpyHostToDevice, s));
+  HIP_TRY(timed(h, kElites, [&] { return enqueue_elite(h, B, h->d_costs, 1); }));  // the evaluation's own slot
+  HIP_TRY(hipStreamSynchronize(s));
+  return copy_elites(h, B, 1, idx, count, tau, ecost);
 }
 
 // slot `slot` of the diagnostics' buffers -> host (the stream is idle)

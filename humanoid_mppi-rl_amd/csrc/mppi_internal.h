@@ -338,6 +338,12 @@ hipError_t launch_stats(const StatsArgs& a, hipStream_t stream);  // cost part, 
 // the target effective sample size (the rule: ess_target.h); one block per solve, read-only on the costs, capturable
 hipError_t launch_lambda_search(const float* costs, int B, int K, int Kp, const EssTarget& s, float cfg_lambda,
                                 float* lambda_out, hipStream_t stream);
+// kernels_elite.hip: elite truncation (mppi_set_elites; the rule: elite_select.h).  Per solve b, from costs [B][Kp]:
+// ecost [B][Kp] = the cost on the n_elite best finite samples (ties by ascending k), +inf elsewhere and on the pads;
+// idx [B][n_elite] the set in ascending k, -1 behind its count [B]; tau [B] its threshold.  One block per solve, one
+// launch, read-only on the costs, capturable.  1 <= n_elite <= K
+hipError_t launch_elite_select(const float* costs, int B, int K, int Kp, int n_elite, float* ecost, int32_t* idx,
+                               int32_t* count, float* tau, hipStream_t stream);
 // kernels_ctrl_cost.hip: the control-cost term (mppi_set_control_cost; the rule for lin: control_cost.h), by value
 // like SolveArgs: read-only on the solve's U, noise and costs, so the launches can sit in a captured graph.
 struct CtrlLaw {

@@ -533,6 +533,67 @@ function rate_term_eval(c::Controller, U, noise; u_prev = nothing)
 end
 
 """
+    set_elites!(c, n_elite)
+
+Weigh only the `n_elite` best samples of each solve (mppi_set_elites): the selection runs on the device, exact, ties
+admitted by ascending sample index; every other sample's weight is 0.  `n_elite` in 1:K enables, 0 disables.  With a
+large lambda this is CEM's elite mean, with `set_ess_target!` a scale-free softmin over the elites.  Any change
+destroys captured graphs; a prefetched noise is kept.
+"""
+function set_elites!(c::Controller, n_elite::Integer)
+    check(ccall((:mppi_set_elites, LIB), Cint, (Ptr{Cvoid}, Cint), c.handle, n_elite))
+    return c
+end
+
+"""
+    elites(c) -> Int
+
+`n_elite` of `set_elites!` (mppi_get_elites); 0 while off.
+"""
+function elites(c::Controller)
+    n = Ref{Cint}(0)
+    check(ccall((:mppi_get_elites, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), c.handle, n))
+    return Int(n[])
+end
+
+"""
+    elite_set(c) -> (idx::Vector{Int32}, tau::Float32)
+
+The elite set of the last solve made with elites on (mppi_get_elite_set; waits for the stream): its members as 1-based
+sample indices in ascending order, and the threshold cost.
+"""
+function elite_set(c::Controller)
+    n = elites(c)
+    idx = fill(Int32(-1), max(n, 1))
+    count, tau = Ref{Int32}(0), Ref{Float32}(0)
+    GC.@preserve idx check(ccall((:mppi_get_elite_set, LIB), Cint,
+                                 (Ptr{Cvoid}, Cint, Ptr{Int32}, Ref{Int32}, Ref{Float32}), c.handle, 1, pointer(idx),
+                                 count, tau))
+    return (idx[1:count[]] .+ Int32(1), tau[])
+end
+
+"""
+    elites_eval(c, costs) -> (idx::Vector{Int32}, tau::Float32, ecost::Vector{Float32})
+
+The selection kernel on `costs` (length K; ties, NaN and infinities allowed) with the handle's `n_elite`
+(mppi_elites_eval): the members as 1-based indices, the threshold, and the costs with `Inf32` off the set.  Needs
+elites enabled.
+"""
+function elites_eval(c::Controller, costs)
+    cs = Float32.(vec(collect(costs)))
+    length(cs) == c.cfg.K || throw(ArgumentError("costs must have K = $(c.cfg.K) entries"))
+    n = elites(c)
+    idx = fill(Int32(-1), max(n, 1))
+    ecost = zeros(Float32, c.cfg.K)
+    count, tau = Ref{Int32}(0), Ref{Float32}(0)
+    GC.@preserve cs idx ecost check(ccall((:mppi_elites_eval, LIB), Cint,
+                                          (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Int32}, Ref{Int32}, Ref{Float32},
+                                           Ptr{Float32}), c.handle, 1, pointer(cs), pointer(idx), count, tau,
+                                          pointer(ecost)))
+    return (idx[1:count[]] .+ Int32(1), tau[], ecost)
+end
+
+"""
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 
 The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and

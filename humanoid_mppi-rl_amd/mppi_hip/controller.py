@@ -77,6 +77,9 @@ class MPPIModel:
               weighs (Engine.set_rate_cost).  With rate_anchor (default) the first control is differenced against the
               control the environment applied last: mppi_step / mppi_controller pass data.ctrl to the engine before
               each solve.  None (default): no term.
+    n_elite:  weigh only the n_elite best samples of each solve (Engine.set_elites), an int in 1..K: with a large
+              lambda_ CEM's elite mean, with ess_target a scale-free softmin over the elites.  0 (default): every
+              sample is weighed.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
@@ -84,7 +87,7 @@ class MPPIModel:
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
                  lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, rate_cost=None,
-                 rate_anchor: bool = True, **overrides):
+                 rate_anchor: bool = True, n_elite: int = 0, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -103,10 +106,15 @@ class MPPIModel:
         self.u_min, self.u_max = self._check_bounds(u_min, u_max)
         self.rate_cost = self._check_rate(rate_cost)
         self.rate_anchor = bool(rate_anchor)
+        if isinstance(n_elite, bool) or not isinstance(n_elite, (int, np.integer)) or n_elite < 0:
+            raise ValueError("MPPIModel: n_elite must be an int in 1..K (0: off)")
+        self.n_elite = int(n_elite)
         self.preset = preset
         self.body_ids = dict(HUMANOID_BODY_IDS if body_ids is None else body_ids)
         self.u0_before = bool(u0_before)
         self.config = Config.preset(preset, precision=precision, **overrides)
+        if self.n_elite > self.config.K:
+            raise ValueError(f"MPPIModel: n_elite must be an int in 1..K = {self.config.K} (0: off)")
         if self.rate_cost is not None and self.rate_cost.size not in (1, self.config.nu):
             raise ValueError(f"MPPIModel: rate_cost must be a scalar or have nu = {self.config.nu} entries")
         self.engine = Engine(self.config, device)
@@ -156,6 +164,8 @@ class MPPIModel:
                                            None if self.u_max is None else np.broadcast_to(self.u_max, self.config.nu))
         if self.rate_cost is not None:
             self.engine.set_rate_cost(np.broadcast_to(self.rate_cost, self.config.nu), self.rate_anchor)
+        if self.n_elite > 0:
+            self.engine.set_elites(self.n_elite)
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0

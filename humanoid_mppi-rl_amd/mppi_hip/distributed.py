@@ -248,6 +248,11 @@ def combine_k_shards(costs: np.ndarray, dU_r: np.ndarray, lam: float, norm_eps: 
     engine adds them: `(costs + engine.control_term(1)[0]) + engine.rate_term(1)` (the rate term depends on the
     sample's own controls alone, so every shard computes its own; all ranks hold the same u_prev).
 
+    With elites on (Engine.set_elites) a rank's dU_r was weighed with the masked costs, so it passes those here:
+    `engine.elites_eval(sum)[3][0]`, the ecost of the sum it would otherwise pass (+inf off the set: weight 0 here
+    too).  The elites are then per rank, n_elite of each shard, not a global set; a global selection across ranks is
+    not supported.
+
     With control bounds on (Engine.set_control_bounds) a rank's replace-mode U is np.clip of its dU_r to the box, which
     is not the weighted noise sum: K-sharding with bounds is not supported on the device; the caller projects its
     noise itself (stats.project_noise_ref), injects it into unbounded shard engines and clips the combined U on the

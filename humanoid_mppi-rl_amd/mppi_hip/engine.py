@@ -338,6 +338,46 @@ class Engine:
                                              _ptr(term)))
         return term
 
+    # -- elite truncation (mppi_set_elites; mppi_hip.stats.elite_select_ref states the rule)
+    def set_elites(self, n_elite: int):
+        """Weigh only the n_elite best samples of each solve (mppi_set_elites): the selection runs on the device behind
+        the rollout and the cost terms, exact and with ties admitted by ascending k; every other sample's weight is 0.
+        n_elite in 1..K enables, 0 disables.  n_elite with a large lambda is CEM's elite mean, with set_ess_target a
+        scale-free softmin over the elites, n_elite = K today's MPPI.  Works in every stream form; the `costs` output
+        stays the rollout's.  The analytic cartpole leaves its fused one-launch form while it is on.  Any change
+        destroys captured graphs; a prefetched noise is kept."""
+        L.check(self.lib.mppi_set_elites(self._h, int(n_elite)))
+        return self
+
+    def elites(self) -> int:
+        """n_elite of mppi_get_elites; 0 while off."""
+        n = ctypes.c_int()
+        L.check(self.lib.mppi_get_elites(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def elite_set(self, B: int = 1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(idx [B, n_elite] int32 in ascending k, -1 behind count; count [B]; tau [B]) of the last solve enqueued with
+        elites (mppi_get_elite_set; waits for the stream) -- after graph_launch the chain's last solve."""
+        n = self.elites()
+        idx = np.empty((B, max(n, 1)), np.int32)
+        count = np.empty(B, np.int32)
+        tau = np.empty(B, np.float32)
+        L.check(self.lib.mppi_get_elite_set(self._h, B, _ptr(idx), _ptr(count), _ptr(tau)))
+        return idx, count, tau
+
+    def elites_eval(self, costs) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """The selection kernel on host costs [B, K] (or [K]; ties, NaN and +-inf allowed) with the handle's n_elite ->
+        (idx [B, n_elite], count [B], tau [B], ecost [B, K]) (mppi_elites_eval).  Needs elites enabled; no dynamics or
+        cost need be loaded."""
+        costs = _f32(costs).reshape(-1, self.config.K)
+        B, n = costs.shape[0], self.elites()
+        idx = np.empty((B, max(n, 1)), np.int32)
+        count = np.empty(B, np.int32)
+        tau = np.empty(B, np.float32)
+        ecost = np.empty((B, self.config.K), np.float32)
+        L.check(self.lib.mppi_elites_eval(self._h, B, _ptr(costs), _ptr(idx), _ptr(count), _ptr(tau), _ptr(ecost)))
+        return idx, count, tau, ecost
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,

@@ -47,6 +47,11 @@ The control-rate cost term (mppi_set_rate_cost; csrc/rate_cost.h is the fp32 rul
     rate[b, k]    = sum_u r[u] sum_t (v[u, t] - v[u, t-1])^2      v[u, -1] = u_prev[b, u] with the anchor, else t >= 1
 
 rate_term_ref is the float64 restatement.
+
+Elite truncation (mppi_set_elites; csrc/elite_select.h is the rule): of the finite costs the softmin would weigh, only
+the n_elite lowest keep their cost, ordered by (cost, k) -- ties at the threshold go to the lower k, -0.0 equals +0.0 --
+and every other sample's becomes +inf.  elite_select_ref is the numpy restatement, a stable argsort: it equals the
+device exactly.
 """
 from __future__ import annotations
 
@@ -417,3 +422,41 @@ def rate_term_ref(U, noise, r, u_prev=None, ctrl_clamp: float = 0.0):
         d = np.concatenate([first, v[:, :, 1:] - v[:, :, :-1]], axis=2)
         term = np.einsum("u,butk->bk", w, d * d)
     return term[0] if single else term
+
+
+def elite_select_ref(costs, n_elite: int):
+    """Elite truncation (include/mppi.h mppi_set_elites; csrc/elite_select.h): costs [B, K] (or [K]) float32, the costs
+    the softmin would otherwise weigh -> (idx [B, n_elite] int32, count [B] int32, tau [B] float32, ecost [B, K] float32)
+    (or the row's own for a [K] input).
+
+        F     = the finite costs, m = min(n_elite, |F|)
+        E     = the first m of F in a STABLE ascending sort: cost first, the lower k on equal cost (-0.0 == +0.0)
+        idx   = E in ascending k, -1 behind it;  count = m
+        tau   = the m-th smallest cost (+ 0.0, so a zero reads +0.0), +inf when m == 0
+        ecost = the cost bit for bit on E, +inf elsewhere
+
+    ValueError unless 1 <= n_elite <= K."""
+    c = np.asarray(costs, np.float32)
+    single = c.ndim == 1
+    if c.ndim not in (1, 2):
+        raise ValueError("elite_select_ref: costs must be [B, K] or [K]")
+    c = c[None] if single else c
+    B, K = c.shape
+    n_elite = int(n_elite)
+    if not 1 <= n_elite <= K:
+        raise ValueError(f"elite_select_ref: n_elite must be in 1..K = {K}")
+    idx = np.full((B, n_elite), -1, np.int32)
+    count = np.zeros(B, np.int32)
+    tau = np.full(B, np.inf, np.float32)
+    ecost = np.full((B, K), np.inf, np.float32)
+    for b in range(B):
+        fin = np.flatnonzero(np.isfinite(c[b]))
+        order = fin[np.argsort(c[b, fin], kind="stable")]  # (-0.0 < +0.0 is false: equal, the lower k first)
+        m = min(n_elite, fin.size)
+        members = np.sort(order[:m])
+        idx[b, :m] = members
+        count[b] = m
+        if m:
+            tau[b] = c[b, order[m - 1]] + np.float32(0.0)
+        ecost[b, members] = c[b, members]
+    return (idx[0], count[0], tau[0], ecost[0]) if single else (idx, count, tau, ecost)

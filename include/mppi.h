@@ -87,6 +87,10 @@ extern "C" {
  *      mppi_get_prev_control / mppi_get_rate_term / mppi_rate_term_eval (a per-actuator penalty on the rate of the
  *      sampled controls, anchored to the previously applied control, added to the costs the softmin weighs); kernel
  *      name "rate_cost" in mppi_kernel_time.  A handle that never enables it launches exactly the kernels it launched
+ *      before, with the same grids and arguments.
+ *      Additive, version unchanged: mppi_set_elites / mppi_get_elites / mppi_get_elite_set / mppi_elites_eval (elite
+ *      truncation: the softmin weighs only the n_elite best samples of each solve, selected on the device); kernel
+ *      name "elites" in mppi_kernel_time.  A handle that never enables it launches exactly the kernels it launched
  *      before, with the same grids and arguments. */
 #define MPPI_ABI_VERSION 4
 
@@ -519,6 +523,52 @@ int mppi_rate_term_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host
                         const float* noise /* [B][nu][H][K] host */, const float* u_prev /* [B][nu] or NULL: the handle's */,
                         float* term /* [B][K] */);
 
+/* Elite truncation: the softmin weighs only the n_elite best samples of each solve, selected ON THE DEVICE between the
+ * rollout and the reduce -- the ingredient that separates MPPI from the CEM / iCEM family: n_elite with a large lambda
+ * is CEM's elite mean, n_elite with mppi_set_ess_target a scale-free softmin over the elites, n_elite = K today's
+ * MPPI.  With elites on, every solve runs one more kernel (csrc/kernels_elite.hip; one block per solve, an exact
+ * radix selection on the costs held in registers) behind its rollout and the cost terms and ahead of the lambda search.
+ * For solve b, with c[0..K) the costs the softmin would otherwise weigh -- costs, + the control-cost term if on, + the
+ * rate term if on, added in fp32 in this order:
+ *     F = {k : c_k finite}, n = |F|                  NaN, +inf and -inf are not finite
+ *     m = min(n_elite, n)
+ *     E = the first m samples of F ordered by (c_k, k): cost first, the lower index on equal cost; -0.0 and +0.0
+ *         compare equal, denormals order by value (nothing is flushed).  E has exactly m members: of the samples that
+ *         tie at the threshold, those with the lowest k are admitted
+ *     tau = the m-th smallest cost (a zero reads +0.0), +inf when n == 0
+ *     ecost[b][k] = c_k bit for bit on E, +inf elsewhere (non-finite inputs and the pad lanes K..Kp included)
+ *     idx[b][0..m) = the members of E in ascending k, idx[b][m..n_elite) = -1;  count[b] = m
+ * (the rule is csrc/elite_select.h, host + device; mppi_hip.stats.elite_select_ref is the numpy restatement.  All of
+ * it is integer work on the costs' bits: exact, bitwise repeatable, no atomics on global memory.)
+ * Every consumer of the solve's costs behind the rollout reads ecost, exactly as for the control-cost and rate terms:
+ * the lambda search of mppi_set_ess_target (its n becomes m), the reduce's softmin, the `weights` output (exactly 0 off
+ * the set), MPPI_FLAG_STATS (n_finite becomes m, its cost_* fields describe the elites; k_best, the lowest k attaining
+ * the minimum, is always elite) and, through the statistics, the noise adaptation.  With n_elite >= n the set of
+ * weighted samples is what it is without the feature; n == 0 still ends in MPPI_E_NONFINITE.  The `costs` output,
+ * mppi_device_buffers' dcosts, the control and rate terms' read-outs, the env step, the MPPI_PREC_BF16X3 probe, the seed
+ * counter and the noise are bit for bit what they are without elites; mppi_stats_eval, mppi_lambda_eval and the terms'
+ * evaluations never select.  The analytic cartpole leaves its fused one-launch form while elites are on, exactly as for
+ * the cost terms and ESS targeting.  A K-sharded solve (mppi_hip.distributed.combine_k_shards) passes each rank's
+ * masked costs: the elites are then per rank, n_elite of each shard, not a global set.
+ * mppi_set_elites: n_elite in 1..K enables, 0 disables; anything else is MPPI_E_ARG and changes nothing.  Any change
+ * destroys captured graphs (mppi_graph_launch returns MPPI_E_STATE until the next capture); setting the value already
+ * in effect is a no-op that keeps them.  A prefetched noise is kept: the selection does not enter the noise, the key
+ * sequence is unchanged.  The feature's buffers are allocated here, none inside a solve.
+ * mppi_get_elites: *n_elite, 0 while off.
+ * mppi_get_elite_set: idx [B][n_elite], count [B] and tau [B] of the last solve enqueued -- after a graph launch the
+ * chain's last solve; there are no per-step slots.  Each pointer may be NULL.  Waits for the stream.  MPPI_E_STATE
+ * before any solve with the n_elite in effect, MPPI_E_ARG for B beyond that solve.
+ * mppi_elites_eval: the same kernel on host costs [B][K] with the handle's n_elite: the entry that needs no rollout.
+ * Each output may be NULL.  Needs only mppi_create and elites enabled (MPPI_E_STATE otherwise).  It goes through the
+ * handle's staging costs, as mppi_lambda_eval does; its outputs have their own slot, so the last solve's set stays
+ * readable. */
+int mppi_set_elites(mppi_handle* h, int n_elite);
+int mppi_get_elites(mppi_handle* h, int* n_elite);
+int mppi_get_elite_set(mppi_handle* h, int B, int32_t* idx /* [B][n_elite] */, int32_t* count /* [B] */,
+                       float* tau /* [B] */); /* last solve enqueued; after a graph launch the chain's last */
+int mppi_elites_eval(mppi_handle* h, int B, const float* costs /* [B][K] host */, int32_t* idx /* [B][n_elite] */,
+                     int32_t* count /* [B] */, float* tau /* [B] */, float* ecost /* [B][K] */);
+
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
  *     eps_m2 [b][u] = 1/H     sum_{t=0..H-1} sum_k w_k eps[b][u][t][k]^2
@@ -572,7 +622,8 @@ int mppi_sync(mppi_handle* h);
  * name. names: "noise", "rollout", "reduce", "update", "stats" (the launches of MPPI_FLAG_STATS), "lambda" (the
  * search of mppi_set_ess_target), "ctrl_cost" (the launches of mppi_set_control_cost, counted as one), "bounds" (the
  * launches of mppi_set_control_bounds ahead of the rollout and behind the update, counted as one per solve),
- * "rate_cost" (the term launches of mppi_set_rate_cost and the store of u_prev, counted as one per solve). */
+ * "rate_cost" (the term launches of mppi_set_rate_cost and the store of u_prev, counted as one per solve), "elites"
+ * (the selection of mppi_set_elites). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
