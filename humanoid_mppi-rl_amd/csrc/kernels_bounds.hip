@@ -126,11 +126,7 @@ __global__ __launch_bounds__(256) void bounds_clip_kernel(BoundsArgs a, float* U
 
 // MPPI_BOUNDS_NT=0|1 (read per launch; an A/B and test knob): force the cached / the nontemporal loads of the
 // projection; default: nontemporal above launch_reduce's 128 MB cut (below it the rollout behind finds the noise cached)
-static int bounds_nt_knob() {
-  const char* e = std::getenv("MPPI_BOUNDS_NT");
-  if (!e || (e[0] != '0' && e[0] != '1') || e[1] != '\0') return -1;
-  return e[0] - '0';
-}
+static int bounds_nt_knob() { return env_flag("MPPI_BOUNDS_NT"); }
 
 // MPPI_BOUNDS_STORE=quad|line (read per launch; an A/B and test knob): force one store form of the projection
 static int bounds_store_knob() {

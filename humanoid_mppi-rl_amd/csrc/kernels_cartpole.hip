@@ -232,7 +232,7 @@ __device__ void cartpole_finish(const SolveArgs& a, int b, int k, float cst, flo
   }
   if (tid == 0) {
     if (b == 0 && a.seed_bump) atomicAdd(a.seed_bump, 1ull);  // plain solves: the next solve's noise key
-    // sticky non-finite flag: set here, cleared by the host when it reads it (mppi_api.hip::read_status)
+    // sticky non-finite flag: set here, cleared by the host when it reads it (mppi_api.hip::report_status)
     if (!(beta < INFINITY)) atomicOr(a.status, 1u);
   }
 }

@@ -296,11 +296,7 @@ size_t stats_part_floats(int B, int nu, int H, int Kp) {
 
 // MPPI_STATS_FORM=direct|seg (read per launch; an A/B and test knob): force one form of stats_moment_kernel; default:
 // seg when the direct form's grid has fewer blocks than the device has CUs
-static int stats_knob() {
-  const char* e = std::getenv("MPPI_STATS_FORM");
-  if (!e) return 0;
-  return std::strcmp(e, "direct") == 0 ? 1 : (std::strcmp(e, "seg") == 0 ? 2 : 0);
-}
+static int stats_knob() { return env_choice("MPPI_STATS_FORM", "direct", "seg"); }
 
 hipError_t launch_stats(const StatsArgs& a, hipStream_t stream) {
   hipLaunchKernelGGL(stats_cost_kernel, dim3(a.B), dim3(kStatsCostThreads), 0, stream, a);

@@ -18,6 +18,7 @@
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
 #include "rate_cost.h"  // rate_cost_valid
+#include "term_cells.h"  // term_part_floats
 #include "noise_adapt.h"  // NoiseAdapt
 #include "noise_model.h"  // ar1_innovation_scale
 
@@ -67,6 +68,18 @@ struct PendingEvt {
   int n;  // what the group adds to the kernel's count (0: its time joins a group already counted)
 };
 
+// Which options a solve carries (solve_opts: from the handle's settings and the solve's flags).  enqueue_solve
+// launches by it, note_ran records by it, and a captured graph keeps the one it was captured under.
+struct SolveOpts {
+  bool stats = false;   // MPPI_FLAG_STATS
+  bool adapt = false;   // mppi_set_noise_adapt
+  bool ess = false;     // mppi_set_ess_target
+  bool ctrl = false;    // mppi_set_control_cost
+  bool bounds = false;  // mppi_set_control_bounds
+  bool rate = false;    // mppi_set_rate_cost
+  bool elite = false;   // mppi_set_elites
+};
+
 }  // namespace
 
 struct mppi_handle {
@@ -99,6 +112,7 @@ struct mppi_handle {
   unsigned* d_gticket = nullptr;
   hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
   int graph_B = 0, graph_n = 0, graph_parity = 0;
+  SolveOpts graph_opts;         // the options the captured graph's solves carry
   bool prefetch_valid = false;  // d_noise / d_noise2 [graph_parity] holds the next launch's first noise
   int prefetch_B = 0;           // ... generated for this batch and seed (graph launches and chained solves)
   uint64_t prefetch_seed = 0;
@@ -134,7 +148,6 @@ struct mppi_handle {
   float *d_stats_w = nullptr, *d_stats_part = nullptr;  // scratch: normalised weights [max_batch][Kp], cell partials
   int stats_slots = 0;
   int stats_B = 0, stats_n = 0;  // batch and slot count of the last flagged solve / graph launch (0: none ran)
-  bool graph_stats = false;      // the captured graph carries the flag
   // the law adapted on the device (mppi_set_noise_adapt; noise_adapt.h, kernels_noise.hip).  While adapt_on, d_law is
   // the law: the generators read it, noise_adapt_kernel moves it behind every solve's statistics, and noise_model
   // only keeps active = 1.  d_law_hist [hist_slots + 1][nu + 1]: the law solve i of the last solve / graph launch drew
@@ -145,7 +158,6 @@ struct mppi_handle {
   float* d_law_hist = nullptr;
   int hist_slots = 0;
   int law_n = 0;             // history rows of the last adapting solve / graph launch (0: none ran)
-  bool graph_adapt = false;  // the captured graph adapts
   // ESS targeting (mppi_set_ess_target; ess_target.h, kernels_lambda.hip).  While ess_on, every solve runs
   // lambda_search_kernel between its rollout and its reduce; the reduce and the statistics read the solve's lambda from
   // d_lambda [lambda_slots + 1][max_batch], slot-major like the statistics (a graph's solve i writes slot i; the last
@@ -155,7 +167,6 @@ struct mppi_handle {
   float* d_lambda = nullptr;
   int lambda_slots = 0;
   int lam_B = 0, lam_n = 0;  // batch and slot count of the last targeting solve / graph launch (0: none ran)
-  bool graph_ess = false;    // the captured graph targets
   // the control-cost term (mppi_set_control_cost; control_cost.h, kernels_ctrl_cost.hip).  While ctrl_gamma > 0 every
   // solve runs ctrl_lin_kernel + the term kernel between its rollout and everything that weighs its costs; the lambda
   // search, the reduce and the statistics then read d_wcost = d_costs + term where they read d_costs otherwise.  All
@@ -165,10 +176,9 @@ struct mppi_handle {
   float* d_wcost = nullptr;       // [2][max_batch][Kp]
   float* d_term = nullptr;        // [2][max_batch][Kp]
   float* d_lin = nullptr;         // [2][max_batch][nu][H]
-  float* d_ctrl_part = nullptr;   // [ctrl_part_floats] the split form's partials (scratch)
+  float* d_ctrl_part = nullptr;   // [term_part_floats] the split form's partials (scratch)
   float* d_ctrl_U = nullptr;      // [max_batch][nu][H] mppi_control_term_eval's U (the resident d_U stays as it is)
   int ctrl_B = 0;                 // batch of the last solve / graph launch with the term (0: none ran)
-  bool graph_ctrl = false;        // the captured graph carries the term
   // per-actuator control bounds (mppi_set_control_bounds; ctrl_bounds.h, kernels_bounds.hip).  While bounds_on every
   // solve projects its noise in place ahead of its rollout (the buffer then holds clip(U + eps, lo, hi) - U) and clips
   // U, the Umirror copy and u0 behind its update; the box travels by value in the launches.  The buffers are allocated
@@ -180,7 +190,6 @@ struct mppi_handle {
   unsigned* d_bpart = nullptr;    // [max_batch nu H][bounds_chunks(Kp)] the projection's per-row counts (scratch)
   float* d_bounds_U = nullptr;    // [max_batch][nu][H] mppi_bounds_eval's U (the resident d_U stays as it is)
   int bounds_B = 0;               // batch of the last bounded solve / graph launch (0: none ran)
-  bool graph_bounds = false;      // the captured graph carries the bounds
   // the control-rate cost term (mppi_set_rate_cost; rate_cost.h, kernels_rate_cost.hip).  While rate_on every solve runs
   // the term kernel between its rollout (and the control-cost term) and everything that weighs its costs; the lambda
   // search, the reduce and the statistics then read d_rate_wcost = (costs [+ control term]) + rate term.  The weights
@@ -193,11 +202,10 @@ struct mppi_handle {
   float rate_r[kMaxNu] = {0};
   float* d_rate_wcost = nullptr;  // [2][max_batch][Kp]
   float* d_rate_term = nullptr;   // [2][max_batch][Kp]
-  float* d_rate_part = nullptr;   // [rate_part_floats] the split form's partials (scratch)
+  float* d_rate_part = nullptr;   // [term_part_floats] the split form's partials (scratch)
   float* d_rate_U = nullptr;      // [max_batch][nu][H] mppi_rate_term_eval's U (the resident d_U stays as it is)
   float* d_uprev = nullptr;       // [2][max_batch][nu]
   int rate_B = 0;                 // batch of the last solve / graph launch with the term (0: none ran)
-  bool graph_rate = false;        // the captured graph carries the term
   // elite truncation (mppi_set_elites; elite_select.h, kernels_elite.hip).  While elite_n > 0 every solve runs
   // elite_select_kernel behind its rollout and the cost terms and ahead of everything that weighs its costs; the lambda
   // search, the reduce and the statistics then read d_elite_wcost = the end of the wcost chain on the elite set, +inf
@@ -209,7 +217,6 @@ struct mppi_handle {
   int32_t* d_elite_count = nullptr;  // [2][max_batch]
   float* d_elite_tau = nullptr;      // [2][max_batch]
   int elite_B = 0;                   // batch of the last solve / graph launch with elites (0: none ran)
-  bool graph_elite = false;          // the captured graph carries the selection
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -248,6 +255,79 @@ static hipError_t timed(mppi_handle* h, int id, F&& launch, int count = 1) {
   (void)hipEventRecord(p.b, h->stream);
   h->pending.push_back(p);
   return e;
+}
+
+#define MPPI_TRY(expr)                 \
+  do {                                 \
+    const int rc_ = (expr);            \
+    if (rc_ != MPPI_OK) return rc_;    \
+  } while (0)
+
+// The captured graphs hold the handle's settings in their kernel arguments: a setter that changes one destroys them.
+// wait: a launch still in flight finishes first (a caller that has waited already, or that knows the stream's state,
+// passes false).  The prefetched noise is not touched: whether it stays valid is the caller's decision.
+static int drop_graphs(mppi_handle* h, bool wait) {
+  if (wait && (h->graph_exec[0] || h->graph_exec[1])) HIP_TRY(hipStreamSynchronize(h->stream));
+  for (hipGraphExec_t& g : h->graph_exec)
+    if (g) {
+      HIP_TRY(hipGraphExecDestroy(g));
+      g = nullptr;
+    }
+  return MPPI_OK;
+}
+
+// The overlapped generator's last launch (and its counter bump) precede anything enqueued on the stream from here on.
+static hipError_t wait_gen(mppi_handle* h) {
+  if (!h->gen_pending) return hipSuccess;
+  const hipError_t e = hipStreamWaitEvent(h->stream, h->ev_gen, 0);
+  if (e == hipSuccess) h->gen_pending = false;
+  return e;
+}
+
+// `rows` noise rows [K] (host, or device with `kind`) into the device rows [Kp] of d_noise, the pads K..Kp zeroed
+static int stage_noise(mppi_handle* h, const float* src, size_t rows, hipMemcpyKind kind = hipMemcpyHostToDevice) {
+  const size_t K = (size_t)h->cfg.K, Kp = (size_t)h->Kp;
+  if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, h->stream));
+  HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, src, K * 4, K * 4, rows, kind, h->stream));
+  return MPPI_OK;
+}
+
+// host costs [B][K] into the staging costs [B][Kp] of an evaluation (the pads keep whatever they hold: no kernel of an
+// evaluation counts them)
+static int stage_costs(mppi_handle* h, const float* src, int B) {
+  const size_t K = (size_t)h->cfg.K, Kp = (size_t)h->Kp;
+  HIP_TRY(hipMemcpy2DAsync(h->d_costs, Kp * 4, src, K * 4, K * 4, B, hipMemcpyHostToDevice, h->stream));
+  return MPPI_OK;
+}
+
+// An option's buffers, all or none: every (pointer, bytes) of the list is allocated, then all are committed; a failure
+// frees what it got and leaves the pointers as they were.  No buffer is cleared: every entry is written before it is read.
+struct BufReq {
+  void** p;
+  size_t bytes;
+};
+static int alloc_group(const char* who, const std::vector<BufReq>& reqs) {
+  std::vector<void*> got;
+  for (const BufReq& r : reqs) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, r.bytes);
+    if (e != hipSuccess) {
+      for (void* g : got) (void)hipFree(g);
+      return fail(MPPI_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    got.push_back(p);
+  }
+  for (size_t i = 0; i < reqs.size(); ++i) *reqs[i].p = got[i];
+  return MPPI_OK;
+}
+static size_t at_least16(size_t bytes) { return bytes < 16 ? 16 : bytes; }
+
+// dst [B][cols][rows] <- src [B][rows][cols].  Julia's U (nu, H) column-major is [H][nu] in memory: (H, nu) brings it to
+// the engine's [nu][H], (nu, H) takes it back
+static void transpose_batched(float* dst, const float* src, int B, int rows, int cols) {
+  for (int b = 0; b < B; ++b)
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) dst[((size_t)b * cols + c) * rows + r] = src[((size_t)b * rows + r) * cols + c];
 }
 
 static CartpoleParams default_cartpole() {
@@ -534,12 +614,7 @@ int mppi_set_cost(mppi_handle* h, int kind, const float* params, int nparams) {
     // handle to "not probed" and the next solve (or capture) probes again.  Graphs captured under the old decision
     // are stale the way mppi_set_noise_model's are (a launch still in flight finishes first)
     HIP_TRY(hipSetDevice(h->device));
-    if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
-    for (hipGraphExec_t& g : h->graph_exec)
-      if (g) {
-        HIP_TRY(hipGraphExecDestroy(g));
-        g = nullptr;
-      }
+    MPPI_TRY(drop_graphs(h, true));
     h->net.x3_l1 = 0;
     h->net.x3_l1_err = -1.0f;
     h->net.x3_f16 = 0;
@@ -890,11 +965,7 @@ static hipError_t launch_rollout(mppi_handle* h, const SolveArgs& a, hipStream_t
 // stepped back so the next consumer draws exactly the key the prefetch took: the key sequence of any interleaving
 // of plain solves and graph launches equals a loop of plain solves.
 static hipError_t drop_prefetch(mppi_handle* h) {
-  if (h->gen_pending) {  // the overlapped generator's launch (and its counter bump) precede anything on the stream
-    const hipError_t e = hipStreamWaitEvent(h->stream, h->ev_gen, 0);
-    if (e != hipSuccess) return e;
-    h->gen_pending = false;
-  }
+  if (const hipError_t e = wait_gen(h); e != hipSuccess) return e;
   if (!h->prefetch_valid) return hipSuccess;
   h->prefetch_valid = false;
   return launch_seed_bump(h->d_seed_ctr, -1, h->stream);
@@ -906,6 +977,38 @@ struct NoiseStep {
   float* cur;
   float* next;
 };
+
+// the options of a solve enqueued (or captured) now with these flags
+static SolveOpts solve_opts(const mppi_handle* h, int flags) {
+  SolveOpts o;
+  o.stats = (flags & MPPI_FLAG_STATS) != 0;
+  o.adapt = h->adapt_on;
+  o.ess = h->ess_on;
+  o.ctrl = h->ctrl_gamma > 0.0f;
+  o.bounds = h->bounds_on;
+  o.rate = h->rate_on;
+  o.elite = h->elite_n > 0;
+  return o;
+}
+
+// n solves of batch B with these options were enqueued (a plain or chained solve: n = 1, slot 0; a graph launch: its
+// solves, solve i in slot i): what the getters may read from now on.  The options without per-step slots keep the
+// chain's last solve.
+static void note_ran(mppi_handle* h, const SolveOpts& o, int B, int n) {
+  if (o.stats) {
+    h->stats_B = B;
+    h->stats_n = n;
+  }
+  if (o.adapt) h->law_n = n;
+  if (o.ess) {
+    h->lam_B = B;
+    h->lam_n = n;
+  }
+  if (o.ctrl) h->ctrl_B = B;
+  if (o.bounds) h->bounds_B = B;
+  if (o.rate) h->rate_B = B;
+  if (o.elite) h->elite_B = B;
+}
 
 // Enqueue one solve on the handle's stream: inputs, noise, rollout, reduce (+ update, shift), env step, outputs.
 // Synchronises only for host-side column-major staging. Capturable into a hipGraph in device mode.
@@ -950,10 +1053,10 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // ESS targeting: the solve's slot of lambdas, written by the search between the rollout and the reduce (below)
   float* const lam = lambda_slot(h, stats_slot);
   a.lambda_dev = lam;
-  const bool ctrl = h->ctrl_gamma > 0.0f;  // the control-cost term: the softmin weighs d_wcost = costs + term (below)
-  const bool rate = h->rate_on;  // the rate term: the softmin weighs d_rate_wcost = (costs [+ control term]) + rate term
-  const bool elite = h->elite_n > 0;  // elite truncation: the softmin weighs d_elite_wcost, the chain's end on the elite set
-  const bool cart_unfused = (lam || ctrl || rate || elite) && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  // o.ctrl: the softmin weighs d_wcost = costs + term; o.rate: d_rate_wcost = (costs [+ control term]) + rate term;
+  // o.elite: d_elite_wcost, the chain's end on the elite set (below)
+  const SolveOpts o = solve_opts(h, flags);
+  const bool cart_unfused = (lam || o.ctrl || o.rate || o.elite) && h->dyn_kind == MPPI_DYN_CARTPOLE;
   // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths); the cartpole's unfused
   // rollout carries no stamp
   a.kclock = (h->kclock && a.seed_ctr && !cart_unfused) ? h->d_kclock : nullptr;
@@ -977,10 +1080,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       const float* src = io->U;
       if (colmajor) {  // Julia U (nu,H) column-major -> [nu][H]
         h->staging.resize(rowsU);
-        for (int b = 0; b < B; ++b)
-          for (int u = 0; u < nu; ++u)
-            for (int t = 0; t < H; ++t)
-              h->staging[((size_t)b * nu + u) * H + t] = io->U[((size_t)b * H + t) * nu + u];
+        transpose_batched(h->staging.data(), io->U, B, H, nu);
         src = h->staging.data();
       }
       HIP_TRY(hipMemcpyAsync(h->d_U, src, rowsU * 4, hipMemcpyHostToDevice, s));
@@ -1001,9 +1101,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
               tmp[(((size_t)b * nu + u) * H + t) * K + k] = io->noise[(((size_t)b * K + k) * H + t) * nu + u];
       src = tmp.data();
     }
-    if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rowsU * Kp * 4, s));
-    HIP_TRY(hipMemcpy2DAsync(h->d_noise, (size_t)Kp * 4, src, (size_t)K * 4, (size_t)K * 4, rowsU,
-                             dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    MPPI_TRY(stage_noise(h, src, rowsU, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     if (!tmp.empty()) HIP_TRY(hipStreamSynchronize(s));
   } else if (!ns) {
     HIP_TRY(timed(h, kNoise, [&] {
@@ -1014,7 +1112,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // per-actuator bounds: the solve's noise -- drawn above, prefetched by the previous solve's generator, or the copy of
   // an injected io.noise (never the caller's array) -- projected in place against the nominal U, ahead of the rollout
   // and of every other reader of this solve's noise
-  if (h->bounds_on) HIP_TRY(timed(h, kBounds, [&] { return enqueue_bounds_project(h, B, a.U, a.noise); }));
+  if (o.bounds) HIP_TRY(timed(h, kBounds, [&] { return enqueue_bounds_project(h, B, a.U, a.noise); }));
 
   // ---- a2-a6: rollout + cost; a7-a9: softmin + weighted-noise reduce + update + shift
   const NoiseGen gen{ns ? ns->next : nullptr, seed, c.sigma, h->d_gticket};
@@ -1022,7 +1120,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // reduce order) cannot give: the next noise then comes from its own launch behind the reduce (below)
   const bool gen_after = ns && ns->next && h->noise_model.active;
   const NoiseGen* pg = ns && ns->next && !gen_after ? &gen : nullptr;
-  const float* wcost = a.costs;  // what the search, the reduce and the statistics weigh
+  float* wcost = a.costs;  // what the search, the reduce and the statistics weigh: the end of the chain below
   if (h->dyn_kind == MPPI_DYN_CARTPOLE && !cart_unfused) {  // one launch: the rollout blocks finish the solve (fused)
     a.part = h->d_part;
     HIP_TRY(timed(h, kRollout, [&] { return launch_cartpole_rollout(a, h->cart, pg, s); }));
@@ -1034,33 +1132,31 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     // yet, or with elites, whose selection needs every cost of the solve)
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
     h->rollout_kernel = g_rollout_kernel;
-    SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
-    if (ctrl) {
+    if (o.ctrl) {
       // the control-cost term, behind the rollout (its costs exist) and ahead of the reduce (a.U is still the nominal the
       // rollout perturbed).  An adapting handle's ctrl_lin_kernel reads d_law on the stream: at this point it still
       // holds the law that drew THIS solve's noise -- the adapt kernel runs behind the reduce and the statistics
       // (below), and the generators of the next solve's noise behind that
       HIP_TRY(timed(h, kCtrl, [&] { return enqueue_ctrl(h, B, a.U, a.noise, a.costs, 0); }));
       wcost = h->d_wcost;
-      r.costs = h->d_wcost;
     }
-    if (rate) {
+    if (o.rate) {
       // the rate term, behind the control-cost term (wcost = (costs + control term) + rate term, in this order) and ahead
       // of the reduce: a.U is still the nominal the rollout perturbed, a.noise what the rollout saw (projected, with
       // bounds on), d_uprev the control the previous step applied (its store sits behind that step's update, below)
       HIP_TRY(timed(h, kRate, [&] { return enqueue_rate(h, B, a.U, a.noise, h->d_uprev, wcost, 0); }));
       wcost = h->d_rate_wcost;
-      r.costs = h->d_rate_wcost;
     }
-    if (elite) {
+    if (o.elite) {
       // elite truncation, behind the terms (it selects on what the softmin would otherwise weigh) and ahead of the lambda
       // search: the search, the reduce and the statistics see the cost on the elite set and +inf elsewhere
       HIP_TRY(timed(h, kElites, [&] { return enqueue_elite(h, B, wcost, 0); }));
       wcost = h->d_elite_wcost;
-      r.costs = h->d_elite_wcost;
     }
     if (lam)
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
+    SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
+    r.costs = wcost;
     HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s); }));
   }
   // per-actuator bounds: behind the update and shift (the cartpole's fused epilogue included), ahead of the env step,
@@ -1068,23 +1164,23 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // U + sum w (v - U), brings a shift-filled last column into a box that excludes zero, and makes lo <= U, u0 <= hi
   // hold exactly whatever the update mode and flags; the same launch sums the projection's counts (its time joins
   // "bounds", counted once per solve above)
-  if (h->bounds_on)
+  if (o.bounds)
     HIP_TRY(timed(h, kBounds, [&] { return launch_bounds_clip(bounds_args(h, B), a.U, a.Umirror, a.u0, s); }, 0));
   // the rate term's anchor: the u0 this solve returns (clipped above; the pre-update column with MPPI_FLAG_U0_BEFORE) is
   // what the next step differences its t = 0 against -- one small launch behind the update and the clip, ahead of the
   // env step, so chained and captured streams anchor step i + 1 to step i with no host round trip (its time joins
   // "rate_cost", counted once per solve above)
-  if (rate && h->rate_anchor && (flags & MPPI_FLAG_SHIFT))
+  if (o.rate && h->rate_anchor && (flags & MPPI_FLAG_SHIFT))
     HIP_TRY(timed(h, kRate, [&] { return launch_rate_store_prev(a.u0, h->d_uprev, B * nu, s); }, 0));
   // diagnostics (MPPI_FLAG_STATS): read-only on this solve's costs and noise, behind the reduce (or the cartpole's fused
   // epilogue) and ahead of everything that may write a.noise -- the next solve's generators, on this stream or ordered
   // behind it (ev_red), only ever write the OTHER buffer of the pair before this point
-  if (flags & MPPI_FLAG_STATS)
+  if (o.stats)
     HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, wcost, a.noise, stats_slot, lam); }));
   // the adapted law (mppi_set_noise_adapt; every such solve carries the flag): one wave directly behind the statistics
   // and ahead of the launch below that draws the next solve's noise, so chained and captured streams draw solve i + 1
   // from the law adapted on solve i, as a loop of plain solves does
-  if (h->adapt_on) HIP_TRY(timed(h, kStats, [&] { return enqueue_adapt(h, B, stats_slot); }));
+  if (o.adapt) HIP_TRY(timed(h, kStats, [&] { return enqueue_adapt(h, B, stats_slot); }));
   if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
     HIP_TRY(timed(h, kNoise, [&] {
       return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s,
@@ -1137,26 +1233,22 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
 }
 
 // The device status word (bit 0: some solve had no finite cost).  The fc/FA rollouts reset it per launch; the fused
-// cartpole epilogue only sets it, so it is cleared here once read (sticky between reads).
-static int read_status(mppi_handle* h, unsigned* st) {
-  HIP_TRY(hipMemcpy(st, h->d_status, 4, hipMemcpyDeviceToHost));
-  if (*st) HIP_TRY(hipMemset(h->d_status, 0, 4));
+// cartpole epilogue only sets it, so it is cleared here once read (sticky between reads).  Read with the stream idle
+// and reported under the entry's name.
+static int report_status(mppi_handle* h, const char* entry) {
+  unsigned st = 0;
+  HIP_TRY(hipMemcpy(&st, h->d_status, 4, hipMemcpyDeviceToHost));
+  if (st) HIP_TRY(hipMemset(h->d_status, 0, 4));
+  if (st & 1u) return fail(MPPI_E_NONFINITE, std::string(entry) + ": every sample of some solve had a non-finite cost");
   return MPPI_OK;
 }
 
 // Wait for the stream, finish host-side layout conversion, report non-finite solves.
 static int finish_solve(mppi_handle* h, int B, const mppi_io* io) {
   HIP_TRY(hipStreamSynchronize(h->stream));
-  const int nu = h->cfg.nu, H = h->cfg.H;
-  if (!h->Uhost.empty())
-    for (int b = 0; b < B; ++b)
-      for (int u = 0; u < nu; ++u)
-        for (int t = 0; t < H; ++t) io->U[((size_t)b * H + t) * nu + u] = h->Uhost[((size_t)b * nu + u) * H + t];
+  if (!h->Uhost.empty()) transpose_batched(io->U, h->Uhost.data(), B, h->cfg.nu, h->cfg.H);
   h->Uhost.clear();
-  unsigned st = 0;
-  if (const int rc = read_status(h, &st); rc != MPPI_OK) return rc;
-  if (st & 1u) return fail(MPPI_E_NONFINITE, "mppi_solve: every sample of some solve had a non-finite cost");
-  return MPPI_OK;
+  return report_status(h, "mppi_solve");
 }
 
 // The graph-stream noise double buffer (d_noise, d_noise2) and the generators' ticket, allocated on first use.
@@ -1210,23 +1302,6 @@ static int ensure_gen_stream(mppi_handle* h) {
   return MPPI_OK;
 }
 
-// a flagged plain or chained solve was enqueued: its statistics are slot 0
-static void note_stats(mppi_handle* h, int B, int flags) {
-  if (flags & MPPI_FLAG_STATS) {
-    h->stats_B = B;
-    h->stats_n = 1;
-  }
-  if (h->adapt_on) h->law_n = 1;
-  if (h->ess_on) {
-    h->lam_B = B;
-    h->lam_n = 1;
-  }
-  if (h->ctrl_gamma > 0.0f) h->ctrl_B = B;
-  if (h->bounds_on) h->bounds_B = B;
-  if (h->rate_on) h->rate_B = B;
-  if (h->elite_n > 0) h->elite_B = B;
-}
-
 // MPPI_FLAG_CHAIN: one solve of a graph stream, launched on the stream (rollout -> reduce_kernel<GEN>, or with
 // gen_overlap the generator stream's noise launch beside the rollout, then the read-only reduce).  A graph launch pays
 // a fixed gap at its boundary (~8.5 us on the box, rocprof trace) that back-to-back stream launches do not, so
@@ -1235,26 +1310,23 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   if (!(flags & MPPI_FLAG_DEVICE)) return fail(MPPI_E_ARG, "mppi_solve: MPPI_FLAG_CHAIN needs MPPI_FLAG_DEVICE");
   if (io->noise) return fail(MPPI_E_ARG, "mppi_solve: MPPI_FLAG_CHAIN draws device noise (no injected noise)");
   flags |= MPPI_FLAG_SEED_COUNTER;
-  if (const int rc = ensure_stream_buffers(h); rc != MPPI_OK) return rc;
+  MPPI_TRY(ensure_stream_buffers(h));
   // (an adapting handle ignores the overlap arm, as a capture does: it would draw the next noise ahead of this
   // solve's update of the law)
   const bool overlap = gen_overlap() && !h->capturing && !h->adapt_on;
-  if (!overlap && h->gen_pending) {  // leaving overlap mode: order the solve stream behind the last generator launch
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_gen, 0));
-    h->gen_pending = false;
-  }
-  if (const int rc = prime_prefetch(h, B, seed); rc != MPPI_OK) return rc;
+  if (!overlap) HIP_TRY(wait_gen(h));  // leaving overlap mode: the solve stream behind the last generator launch
+  MPPI_TRY(prime_prefetch(h, B, seed));
   float* buf[2] = {h->d_noise, h->d_noise2};
   if (!overlap) {
     const NoiseStep ns{buf[h->graph_parity], buf[h->graph_parity ^ 1]};
     const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns);
     if (rc != MPPI_OK) return rc;
-    note_stats(h, B, flags);
+    note_ran(h, solve_opts(h, flags), B, 1);
     h->graph_parity ^= 1;  // this solve's reduce prefetched the next one's noise (still key-valid for B, seed)
     if (flags & MPPI_FLAG_ASYNC) return MPPI_OK;
     return finish_solve(h, B, io);
   }
-  if (const int rc = ensure_gen_stream(h); rc != MPPI_OK) return rc;
+  MPPI_TRY(ensure_gen_stream(h));
   const mppi_config& c = h->cfg;
   // this solve's noise (buf[p]) was written by the previous call's generator launch (or primed on the stream)
   if (h->gen_pending) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_gen, 0));
@@ -1270,7 +1342,7 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   const NoiseStep ns{buf[h->graph_parity], nullptr};  // read-only reduce, no counter bump (the generator owns it)
   const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns);
   if (rc != MPPI_OK) return rc;
-  note_stats(h, B, flags);
+  note_ran(h, solve_opts(h, flags), B, 1);
   h->graph_parity ^= 1;  // the generator prefetched the next one's noise (key-valid for B, seed)
   if (flags & MPPI_FLAG_ASYNC) return MPPI_OK;
   return finish_solve(h, B, io);
@@ -1339,10 +1411,7 @@ static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
       ku = hipMemcpyDeviceToDevice;
     } else if (colmajor) {  // Julia U (nu,H) column-major -> [nu][H]
       stage.resize(nU);
-      for (int b = 0; b < Bp; ++b)
-        for (int u = 0; u < c.nu; ++u)
-          for (int t = 0; t < c.H; ++t)
-            stage[((size_t)b * c.nu + u) * c.H + t] = io->U[((size_t)b * c.H + t) * c.nu + u];
+      transpose_batched(stage.data(), io->U, Bp, c.H, c.nu);
       U = stage.data();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(p_U, U, nU * 4, ku, s);
@@ -1454,7 +1523,7 @@ int mppi_solve_ex(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int f
   HIP_TRY(drop_prefetch(h));  // a plain solve generates its own noise into d_noise
   rc = enqueue_solve(h, B, io, seed, flags);
   if (rc != MPPI_OK) return rc;
-  note_stats(h, B, flags);
+  note_ran(h, solve_opts(h, flags), B, 1);
   if ((flags & MPPI_FLAG_DEVICE) && (flags & MPPI_FLAG_ASYNC)) return MPPI_OK;
   return finish_solve(h, B, io);
 }
@@ -1477,11 +1546,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   if (h->adapt_on) flags |= MPPI_FLAG_STATS;  // the adaptation reads solve i's moments out of slot i
   HIP_TRY(hipSetDevice(h->device));
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;  // before the capture: it synchronises the stream
-  for (hipGraphExec_t& g : h->graph_exec)
-    if (g) {
-      HIP_TRY(hipGraphExecDestroy(g));
-      g = nullptr;
-    }
+  MPPI_TRY(drop_graphs(h, false));
   // a prefetched noise stays valid for a graph of the same batch and seed (checked again at launch)
   if (h->prefetch_valid && (B != h->prefetch_B || seed != h->prefetch_seed)) HIP_TRY(drop_prefetch(h));
   const mppi_config& c = h->cfg;
@@ -1523,13 +1588,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->prof = prof;
   h->capturing = false;
   h->graph_kclock = h->kclock;
-  h->graph_stats = (flags & MPPI_FLAG_STATS) != 0;
-  h->graph_adapt = h->adapt_on;
-  h->graph_ess = h->ess_on;
-  h->graph_ctrl = h->ctrl_gamma > 0.0f;
-  h->graph_bounds = h->bounds_on;
-  h->graph_rate = h->rate_on;
-  h->graph_elite = h->elite_n > 0;
+  h->graph_opts = solve_opts(h, flags);
   h->graph_B = B;
   h->graph_n = n_solves;
   h->graph_seed = seed;
@@ -1541,43 +1600,22 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
   if (!h->graph_exec[0] || !h->graph_exec[1])
     return fail(MPPI_E_STATE, "mppi_graph_launch: call mppi_graph_capture first");
   HIP_TRY(hipSetDevice(h->device));
-  if (h->gen_pending) {  // chained solves with the overlapped generator came before: its noise and bump first
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_gen, 0));
-    h->gen_pending = false;
-  }
+  HIP_TRY(wait_gen(h));  // chained solves with the overlapped generator came before: its noise and bump first
   // first launch (or after plain solves / a counter reset / chained solves of another batch): generate the noise
-  if (const int rc = prime_prefetch(h, h->graph_B, h->graph_seed); rc != MPPI_OK) return rc;
+  MPPI_TRY(prime_prefetch(h, h->graph_B, h->graph_seed));
   HIP_TRY(hipGraphLaunch(h->graph_exec[h->graph_parity], h->stream));
   if (h->graph_kclock) h->kclock_launches += h->graph_n;
-  if (h->graph_stats) {
-    h->stats_B = h->graph_B;
-    h->stats_n = h->graph_n;
-  }
-  if (h->graph_adapt) h->law_n = h->graph_n;
-  if (h->graph_ess) {
-    h->lam_B = h->graph_B;
-    h->lam_n = h->graph_n;
-  }
-  if (h->graph_ctrl) h->ctrl_B = h->graph_B;  // (no per-step slots: the chain's last solve)
-  if (h->graph_bounds) h->bounds_B = h->graph_B;  // (likewise)
-  if (h->graph_rate) h->rate_B = h->graph_B;      // (likewise)
-  if (h->graph_elite) h->elite_B = h->graph_B;    // (likewise)
+  note_ran(h, h->graph_opts, h->graph_B, h->graph_n);
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  unsigned st = 0;
-  if (const int rc = read_status(h, &st); rc != MPPI_OK) return rc;
-  if (st & 1u) return fail(MPPI_E_NONFINITE, "mppi_graph_launch: every sample of some solve had a non-finite cost");
-  return MPPI_OK;
+  return report_status(h, "mppi_graph_launch");
 }
 
 int mppi_set_seed_counter(mppi_handle* h, uint64_t value) {
   if (!h) return fail(MPPI_E_ARG, "mppi_set_seed_counter: null handle");
   HIP_TRY(hipSetDevice(h->device));
-  if (h->gen_pending) {  // the generator's last bump lands before the new value
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_gen, 0));
-    h->gen_pending = false;
-  }
+  HIP_TRY(wait_gen(h));  // the generator's last bump lands before the new value
   HIP_TRY(hipMemcpyAsync(h->d_seed_ctr, &value, 8, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->prefetch_valid = false;  // a prefetched noise used the old counter
@@ -1587,10 +1625,7 @@ int mppi_set_seed_counter(mppi_handle* h, uint64_t value) {
 int mppi_get_seed_counter(mppi_handle* h, uint64_t* value) {
   if (!h || !value) return fail(MPPI_E_ARG, "mppi_get_seed_counter: null argument");
   HIP_TRY(hipSetDevice(h->device));
-  if (h->gen_pending) {  // the overlapped generator's bump is part of the counter's value
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_gen, 0));
-    h->gen_pending = false;
-  }
+  HIP_TRY(wait_gen(h));  // the overlapped generator's bump is part of the counter's value
   uint64_t v = 0;
   HIP_TRY(hipMemcpyAsync(&v, h->d_seed_ctr, 8, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1617,12 +1652,7 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
   // stale state: a prefetched noise was drawn with the old law (the counter steps back: the key sequence is unchanged),
   // and the captured graphs hold the old model in their kernel arguments (a launch still in flight finishes first)
   HIP_TRY(drop_prefetch(h));
-  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
-  for (hipGraphExec_t& g : h->graph_exec)
-    if (g) {
-      HIP_TRY(hipGraphExecDestroy(g));
-      g = nullptr;
-    }
+  MPPI_TRY(drop_graphs(h, true));
   NoiseModel m;
   m.active = active || h->adapt_on ? 1 : 0;  // (an adapting handle's model stays active: (NULL, 0) is its values)
   m.rho = rho;
@@ -1664,12 +1694,7 @@ int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigm
   // stale state, as in mppi_set_noise_model: the prefetched noise (the counter steps back: the key sequence is
   // unchanged) and the captured graphs, whose generators are those of the other path
   HIP_TRY(drop_prefetch(h));
-  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
-  for (hipGraphExec_t& g : h->graph_exec)
-    if (g) {
-      HIP_TRY(hipGraphExecDestroy(g));
-      g = nullptr;
-    }
+  MPPI_TRY(drop_graphs(h, true));
   if (on && !h->adapt_on) {
     // (no memset: noise_law_set_kernel below writes every entry, in stream order; a memset on the null stream is not
     // ordered against the handle's stream and could land behind it)
@@ -1685,7 +1710,7 @@ int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigm
     h->adapt_on = true;
     h->law_n = 0;
   } else if (!on) {  // back to the by-value path with the law as it stands
-    if (const int rc = fetch_law(h); rc != MPPI_OK) return rc;
+    MPPI_TRY(fetch_law(h));
     h->adapt_on = false;
   }
   h->adapt = NoiseAdapt{rate, sigma_min, sigma_max, rho_max};
@@ -1721,7 +1746,7 @@ int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active
   if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_model: null handle");
   if (h->adapt_on) {  // the live law: every enqueued solve's update included
     HIP_TRY(hipSetDevice(h->device));
-    if (const int rc = fetch_law(h); rc != MPPI_OK) return rc;
+    MPPI_TRY(fetch_law(h));
   }
   const NoiseModel& m = h->noise_model;
   if (sigma_u)
@@ -1746,12 +1771,7 @@ int mppi_set_ess_target(mppi_handle* h, float ess_frac, float lambda_min, float 
   HIP_TRY(hipSetDevice(h->device));
   // stale state: the captured graphs hold the settings (or their absence) in their launches; a launch still in flight
   // finishes first.  A prefetched noise is kept: lambda does not enter the noise, the key sequence is unchanged
-  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
-  for (hipGraphExec_t& g : h->graph_exec)
-    if (g) {
-      HIP_TRY(hipGraphExecDestroy(g));
-      g = nullptr;
-    }
+  MPPI_TRY(drop_graphs(h, true));
   h->ess = t;
   h->ess_on = on;
   return MPPI_OK;
@@ -1783,10 +1803,9 @@ int mppi_lambda_eval(mppi_handle* h, int B, const float* costs, float* lambda) {
   if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_lambda_eval: B out of range [1, max_batch]");
   if (!h->ess_on) return fail(MPPI_E_STATE, "mppi_lambda_eval: call mppi_set_ess_target first");
   HIP_TRY(hipSetDevice(h->device));
-  if (const int rc = ensure_lambda(h, 1); rc != MPPI_OK) return rc;
+  MPPI_TRY(ensure_lambda(h, 1));
   hipStream_t s = h->stream;
-  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp;
-  HIP_TRY(hipMemcpy2DAsync(h->d_costs, Kp * 4, costs, K * 4, K * 4, B, hipMemcpyHostToDevice, s));
+  MPPI_TRY(stage_costs(h, costs, B));
   float* out = h->d_lambda + (size_t)h->lambda_slots * c.max_batch;  // the evaluation's own slot
   HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(h->d_costs, B, c.K, h->Kp, h->ess, c.lambda, out, s); }));
   HIP_TRY(hipMemcpyAsync(lambda, out, (size_t)B * 4, hipMemcpyDeviceToHost, s));
@@ -1803,32 +1822,16 @@ int mppi_set_control_cost(mppi_handle* h, float gamma) {
   const mppi_config& c = h->cfg;
   if (gamma > 0.0f && !h->d_wcost) {  // all of the term's buffers, once, or none (every entry is written before it is read)
     const size_t nk = (size_t)2 * c.max_batch * h->Kp * 4, nl = (size_t)c.max_batch * c.nu * c.H * 4;
-    const size_t np = ctrl_part_floats(c.max_batch, c.nu, c.H, h->Kp) * 4;
-    float *w = nullptr, *t = nullptr, *l = nullptr, *p = nullptr, *u = nullptr;
-    hipError_t e = hipMalloc(&w, nk);
-    if (e == hipSuccess) e = hipMalloc(&t, nk);
-    if (e == hipSuccess) e = hipMalloc(&l, 2 * nl);
-    if (e == hipSuccess) e = hipMalloc(&p, np < 16 ? 16 : np);
-    if (e == hipSuccess) e = hipMalloc(&u, nl);
-    if (e != hipSuccess) {
-      for (float* x : {w, t, l, p, u})
-        if (x) (void)hipFree(x);
-      return fail(MPPI_E_HIP, std::string("mppi_set_control_cost: ") + hipGetErrorString(e));
-    }
-    h->d_wcost = w;
-    h->d_term = t;
-    h->d_lin = l;
-    h->d_ctrl_part = p;
-    h->d_ctrl_U = u;
+    const size_t np = term_part_floats(c.max_batch, c.nu, c.H, h->Kp) * 4;
+    MPPI_TRY(alloc_group("mppi_set_control_cost", {{(void**)&h->d_wcost, nk},
+                                                   {(void**)&h->d_term, nk},
+                                                   {(void**)&h->d_lin, 2 * nl},
+                                                   {(void**)&h->d_ctrl_part, at_least16(np)},
+                                                   {(void**)&h->d_ctrl_U, nl}}));
   }
   // stale state: the captured graphs hold gamma (or the term's absence) in their launches; a launch still in flight
   // finishes first.  A prefetched noise is kept: gamma does not enter the noise, the key sequence is unchanged
-  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
-  for (hipGraphExec_t& g : h->graph_exec)
-    if (g) {
-      HIP_TRY(hipGraphExecDestroy(g));
-      g = nullptr;
-    }
+  MPPI_TRY(drop_graphs(h, true));
   h->ctrl_gamma = gamma;
   return MPPI_OK;
 }
@@ -1870,10 +1873,9 @@ int mppi_control_term_eval(mppi_handle* h, int B, const float* U, const float* n
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
   hipStream_t s = h->stream;
-  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  const size_t rows = (size_t)B * c.nu * c.H;
   HIP_TRY(hipMemcpyAsync(h->d_ctrl_U, U, rows * 4, hipMemcpyHostToDevice, s));
-  if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, s));
-  HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, noise, K * 4, K * 4, rows, hipMemcpyHostToDevice, s));
+  MPPI_TRY(stage_noise(h, noise, rows));
   // (the evaluation's own slot; its wcost adds the term to whatever the staging costs hold and is never read)
   HIP_TRY(timed(h, kCtrl, [&] { return enqueue_ctrl(h, B, h->d_ctrl_U, h->d_noise, h->d_costs, 1); }));
   HIP_TRY(hipStreamSynchronize(s));
@@ -1903,30 +1905,14 @@ int mppi_set_control_bounds(mppi_handle* h, const float* lo, const float* hi) {
   if (on && !h->d_bcounts) {  // all three buffers, once, or none (every entry is written before it is read)
     const size_t nc = (size_t)2 * c.max_batch * c.nu * sizeof(unsigned), nU = (size_t)c.max_batch * c.nu * c.H * 4;
     const size_t np = (size_t)c.max_batch * c.nu * c.H * bounds_chunks(h->Kp) * sizeof(unsigned);
-    unsigned *cnt = nullptr, *part = nullptr;
-    float* u = nullptr;
-    hipError_t e = hipMalloc(&cnt, nc < 16 ? 16 : nc);
-    if (e == hipSuccess) e = hipMalloc(&part, np < 16 ? 16 : np);
-    if (e == hipSuccess) e = hipMalloc(&u, nU < 16 ? 16 : nU);
-    if (e != hipSuccess) {
-      if (cnt) (void)hipFree(cnt);
-      if (part) (void)hipFree(part);
-      if (u) (void)hipFree(u);
-      return fail(MPPI_E_HIP, std::string("mppi_set_control_bounds: ") + hipGetErrorString(e));
-    }
-    h->d_bcounts = cnt;
-    h->d_bpart = part;
-    h->d_bounds_U = u;
+    MPPI_TRY(alloc_group("mppi_set_control_bounds", {{(void**)&h->d_bcounts, at_least16(nc)},
+                                                     {(void**)&h->d_bpart, at_least16(np)},
+                                                     {(void**)&h->d_bounds_U, at_least16(nU)}}));
   }
   // stale state: the captured graphs hold the box (or its absence) in their launches; a launch still in flight finishes
   // first.  A prefetched noise is kept: it is projected at the start of the solve that consumes it, with the box in
   // effect then, so the key sequence is unchanged
-  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
-  for (hipGraphExec_t& g : h->graph_exec)
-    if (g) {
-      HIP_TRY(hipGraphExecDestroy(g));
-      g = nullptr;
-    }
+  MPPI_TRY(drop_graphs(h, true));
   std::memcpy(h->bounds_lo, nlo, sizeof(nlo));
   std::memcpy(h->bounds_hi, nhi, sizeof(nhi));
   h->bounds_on = on;
@@ -1964,8 +1950,7 @@ int mppi_bounds_eval(mppi_handle* h, int B, const float* U, const float* noise_i
   hipStream_t s = h->stream;
   const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
   HIP_TRY(hipMemcpyAsync(h->d_bounds_U, U, rows * 4, hipMemcpyHostToDevice, s));
-  if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, s));
-  HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, noise_in, K * 4, K * 4, rows, hipMemcpyHostToDevice, s));
+  MPPI_TRY(stage_noise(h, noise_in, rows));
   HIP_TRY(timed(h, kBounds, [&] {  // the projection, then its counts into the evaluation's own slot (no U to clip)
     const hipError_t e = enqueue_bounds_project(h, B, h->d_bounds_U, h->d_noise);
     return e != hipSuccess ? e : launch_bounds_clip(bounds_args(h, B, 1), nullptr, nullptr, nullptr, s);
@@ -2014,35 +1999,18 @@ int mppi_set_rate_cost(mppi_handle* h, const float* r, int anchor) {
       return MPPI_OK;  // no change: captured graphs stay
   }
   HIP_TRY(hipSetDevice(h->device));
-  if (on) {
-    if (const int rc = ensure_uprev(h); rc != MPPI_OK) return rc;
-  }
+  if (on) MPPI_TRY(ensure_uprev(h));
   if (on && !h->d_rate_wcost) {  // the term's buffers, once, all or none (every entry is written before it is read)
     const size_t nk = (size_t)2 * c.max_batch * h->Kp * 4, nl = (size_t)c.max_batch * c.nu * c.H * 4;
-    const size_t np = rate_part_floats(c.max_batch, c.nu, c.H, h->Kp) * 4;
-    float *w = nullptr, *t = nullptr, *p = nullptr, *u = nullptr;
-    hipError_t e = hipMalloc(&w, nk);
-    if (e == hipSuccess) e = hipMalloc(&t, nk);
-    if (e == hipSuccess) e = hipMalloc(&p, np < 16 ? 16 : np);
-    if (e == hipSuccess) e = hipMalloc(&u, nl);
-    if (e != hipSuccess) {
-      for (float* x : {w, t, p, u})
-        if (x) (void)hipFree(x);
-      return fail(MPPI_E_HIP, std::string("mppi_set_rate_cost: ") + hipGetErrorString(e));
-    }
-    h->d_rate_wcost = w;
-    h->d_rate_term = t;
-    h->d_rate_part = p;
-    h->d_rate_U = u;
+    const size_t np = term_part_floats(c.max_batch, c.nu, c.H, h->Kp) * 4;
+    MPPI_TRY(alloc_group("mppi_set_rate_cost", {{(void**)&h->d_rate_wcost, nk},
+                                                {(void**)&h->d_rate_term, nk},
+                                                {(void**)&h->d_rate_part, at_least16(np)},
+                                                {(void**)&h->d_rate_U, nl}}));
   }
   // stale state: the captured graphs hold r and the anchor (or the term's absence) in their launches; a launch still in
   // flight finishes first.  A prefetched noise is kept: the term does not enter the noise, the key sequence is unchanged
-  if (h->graph_exec[0] || h->graph_exec[1]) HIP_TRY(hipStreamSynchronize(h->stream));
-  for (hipGraphExec_t& g : h->graph_exec)
-    if (g) {
-      HIP_TRY(hipGraphExecDestroy(g));
-      g = nullptr;
-    }
+  MPPI_TRY(drop_graphs(h, true));
   std::memcpy(h->rate_r, nr, sizeof(nr));
   h->rate_anchor = na;
   h->rate_on = on;
@@ -2062,7 +2030,7 @@ int mppi_set_prev_control(mppi_handle* h, int B, const float* u_prev) {
   if (!h || !u_prev) return fail(MPPI_E_ARG, "mppi_set_prev_control: null argument");
   if (B < 1 || B > h->cfg.max_batch) return fail(MPPI_E_ARG, "mppi_set_prev_control: B out of range [1, max_batch]");
   HIP_TRY(hipSetDevice(h->device));
-  if (const int rc = ensure_uprev(h); rc != MPPI_OK) return rc;
+  MPPI_TRY(ensure_uprev(h));
   // data, not a launch argument: ordered on the stream behind every solve enqueued so far, captured graphs stay
   HIP_TRY(hipMemcpyAsync(h->d_uprev, u_prev, (size_t)B * h->cfg.nu * 4, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));  // (the caller's array may go)
@@ -2108,12 +2076,11 @@ int mppi_rate_term_eval(mppi_handle* h, int B, const float* U, const float* nois
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
   hipStream_t s = h->stream;
-  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  const size_t rows = (size_t)B * c.nu * c.H;
   float* const up = h->d_uprev + (size_t)c.max_batch * c.nu;  // the evaluation's own u_prev (the handle's stays)
   HIP_TRY(hipMemcpyAsync(h->d_rate_U, U, rows * 4, hipMemcpyHostToDevice, s));
   if (u_prev) HIP_TRY(hipMemcpyAsync(up, u_prev, (size_t)B * c.nu * 4, hipMemcpyHostToDevice, s));
-  if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, s));
-  HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, noise, K * 4, K * 4, rows, hipMemcpyHostToDevice, s));
+  MPPI_TRY(stage_noise(h, noise, rows));
   // (the evaluation's own slot; its wcost adds the term to whatever the staging costs hold and is never read)
   HIP_TRY(timed(h, kRate, [&] {
     return enqueue_rate(h, B, h->d_rate_U, h->d_noise, u_prev ? up : h->d_uprev, h->d_costs, 1);
@@ -2134,33 +2101,18 @@ int mppi_set_elites(mppi_handle* h, int n_elite) {
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (n_elite > 0) {  // the feature's buffers (every entry is written before it is read); the set's by its row length
     const size_t nb = (size_t)2 * c.max_batch;
-    int32_t* ni = nullptr;
-    hipError_t e = hipMalloc(&ni, nb * n_elite * 4);
-    float *w = nullptr, *t = nullptr;
-    int32_t* cn = nullptr;
+    int32_t* ni = nullptr;  // (the old set stays until the new one exists)
+    std::vector<BufReq> reqs{{(void**)&ni, nb * n_elite * 4}};
     if (!h->d_elite_wcost) {
-      if (e == hipSuccess) e = hipMalloc(&w, nb * h->Kp * 4);
-      if (e == hipSuccess) e = hipMalloc(&cn, nb * 4);
-      if (e == hipSuccess) e = hipMalloc(&t, nb * 4);
+      reqs.push_back({(void**)&h->d_elite_wcost, nb * h->Kp * 4});
+      reqs.push_back({(void**)&h->d_elite_count, nb * 4});
+      reqs.push_back({(void**)&h->d_elite_tau, nb * 4});
     }
-    if (e != hipSuccess) {
-      for (void* x : {(void*)ni, (void*)w, (void*)cn, (void*)t})
-        if (x) (void)hipFree(x);
-      return fail(MPPI_E_HIP, std::string("mppi_set_elites: ") + hipGetErrorString(e));
-    }
+    MPPI_TRY(alloc_group("mppi_set_elites", reqs));
     if (h->d_elite_idx) (void)hipFree(h->d_elite_idx);
     h->d_elite_idx = ni;
-    if (w) {
-      h->d_elite_wcost = w;
-      h->d_elite_count = cn;
-      h->d_elite_tau = t;
-    }
   }
-  for (hipGraphExec_t& g : h->graph_exec)
-    if (g) {
-      HIP_TRY(hipGraphExecDestroy(g));
-      g = nullptr;
-    }
+  MPPI_TRY(drop_graphs(h, false));
   h->elite_n = n_elite;
   h->elite_B = 0;  // the last set had another row length: none to read until the next solve
   return MPPI_OK;
@@ -2202,9 +2154,7 @@ int mppi_elites_eval(mppi_handle* h, int B, const float* costs, int32_t* idx, in
   if (h->elite_n == 0) return fail(MPPI_E_STATE, "mppi_elites_eval: call mppi_set_elites first");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t s = h->stream;
-  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp;
-  // through the staging costs, as mppi_lambda_eval (the pads keep whatever they hold: the kernel never counts them)
-  HIP_TRY(hipMemcpy2DAsync(h->d_costs, Kp * 4, costs, K * 4, K * 4, B, hipMemcpyHostToDevice, s));
+  MPPI_TRY(stage_costs(h, costs, B));  // through the staging costs, as mppi_lambda_eval
   HIP_TRY(timed(h, kElites, [&] { return enqueue_elite(h, B, h->d_costs, 1); }));  // the evaluation's own slot
   HIP_TRY(hipStreamSynchronize(s));
   return copy_elites(h, B, 1, idx, count, tau, ecost);
@@ -2233,7 +2183,7 @@ int mppi_get_stats(mppi_handle* h, int B, int step, mppi_solve_stats* stats, flo
 int mppi_device_stats(mppi_handle* h, void** d_stats, void** d_m2, void** d_m11) {
   if (!h) return fail(MPPI_E_ARG, "mppi_device_stats: null handle");
   HIP_TRY(hipSetDevice(h->device));
-  if (const int rc = ensure_stats(h, 1); rc != MPPI_OK) return rc;
+  MPPI_TRY(ensure_stats(h, 1));
   if (d_stats) *d_stats = h->d_stats;
   if (d_m2) *d_m2 = h->d_stats_m2;
   if (d_m11) *d_m11 = h->d_stats_m11;
@@ -2246,15 +2196,11 @@ int mppi_stats_eval(mppi_handle* h, int B, const float* costs, const float* nois
   const mppi_config& c = h->cfg;
   if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_stats_eval: B out of range [1, max_batch]");
   HIP_TRY(hipSetDevice(h->device));
-  if (const int rc = ensure_stats(h, 1); rc != MPPI_OK) return rc;
+  MPPI_TRY(ensure_stats(h, 1));
   HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
   hipStream_t s = h->stream;
-  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
-  HIP_TRY(hipMemcpy2DAsync(h->d_costs, Kp * 4, costs, K * 4, K * 4, B, hipMemcpyHostToDevice, s));
-  if (noise) {
-    if (K != Kp) HIP_TRY(hipMemsetAsync(h->d_noise, 0, rows * Kp * 4, s));
-    HIP_TRY(hipMemcpy2DAsync(h->d_noise, Kp * 4, noise, K * 4, K * 4, rows, hipMemcpyHostToDevice, s));
-  }
+  MPPI_TRY(stage_costs(h, costs, B));
+  if (noise) MPPI_TRY(stage_noise(h, noise, (size_t)B * c.nu * c.H));
   const int slot = h->stats_slots;  // the evaluation's own slot
   HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, h->d_costs, noise ? h->d_noise : nullptr, slot); }));
   HIP_TRY(hipStreamSynchronize(s));

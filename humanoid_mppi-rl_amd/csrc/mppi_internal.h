@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+#include <cstring>
+
 #include "../../include/mppi.h"
 
 struct NoiseAdapt;  // noise_adapt.h: the settings of mppi_set_noise_adapt
@@ -195,6 +198,19 @@ struct FcNet {
 // drives several GPUs gets each one's own count.  Thread-safe (relaxed atomics; a race only repeats the query).
 int current_device_cus();
 
+// The launchers' environment knobs (read per launch; A/B and test knobs).  env_flag: NAME=0|1 -> 0 / 1, anything else
+// (unset included) -> -1, the launcher's own default.  env_choice: NAME=<one>|<two> -> 1 / 2, anything else -> 0.
+inline int env_flag(const char* name) {
+  const char* e = std::getenv(name);
+  if (!e || (e[0] != '0' && e[0] != '1') || e[1] != '\0') return -1;
+  return e[0] - '0';
+}
+inline int env_choice(const char* name, const char* one, const char* two) {
+  const char* e = std::getenv(name);
+  if (!e) return 0;
+  return std::strcmp(e, one) == 0 ? 1 : (std::strcmp(e, two) == 0 ? 2 : 0);
+}
+
 // The rollout kernel the last fc / FA / cartpole launch on this host thread routed to (mppi_rollout_kernel): set by
 // every launcher, read by the ABI right after the launch (a handle is used from one thread).
 extern thread_local const char* g_rollout_kernel;
@@ -359,11 +375,10 @@ struct CtrlArgs {
   float* lin;           // [B][nu][H] out
   float* term;          // [B][Kp] out (pads K..Kp: 0)
   float* wcost;         // [B][Kp] out: costs + term (pads K..Kp: costs)
-  float* part;          // [ctrl_part_floats] scratch: the split form's per-cell partial sums
+  float* part;          // [term_part_floats (term_cells.h)] scratch: the split form's per-cell partial sums
   CtrlLaw law;
   const float* d_law;   // the device law [kLawFloats] of an adapting handle, or nullptr: `law`
 };
-size_t ctrl_part_floats(int B, int nu, int H, int Kp);
 hipError_t launch_ctrl_cost(const CtrlArgs& a, hipStream_t stream);  // lin, then the term and wcost (one of two forms)
 // kernels_bounds.hip: per-actuator control bounds (mppi_set_control_bounds; the rule: ctrl_bounds.h), by value like
 // SolveArgs (the box travels as a kernel argument: nu <= kMaxNu), so the launches can sit in a captured graph.
@@ -393,10 +408,9 @@ struct RateArgs {
   const float* costs;   // [B][Kp] what the term is added to: the rollout's costs, or costs + control-cost term
   float* term;          // [B][Kp] out (pads K..Kp: 0)
   float* wcost;         // [B][Kp] out: costs + term (pads K..Kp: costs)
-  float* part;          // [rate_part_floats] scratch: the split form's per-cell partial sums
+  float* part;          // [term_part_floats (term_cells.h)] scratch: the split form's per-cell partial sums
   float r[kMaxNu];
 };
-size_t rate_part_floats(int B, int nu, int H, int Kp);
 hipError_t launch_rate_cost(const RateArgs& a, hipStream_t stream);  // the term and wcost (one of two forms)
 hipError_t launch_rate_store_prev(const float* u0, float* u_prev, int n, hipStream_t stream);  // u_prev <- u0 [n]
 hipError_t launch_record(const float* x, const float* u, float* rx, float* ru, int nxB, int nuB, hipStream_t stream);
