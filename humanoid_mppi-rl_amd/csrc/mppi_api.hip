@@ -13,6 +13,7 @@
 
 #include "costs.h"
 #include "ctrl_bounds.h"  // ctrl_bounds_valid
+#include "elite_keep.h"  // (the rule of mppi_set_elite_keep)
 #include "elite_select.h"  // (the rule of mppi_set_elites)
 #include "ess_target.h"  // EssTarget
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
@@ -57,10 +58,11 @@ enum KernelId {
   kBounds = 7,
   kRate = 8,
   kElites = 9,
-  kNumKernels = 10
+  kKeep = 10,
+  kNumKernels = 11
 };
 const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost",
-                                         "bounds", "rate_cost", "elites"};
+                                         "bounds", "rate_cost", "elites", "keep"};
 
 struct PendingEvt {
   int id;
@@ -78,6 +80,7 @@ struct SolveOpts {
   bool bounds = false;  // mppi_set_control_bounds
   bool rate = false;    // mppi_set_rate_cost
   bool elite = false;   // mppi_set_elites
+  bool keep = false;    // mppi_set_elite_keep
 };
 
 }  // namespace
@@ -217,6 +220,25 @@ struct mppi_handle {
   int32_t* d_elite_count = nullptr;  // [2][max_batch]
   float* d_elite_tau = nullptr;      // [2][max_batch]
   int elite_B = 0;                   // batch of the last solve / graph launch with elites (0: none ran)
+  // keep / shift elites (mppi_set_elite_keep; elite_keep.h, kernels_elite_keep.hip).  While keep_n > 0 every solve
+  // injects the stored set into the first columns of its noise ahead of the bounds projection and the rollout
+  // (keep_inject_kernel; count and steps are read on the device, so an empty set changes nothing), and stores its own
+  // n_keep best behind the cost terms and the selection, ahead of the lambda search (a second elite_select launch on
+  // the unmasked chain, or the elites' own set when n_elite == n_keep, then keep_gather_kernel).  The set persists per
+  // batch slot b over max_batch, like u_prev.  All buffers are allocated by mppi_set_elite_keep, two slots each where
+  // an evaluation must not disturb the handle's: slot 0 the handle's set, slot 1 the eval entries'.
+  int keep_n = 0;                    // n_keep (0: off)
+  float* d_keep_v = nullptr;         // [2][max_batch][nu][H][keep_pitch(n_keep)]
+  float* d_keep_cost = nullptr;      // [2][max_batch][n_keep]
+  int32_t* d_keep_idx = nullptr;     // [2][max_batch][n_keep]
+  int32_t* d_keep_count = nullptr;   // [2][max_batch]
+  int32_t* d_keep_steps = nullptr;   // [2][max_batch]
+  int32_t* d_keep_sel = nullptr;     // [max_batch][n_keep] the selection's own idx (scratch: the gather copies it)
+  int32_t* d_keep_selcount = nullptr;  // [max_batch] (scratch)
+  float* d_keep_tau = nullptr;       // [max_batch] (scratch: the selection's threshold, never read)
+  float* d_keep_ecost = nullptr;     // [max_batch][Kp] (scratch: the selection's masked costs, never read)
+  float* d_keep_U = nullptr;         // [max_batch][nu][H] the eval entries' U (the resident d_U stays as it is)
+  int keep_B = 0;                    // slots 0..keep_B hold a set: stored by a solve or written by mppi_set_kept (0: none)
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -417,7 +439,9 @@ void mppi_destroy(mppi_handle* h) {
                   h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist,
                   h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U, h->d_bcounts,
                   h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev,
-                  h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau};
+                  h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
+                  h->d_keep_idx, h->d_keep_count, h->d_keep_steps, h->d_keep_sel, h->d_keep_selcount, h->d_keep_tau,
+                  h->d_keep_ecost, h->d_keep_U};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -931,6 +955,53 @@ static hipError_t enqueue_elite(mppi_handle* h, int B, const float* costs, int s
                              h->d_elite_idx + ob * h->elite_n, h->d_elite_count + ob, h->d_elite_tau + ob, h->stream);
 }
 
+// Keep / shift elites: the launches' arguments for B solves on output / input slot `slot` (0: the handle's set, 1: the
+// eval entries').
+static KeepArgs keep_args(const mppi_handle* h, int B, const float* U, float* noise, int slot) {
+  const mppi_config& c = h->cfg;
+  const size_t ob = (size_t)slot * c.max_batch, n = (size_t)h->keep_n;
+  KeepArgs ka;
+  std::memset(&ka, 0, sizeof(ka));
+  ka.B = B;
+  ka.nu = c.nu;
+  ka.H = c.H;
+  ka.K = c.K;
+  ka.Kp = h->Kp;
+  ka.n_keep = h->keep_n;
+  ka.pitch = keep_pitch(h->keep_n);
+  ka.clamp = c.ctrl_clamp;
+  ka.noise = noise;
+  ka.U = U;
+  ka.v = h->d_keep_v + ob * c.nu * c.H * ka.pitch;
+  ka.kcost = h->d_keep_cost + ob * n;
+  ka.idx = h->d_keep_idx + ob * n;
+  ka.count = h->d_keep_count + ob;
+  ka.steps = h->d_keep_steps + ob;
+  return ka;
+}
+
+// The store of B solves into slot `slot`: the n_keep best of `costs` [B][Kp] (the unmasked end of the wcost chain)
+// selected by elite_select.h's rule -- `shared`: the elites' selection of this solve ran on the same costs with
+// n_elite == n_keep and its set (slot 0 of the elites' buffers) is the kept set; else a second launch of the same
+// kernel into the feature's scratch -- then the gather.
+static hipError_t enqueue_keep_store(mppi_handle* h, int B, const float* U, float* noise, const float* costs, int shift,
+                                     bool shared, int slot) {
+  const mppi_config& c = h->cfg;
+  KeepArgs ka = keep_args(h, B, U, noise, slot);
+  ka.costs = costs;
+  if (shared) {
+    ka.sel_idx = h->d_elite_idx;
+    ka.sel_count = h->d_elite_count;
+  } else {
+    const hipError_t e = launch_elite_select(costs, B, c.K, h->Kp, h->keep_n, h->d_keep_ecost, h->d_keep_sel,
+                                             h->d_keep_selcount, h->d_keep_tau, h->stream);
+    if (e != hipSuccess) return e;
+    ka.sel_idx = h->d_keep_sel;
+    ka.sel_count = h->d_keep_selcount;
+  }
+  return launch_keep_gather(ka, shift, h->stream);
+}
+
 // Validate one solve request against the handle.
 static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if (!h || !io) return fail(MPPI_E_ARG, "mppi_solve: null argument");
@@ -988,6 +1059,7 @@ static SolveOpts solve_opts(const mppi_handle* h, int flags) {
   o.bounds = h->bounds_on;
   o.rate = h->rate_on;
   o.elite = h->elite_n > 0;
+  o.keep = h->keep_n > 0;
   return o;
 }
 
@@ -1008,6 +1080,7 @@ static void note_ran(mppi_handle* h, const SolveOpts& o, int B, int n) {
   if (o.bounds) h->bounds_B = B;
   if (o.rate) h->rate_B = B;
   if (o.elite) h->elite_B = B;
+  if (o.keep && B > h->keep_B) h->keep_B = B;  // (slots beyond B keep the set they hold)
 }
 
 // Enqueue one solve on the handle's stream: inputs, noise, rollout, reduce (+ update, shift), env step, outputs.
@@ -1056,7 +1129,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // o.ctrl: the softmin weighs d_wcost = costs + term; o.rate: d_rate_wcost = (costs [+ control term]) + rate term;
   // o.elite: d_elite_wcost, the chain's end on the elite set (below)
   const SolveOpts o = solve_opts(h, flags);
-  const bool cart_unfused = (lam || o.ctrl || o.rate || o.elite) && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  const bool cart_unfused = (lam || o.ctrl || o.rate || o.elite || o.keep) && h->dyn_kind == MPPI_DYN_CARTPOLE;
   // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths); the cartpole's unfused
   // rollout carries no stamp
   a.kclock = (h->kclock && a.seed_ctr && !cart_unfused) ? h->d_kclock : nullptr;
@@ -1109,6 +1182,15 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     }));
   }
 
+  // keep / shift elites: the stored set into the first columns of this solve's noise, behind whatever filled it -- the
+  // launch above, the copy of an injected io.noise (never the caller's array), or, for ns, the previous solve's fused
+  // generator (reduce_kernel<GEN>, earlier on this stream), its gen_after launch (likewise), the overlap arm's
+  // generator stream (chain_solve waits on ev_gen ahead of this call) or prime_prefetch (on this stream) -- and ahead of
+  // the bounds projection and the rollout.  The x3 probe runs before any of this with buffers of its own and the env
+  // step reads d_env_noise: neither sees the injection.  count and steps are read on the device: the launch is there
+  // for every solve of a handle with the feature on and changes nothing while the set is empty
+  if (o.keep) HIP_TRY(timed(h, kKeep, [&] { return launch_keep_inject(keep_args(h, B, a.U, a.noise, 0), s); }));
+
   // per-actuator bounds: the solve's noise -- drawn above, prefetched by the previous solve's generator, or the copy of
   // an injected io.noise (never the caller's array) -- projected in place against the nominal U, ahead of the rollout
   // and of every other reader of this solve's noise
@@ -1129,7 +1211,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     // (a targeting cartpole too: its fused epilogue forms the softmin partials with lambda before all costs exist, so
     // it runs the unfused rollout of the env step, a.part == nullptr, then the search and reduce_kernel: 3 launches;
     // and a cartpole with the control-cost or the rate term, whose epilogue would weigh costs the term has not reached
-    // yet, or with elites, whose selection needs every cost of the solve)
+    // yet, or with elites or kept elites, whose selection needs every cost of the solve)
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
     h->rollout_kernel = g_rollout_kernel;
     if (o.ctrl) {
@@ -1151,7 +1233,19 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       // elite truncation, behind the terms (it selects on what the softmin would otherwise weigh) and ahead of the lambda
       // search: the search, the reduce and the statistics see the cost on the elite set and +inf elsewhere
       HIP_TRY(timed(h, kElites, [&] { return enqueue_elite(h, B, wcost, 0); }));
-      wcost = h->d_elite_wcost;
+      if (!o.keep) wcost = h->d_elite_wcost;
+    }
+    if (o.keep) {
+      // keep / shift elites: this solve's n_keep best by the unmasked chain (wcost is still the selection's input),
+      // gathered behind the terms and the elites' selection (whose set serves both when n_elite == n_keep) and ahead of
+      // the lambda search and the reduce: a.U is still the nominal the rollout perturbed, a.noise what the rollout saw
+      // (injected, then projected with bounds on).  The gather overwrites the set the injection above read, on the
+      // same stream behind it (its time joins "keep", counted once per solve above)
+      const bool shared = o.elite && h->elite_n == h->keep_n;
+      HIP_TRY(timed(h, kKeep, [&] {
+        return enqueue_keep_store(h, B, a.U, a.noise, wcost, (flags & MPPI_FLAG_SHIFT) != 0, shared, 0);
+      }, 0));
+      if (o.elite) wcost = h->d_elite_wcost;
     }
     if (lam)
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
@@ -2158,6 +2252,179 @@ int mppi_elites_eval(mppi_handle* h, int B, const float* costs, int32_t* idx, in
   HIP_TRY(timed(h, kElites, [&] { return enqueue_elite(h, B, h->d_costs, 1); }));  // the evaluation's own slot
   HIP_TRY(hipStreamSynchronize(s));
   return copy_elites(h, B, 1, idx, count, tau, ecost);
+}
+
+int mppi_set_elite_keep(mppi_handle* h, int n_keep) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_elite_keep: null handle");
+  const mppi_config& c = h->cfg;
+  if (n_keep < 0 || n_keep > c.K) return fail(MPPI_E_ARG, "mppi_set_elite_keep: n_keep must be in [0, K] (0 disables)");
+  if (n_keep == h->keep_n) return MPPI_OK;  // no change: captured graphs and the stored set stay
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state: the captured graphs hold n_keep (or the feature's absence) in their launches, and the set's rows have
+  // n_keep entries; everything in flight finishes first.  A prefetched noise is kept: the injection happens in the
+  // solve that consumes it, the key sequence is unchanged
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (n_keep > 0) {  // the set's buffers by its row length, the rest once; all here, none inside a solve
+    const size_t mb = (size_t)c.max_batch, nb = 2 * mb, n = (size_t)n_keep;
+    const size_t nv = nb * c.nu * c.H * keep_pitch(n_keep) * 4;
+    float *nvp = nullptr, *ncost = nullptr;  // (the old set stays until the new one exists)
+    int32_t *nidx = nullptr, *nsel = nullptr;
+    std::vector<BufReq> reqs{{(void**)&nvp, nv}, {(void**)&ncost, nb * n * 4}, {(void**)&nidx, nb * n * 4},
+                             {(void**)&nsel, mb * n * 4}};
+    if (!h->d_keep_count) {
+      reqs.push_back({(void**)&h->d_keep_count, at_least16(nb * 4)});
+      reqs.push_back({(void**)&h->d_keep_steps, at_least16(nb * 4)});
+      reqs.push_back({(void**)&h->d_keep_selcount, at_least16(mb * 4)});
+      reqs.push_back({(void**)&h->d_keep_tau, at_least16(mb * 4)});
+      reqs.push_back({(void**)&h->d_keep_ecost, mb * h->Kp * 4});
+      reqs.push_back({(void**)&h->d_keep_U, mb * c.nu * c.H * 4});
+    }
+    MPPI_TRY(alloc_group("mppi_set_elite_keep", reqs));
+    void* old[] = {h->d_keep_v, h->d_keep_cost, h->d_keep_idx, h->d_keep_sel};
+    for (void* p : old)
+      if (p) (void)hipFree(p);
+    h->d_keep_v = nvp;
+    h->d_keep_cost = ncost;
+    h->d_keep_idx = nidx;
+    h->d_keep_sel = nsel;
+    // the stored set reads as empty: count = steps = 0 in both slots, v zeroed (cleared ON THE HANDLE'S STREAM and waited
+    // for: a memset on the null stream is not ordered against what the non-blocking stream receives next)
+    HIP_TRY(hipMemsetAsync(h->d_keep_count, 0, nb * 4, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_keep_steps, 0, nb * 4, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d_keep_v, 0, nv, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  MPPI_TRY(drop_graphs(h, false));
+  h->keep_n = n_keep;
+  h->keep_B = 0;  // the last set had another row length: none to read until a solve stores or mppi_set_kept writes one
+  return MPPI_OK;
+}
+
+int mppi_get_elite_keep(mppi_handle* h, int* n_keep) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_elite_keep: null handle");
+  if (n_keep) *n_keep = h->keep_n;
+  return MPPI_OK;
+}
+
+// slot `slot` of the kept set -> host (the stream is idle); each pointer may be nullptr
+static int copy_kept(mppi_handle* h, int B, int slot, float* v, float* kcost, int32_t* idx, int32_t* count,
+                     int32_t* steps) {
+  const mppi_config& c = h->cfg;
+  const size_t ob = (size_t)slot * c.max_batch, n = (size_t)h->keep_n, pitch = (size_t)keep_pitch(h->keep_n);
+  const size_t rows = (size_t)B * c.nu * c.H;
+  if (v)
+    HIP_TRY(hipMemcpy2D(v, n * 4, h->d_keep_v + ob * c.nu * c.H * pitch, pitch * 4, n * 4, rows, hipMemcpyDeviceToHost));
+  if (kcost) HIP_TRY(hipMemcpy(kcost, h->d_keep_cost + ob * n, (size_t)B * n * 4, hipMemcpyDeviceToHost));
+  if (idx) HIP_TRY(hipMemcpy(idx, h->d_keep_idx + ob * n, (size_t)B * n * 4, hipMemcpyDeviceToHost));
+  if (count) HIP_TRY(hipMemcpy(count, h->d_keep_count + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (steps) HIP_TRY(hipMemcpy(steps, h->d_keep_steps + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_get_kept(mppi_handle* h, int B, float* v, float* kcost, int32_t* idx, int32_t* count, int32_t* steps) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_kept: null handle");
+  if (h->keep_B == 0 || h->keep_n == 0)
+    return fail(MPPI_E_STATE, "mppi_get_kept: no solve has stored and no mppi_set_kept has written a set under the "
+                              "current mppi_set_elite_keep setting");
+  if (B < 1 || B > h->keep_B) return fail(MPPI_E_ARG, "mppi_get_kept: B beyond the slots that hold a set");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_kept(h, B, 0, v, kcost, idx, count, steps);
+}
+
+// count [B] in 0..n_keep and steps [B] in 0..H (what mppi_set_kept and mppi_keep_inject_eval accept)
+static bool kept_sizes_valid(const mppi_handle* h, int B, const int32_t* count, const int32_t* steps) {
+  for (int b = 0; b < B; ++b)
+    if (count[b] < 0 || count[b] > h->keep_n || steps[b] < 0 || steps[b] > h->cfg.H) return false;
+  return true;
+}
+
+// host v [B][nu][H][n_keep], count [B], steps [B] -> slot `slot` of the set, on the stream (the caller waits)
+static int upload_kept(mppi_handle* h, int B, int slot, const float* v, const int32_t* count, const int32_t* steps) {
+  const mppi_config& c = h->cfg;
+  const size_t ob = (size_t)slot * c.max_batch, n = (size_t)h->keep_n, pitch = (size_t)keep_pitch(h->keep_n);
+  const size_t rows = (size_t)B * c.nu * c.H;
+  hipStream_t s = h->stream;
+  if (pitch != n) HIP_TRY(hipMemsetAsync(h->d_keep_v + ob * c.nu * c.H * pitch, 0, rows * pitch * 4, s));
+  HIP_TRY(hipMemcpy2DAsync(h->d_keep_v + ob * c.nu * c.H * pitch, pitch * 4, v, n * 4, n * 4, rows,
+                           hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->d_keep_count + ob, count, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->d_keep_steps + ob, steps, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  return MPPI_OK;
+}
+
+int mppi_set_kept(mppi_handle* h, int B, const float* v, const int32_t* count, const int32_t* steps) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_kept: null handle");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_set_kept: B out of range [1, max_batch]");
+  if (h->keep_n == 0) return fail(MPPI_E_STATE, "mppi_set_kept: call mppi_set_elite_keep first");
+  if (v && (!count || !steps)) return fail(MPPI_E_ARG, "mppi_set_kept: count and steps go with v");
+  if (v && !kept_sizes_valid(h, B, count, steps))
+    return fail(MPPI_E_ARG, "mppi_set_kept: count must be in [0, n_keep] and steps in [0, H]");
+  HIP_TRY(hipSetDevice(h->device));
+  // data, not a launch argument: ordered on the stream behind every solve enqueued so far (the set they stored is
+  // replaced), captured graphs stay -- their first solve injects this set when they replay
+  hipStream_t s = h->stream;
+  const size_t n = (size_t)h->keep_n, pitch = (size_t)keep_pitch(h->keep_n), rows = (size_t)B * c.nu * c.H;
+  if (v) {
+    MPPI_TRY(upload_kept(h, B, 0, v, count, steps));
+  } else {  // empty slots 0..B
+    HIP_TRY(hipMemsetAsync(h->d_keep_count, 0, (size_t)B * 4, s));
+    HIP_TRY(hipMemsetAsync(h->d_keep_steps, 0, (size_t)B * 4, s));
+    HIP_TRY(hipMemsetAsync(h->d_keep_v, 0, rows * pitch * 4, s));
+  }
+  // a written set has no costs and no sample indices of a solve: kcost = +inf, idx = -1
+  const std::vector<float> inf((size_t)B * n, INFINITY);
+  const std::vector<int32_t> none((size_t)B * n, -1);
+  HIP_TRY(hipMemcpyAsync(h->d_keep_cost, inf.data(), inf.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(h->d_keep_idx, none.data(), none.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // (the caller's and the local arrays may go)
+  if (B > h->keep_B) h->keep_B = B;
+  return MPPI_OK;
+}
+
+int mppi_keep_store_eval(mppi_handle* h, int B, const float* U, const float* noise, const float* costs, int shift,
+                         float* v, float* kcost, int32_t* idx, int32_t* count, int32_t* steps) {
+  if (!h || !U || !noise || !costs) return fail(MPPI_E_ARG, "mppi_keep_store_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_keep_store_eval: B out of range [1, max_batch]");
+  if (h->keep_n == 0) return fail(MPPI_E_STATE, "mppi_keep_store_eval: call mppi_set_elite_keep first");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t rows = (size_t)B * c.nu * c.H;
+  HIP_TRY(hipMemcpyAsync(h->d_keep_U, U, rows * 4, hipMemcpyHostToDevice, s));
+  MPPI_TRY(stage_noise(h, noise, rows));
+  MPPI_TRY(stage_costs(h, costs, B));
+  // the solve's own kernels (the selection never shared: its scratch is rewritten by every storing solve before it is
+  // read) into the evaluation's slot: the handle's stored set is untouched
+  HIP_TRY(timed(h, kKeep, [&] {
+    return enqueue_keep_store(h, B, h->d_keep_U, h->d_noise, h->d_costs, shift != 0, false, 1);
+  }));
+  HIP_TRY(hipStreamSynchronize(s));
+  return copy_kept(h, B, 1, v, kcost, idx, count, steps);
+}
+
+int mppi_keep_inject_eval(mppi_handle* h, int B, const float* U, const float* noise_in, const float* v,
+                          const int32_t* count, const int32_t* steps, float* noise_out) {
+  if (!h || !U || !noise_in || !v || !count || !steps || !noise_out)
+    return fail(MPPI_E_ARG, "mppi_keep_inject_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_keep_inject_eval: B out of range [1, max_batch]");
+  if (h->keep_n == 0) return fail(MPPI_E_STATE, "mppi_keep_inject_eval: call mppi_set_elite_keep first");
+  if (!kept_sizes_valid(h, B, count, steps))
+    return fail(MPPI_E_ARG, "mppi_keep_inject_eval: count must be in [0, n_keep] and steps in [0, H]");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  HIP_TRY(hipMemcpyAsync(h->d_keep_U, U, rows * 4, hipMemcpyHostToDevice, s));
+  MPPI_TRY(stage_noise(h, noise_in, rows));
+  MPPI_TRY(upload_kept(h, B, 1, v, count, steps));  // the evaluation's slot: the handle's stored set is untouched
+  HIP_TRY(timed(h, kKeep, [&] { return launch_keep_inject(keep_args(h, B, h->d_keep_U, h->d_noise, 1), s); }));
+  HIP_TRY(hipMemcpy2DAsync(noise_out, K * 4, h->d_noise, Kp * 4, K * 4, rows, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MPPI_OK;
 }
 
 // slot `slot` of the diagnostics' buffers -> host (the stream is idle)

@@ -360,6 +360,27 @@ hipError_t launch_lambda_search(const float* costs, int B, int K, int Kp, const 
 // launch, read-only on the costs, capturable.  1 <= n_elite <= K
 hipError_t launch_elite_select(const float* costs, int B, int K, int Kp, int n_elite, float* ecost, int32_t* idx,
                                int32_t* count, float* tau, hipStream_t stream);
+// kernels_elite_keep.hip: keep / shift elites (mppi_set_elite_keep; the rule: elite_keep.h), by value like SolveArgs, so
+// the launches can sit in a captured graph.  The stored set of solve b: v [nu][H][pitch] (pitch = n_keep rounded up to
+// 4), kcost / idx [n_keep], count, steps.
+struct KeepArgs {
+  int B, nu, H, K, Kp;
+  int n_keep, pitch;
+  float clamp;               // cfg.ctrl_clamp (<= 0: none; the gather only)
+  float* noise;              // [B][nu][H][Kp] the gather reads it as the rollout saw it; the injection writes it in place
+  const float* U;            // [B][nu][H] the nominal: the one the rollout perturbed (gather) / will perturb (injection)
+  const float* costs;        // [B][Kp] what the selection ran on (gather only)
+  const int32_t* sel_idx;    // [B][n_keep] the selection's set in ascending k, -1 behind its count (gather only)
+  const int32_t* sel_count;  // [B] (gather only)
+  float* v;                  // [B][nu][H][pitch] the gather's output / the injection's input
+  float* kcost;              // [B][n_keep] out (gather only)
+  int32_t* idx;              // [B][n_keep] out (gather only)
+  int32_t* count;            // [B] gather: out; injection: in, read on the device
+  int32_t* steps;            // [B] likewise
+};
+inline int keep_pitch(int n_keep) { return (n_keep + 3) / 4 * 4; }
+hipError_t launch_keep_gather(const KeepArgs& a, int shift, hipStream_t stream);  // v, kcost, idx, count, steps
+hipError_t launch_keep_inject(const KeepArgs& a, hipStream_t stream);  // eps = v - U on columns < count, rows < steps
 // kernels_ctrl_cost.hip: the control-cost term (mppi_set_control_cost; the rule for lin: control_cost.h), by value
 // like SolveArgs: read-only on the solve's U, noise and costs, so the launches can sit in a captured graph.
 struct CtrlLaw {

@@ -594,6 +594,52 @@ function elites_eval(c::Controller, costs)
 end
 
 """
+    set_elite_keep!(c, n_keep)
+
+Carry the `n_keep` best sampled control sequences of each solve into the next one (mppi_set_elite_keep; iCEM's keep /
+shift elites): gathered on the device, time-shifted when the solve shifts, and injected into the first columns of the
+next solve's noise.  `n_keep` in 1:K enables, 0 disables.  The first solve with the feature on is bit for bit the solve
+without it.  Any change destroys captured graphs and empties the stored set.
+"""
+function set_elite_keep!(c::Controller, n_keep::Integer)
+    check(ccall((:mppi_set_elite_keep, LIB), Cint, (Ptr{Cvoid}, Cint), c.handle, n_keep))
+    return c
+end
+
+"""
+    elite_keep(c) -> Int
+
+`n_keep` of `set_elite_keep!` (mppi_get_elite_keep); 0 while off.
+"""
+function elite_keep(c::Controller)
+    n = Ref{Cint}(0)
+    check(ccall((:mppi_get_elite_keep, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), c.handle, n))
+    return Int(n[])
+end
+
+"""
+    kept(c) -> (v::Array{Float32,3}, kcost::Vector{Float32}, idx::Vector{Int32}, steps::Int)
+
+The set stored by the last solve made with `set_elite_keep!` on (mppi_get_kept; waits for the stream): the planned
+candidate control sequences `v` (nu, H, count) -- entries at steps beyond `steps` are 0 --, their costs, and their
+1-based sample indices in ascending order.
+"""
+function kept(c::Controller)
+    n = max(elite_keep(c), 1)
+    nu, H = c.cfg.nu, c.cfg.H
+    v = zeros(Float32, n, H, nu)  # the engine's [nu][H][n_keep], row-major
+    kcost = zeros(Float32, n)
+    idx = fill(Int32(-1), n)
+    count, steps = Ref{Int32}(0), Ref{Int32}(0)
+    GC.@preserve v kcost idx check(ccall((:mppi_get_kept, LIB), Cint,
+                                         (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ref{Int32},
+                                          Ref{Int32}), c.handle, 1, pointer(v), pointer(kcost), pointer(idx), count,
+                                         steps))
+    m = Int(count[])
+    return (permutedims(v, (3, 2, 1))[:, :, 1:m], kcost[1:m], idx[1:m] .+ Int32(1), Int(steps[]))
+end
+
+"""
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 
 The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and

@@ -32,7 +32,9 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_get_control_cost", "mppi_get_control_term", "mppi_control_term_eval", "mppi_set_control_bounds",
             "mppi_get_control_bounds", "mppi_get_bound_counts", "mppi_bounds_eval", "mppi_set_rate_cost",
             "mppi_get_rate_cost", "mppi_set_prev_control", "mppi_get_prev_control", "mppi_get_rate_term",
-            "mppi_rate_term_eval", "mppi_set_elites", "mppi_get_elites", "mppi_get_elite_set", "mppi_elites_eval"]
+            "mppi_rate_term_eval", "mppi_set_elites", "mppi_get_elites", "mppi_get_elite_set", "mppi_elites_eval",
+            "mppi_set_elite_keep", "mppi_get_elite_keep", "mppi_get_kept", "mppi_set_kept", "mppi_keep_store_eval",
+            "mppi_keep_inject_eval"]
 
 
 class MPPIError(RuntimeError):
@@ -140,6 +142,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_get_elites": (i32, [vp, ctypes.POINTER(i32)]),
         "mppi_get_elite_set": (i32, [vp, i32, vp, vp, vp]),
         "mppi_elites_eval": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+        "mppi_set_elite_keep": (i32, [vp, i32]),
+        "mppi_get_elite_keep": (i32, [vp, ctypes.POINTER(i32)]),
+        "mppi_get_kept": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+        "mppi_set_kept": (i32, [vp, i32, vp, vp, vp]),
+        "mppi_keep_store_eval": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "mppi_keep_inject_eval": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
         "mppi_get_stats": (i32, [vp, i32, i32, vp, vp, vp]),
         "mppi_device_stats": (i32, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]),
         "mppi_stats_eval": (i32, [vp, i32, vp, vp, vp, vp, vp]),

@@ -80,6 +80,9 @@ class MPPIModel:
     n_elite:  weigh only the n_elite best samples of each solve (Engine.set_elites), an int in 1..K: with a large
               lambda_ CEM's elite mean, with ess_target a scale-free softmin over the elites.  0 (default): every
               sample is weighed.
+    n_keep:   carry the n_keep best sampled control sequences of each solve into the next one (Engine.set_elite_keep;
+              iCEM's keep / shift elites), an int in 1..K: mppi_controller's shifting solves carry them time-shifted,
+              mppi_step's as they are.  0 (default): every solve starts from fresh noise alone.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
@@ -87,7 +90,7 @@ class MPPIModel:
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
                  lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, rate_cost=None,
-                 rate_anchor: bool = True, n_elite: int = 0, **overrides):
+                 rate_anchor: bool = True, n_elite: int = 0, n_keep: int = 0, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -109,12 +112,17 @@ class MPPIModel:
         if isinstance(n_elite, bool) or not isinstance(n_elite, (int, np.integer)) or n_elite < 0:
             raise ValueError("MPPIModel: n_elite must be an int in 1..K (0: off)")
         self.n_elite = int(n_elite)
+        if isinstance(n_keep, bool) or not isinstance(n_keep, (int, np.integer)) or n_keep < 0:
+            raise ValueError("MPPIModel: n_keep must be an int in 1..K (0: off)")
+        self.n_keep = int(n_keep)
         self.preset = preset
         self.body_ids = dict(HUMANOID_BODY_IDS if body_ids is None else body_ids)
         self.u0_before = bool(u0_before)
         self.config = Config.preset(preset, precision=precision, **overrides)
         if self.n_elite > self.config.K:
             raise ValueError(f"MPPIModel: n_elite must be an int in 1..K = {self.config.K} (0: off)")
+        if self.n_keep > self.config.K:
+            raise ValueError(f"MPPIModel: n_keep must be an int in 1..K = {self.config.K} (0: off)")
         if self.rate_cost is not None and self.rate_cost.size not in (1, self.config.nu):
             raise ValueError(f"MPPIModel: rate_cost must be a scalar or have nu = {self.config.nu} entries")
         self.engine = Engine(self.config, device)
@@ -166,6 +174,8 @@ class MPPIModel:
             self.engine.set_rate_cost(np.broadcast_to(self.rate_cost, self.config.nu), self.rate_anchor)
         if self.n_elite > 0:
             self.engine.set_elites(self.n_elite)
+        if self.n_keep > 0:
+            self.engine.set_elite_keep(self.n_keep)
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0

@@ -378,6 +378,101 @@ class Engine:
         L.check(self.lib.mppi_elites_eval(self._h, B, _ptr(costs), _ptr(idx), _ptr(count), _ptr(tau), _ptr(ecost)))
         return idx, count, tau, ecost
 
+    # -- keep / shift elites (mppi_set_elite_keep; mppi_hip.stats.keep_store_ref / keep_inject_ref state the rule)
+    def set_elite_keep(self, n_keep: int):
+        """Carry the n_keep best sampled control sequences of each solve into the next one (mppi_set_elite_keep; iCEM's
+        keep / shift elites): gathered on the device behind the rollout and the cost terms, time-shifted when the solve
+        shifts, and injected into the first columns of the next solve's noise ahead of its bounds projection and
+        rollout.  n_keep in 1..K enables, 0 disables.  Works in every stream form with no host round trip; the first
+        solve with the feature on is bit for bit the solve without it.  The analytic cartpole leaves its fused
+        one-launch form while it is on.  Any change destroys captured graphs and empties the stored set; a prefetched
+        noise is kept."""
+        L.check(self.lib.mppi_set_elite_keep(self._h, int(n_keep)))
+        return self
+
+    def elite_keep(self) -> int:
+        """n_keep of mppi_get_elite_keep; 0 while off."""
+        n = ctypes.c_int()
+        L.check(self.lib.mppi_get_elite_keep(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def kept(self, B: int = 1) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(v [B, nu, H, n_keep], kcost [B, n_keep], idx [B, n_keep] int32, count [B] int32, steps [B] int32): the set
+        stored by the last solve enqueued, or written by set_kept (mppi_get_kept; waits for the stream) -- the planned
+        candidate sequences and their costs.  After set_kept, kcost is +inf and idx -1."""
+        c, n = self.config, max(self.elite_keep(), 1)
+        v = np.empty((B, c.nu, c.H, n), np.float32)
+        kcost = np.empty((B, n), np.float32)
+        idx = np.empty((B, n), np.int32)
+        count = np.empty(B, np.int32)
+        steps = np.empty(B, np.int32)
+        L.check(self.lib.mppi_get_kept(self._h, B, _ptr(v), _ptr(kcost), _ptr(idx), _ptr(count), _ptr(steps)))
+        return v, kcost, idx, count, steps
+
+    def _kept_args(self, who, B, v, count, steps):
+        c, n = self.config, self.elite_keep()
+        v = _f32(v)
+        if n == 0 or v.size != B * c.nu * c.H * n:
+            raise ValueError(f"{who}: v must be [B, nu, H, n_keep] = [{B}, {c.nu}, {c.H}, {n}] with the feature on")
+        count = np.ascontiguousarray(np.asarray(count, np.int32)).ravel()
+        steps = np.ascontiguousarray(np.asarray(steps, np.int32)).ravel()
+        if count.size != B or steps.size != B:
+            raise ValueError(f"{who}: count and steps must have B = {B} entries")
+        return v.reshape(B, c.nu, c.H, n), count, steps
+
+    def set_kept(self, v, count=None, steps=None, B: int | None = None):
+        """Write the stored set of slots 0..B (mppi_set_kept): v [B, nu, H, n_keep] candidate control sequences, count
+        [B] in 0..n_keep (default: n_keep) and steps [B] in 0..H (default: H) -- seeds the next solve with sequences of
+        the caller's, or restores a saved set.  v None empties slots 0..B (B default 1).  Data, not a setting: captured
+        graphs stay and their first solve injects this set."""
+        c = self.config
+        if v is None:
+            L.check(self.lib.mppi_set_kept(self._h, 1 if B is None else int(B), None, None, None))
+            return self
+        n = self.elite_keep()
+        v = _f32(v)
+        if B is None:
+            B = v.size // max(c.nu * c.H * max(n, 1), 1)
+        B = int(B)
+        count = np.full(B, n, np.int32) if count is None else count
+        steps = np.full(B, c.H, np.int32) if steps is None else steps
+        v, count, steps = self._kept_args("set_kept", B, v, count, steps)
+        L.check(self.lib.mppi_set_kept(self._h, B, _ptr(v), _ptr(count), _ptr(steps)))
+        return self
+
+    def keep_store_eval(self, U, noise, costs, shift: bool = False):
+        """The selection + gather kernels on host arrays U [B, nu, H], noise [B, nu, H, K] (as the rollout saw it) and
+        costs [B, K] (NaN, +-inf and ties allowed) with the handle's n_keep and ctrl_clamp -> (v, kcost, idx, count,
+        steps) as kept() (mppi_keep_store_eval).  The handle's stored set is untouched.  Needs the feature enabled; no
+        dynamics or cost need be loaded."""
+        c, n = self.config, max(self.elite_keep(), 1)
+        U = _f32(U).reshape(-1, c.nu, c.H)
+        B = U.shape[0]
+        nz = _f32(noise).reshape(B, c.nu, c.H, c.K)
+        costs = _f32(costs).reshape(B, c.K)
+        v = np.empty((B, c.nu, c.H, n), np.float32)
+        kcost = np.empty((B, n), np.float32)
+        idx = np.empty((B, n), np.int32)
+        count = np.empty(B, np.int32)
+        steps = np.empty(B, np.int32)
+        L.check(self.lib.mppi_keep_store_eval(self._h, B, _ptr(U), _ptr(nz), _ptr(costs), int(bool(shift)), _ptr(v),
+                                              _ptr(kcost), _ptr(idx), _ptr(count), _ptr(steps)))
+        return v, kcost, idx, count, steps
+
+    def keep_inject_eval(self, U, noise, v, count, steps) -> np.ndarray:
+        """The inject kernel on host arrays U [B, nu, H], noise [B, nu, H, K], v [B, nu, H, n_keep], count and steps
+        [B] -> the noise the rollout would see [B, nu, H, K] (mppi_keep_inject_eval).  The handle's stored set is
+        untouched.  Needs the feature enabled; no dynamics or cost need be loaded."""
+        c = self.config
+        U = _f32(U).reshape(-1, c.nu, c.H)
+        B = U.shape[0]
+        nz = _f32(noise).reshape(B, c.nu, c.H, c.K)
+        v, count, steps = self._kept_args("keep_inject_eval", B, v, count, steps)
+        out = np.empty_like(nz)
+        L.check(self.lib.mppi_keep_inject_eval(self._h, B, _ptr(U), _ptr(nz), _ptr(v), _ptr(count), _ptr(steps),
+                                               _ptr(out)))
+        return out
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,

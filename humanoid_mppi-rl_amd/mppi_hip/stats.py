@@ -52,6 +52,11 @@ Elite truncation (mppi_set_elites; csrc/elite_select.h is the rule): of the fini
 the n_elite lowest keep their cost, ordered by (cost, k) -- ties at the threshold go to the lower k, -0.0 equals +0.0 --
 and every other sample's becomes +inf.  elite_select_ref is the numpy restatement, a stable argsort: it equals the
 device exactly.
+
+Keep / shift elites (mppi_set_elite_keep; csrc/elite_keep.h is the rule): the n_keep best sampled control sequences of
+a solve, v = clamp(U + eps') taken at step t + shift, are stored and become the first columns of the next solve's noise
+as eps = v - U.  keep_store_ref and keep_inject_ref are the float32 restatements -- one add, the clamp form of
+rate_cost_v, one subtract -- and equal the device bit for bit.
 """
 from __future__ import annotations
 
@@ -460,3 +465,82 @@ def elite_select_ref(costs, n_elite: int):
             tau[b] = c[b, order[m - 1]] + np.float32(0.0)
         ecost[b, members] = c[b, members]
     return (idx[0], count[0], tau[0], ecost[0]) if single else (idx, count, tau, ecost)
+
+
+def keep_store_ref(U, noise, costs, n_keep: int, shift: bool = False, ctrl_clamp: float = 0.0):
+    """The store of mppi_set_elite_keep in float32 (csrc/elite_keep.h), bitwise what the device computes: U [B, nu, H]
+    (or [nu, H]) the nominal the rollout perturbed, noise [B, nu, H, K] (or [nu, H, K]) as the rollout saw it, costs
+    [B, K] (or [K]) what the softmin would weigh ahead of any elite masking ->
+    (v [B, nu, H, n_keep] float32, kcost [B, n_keep] float32, idx [B, n_keep] int32, count [B] int32, steps [B] int32).
+
+        idx, count   = elite_select_ref(costs, n_keep): the n_keep best finite costs by (cost, k), in ascending k
+        steps        = H - shift
+        v[u, t, j]   = float32(U[u, t+shift] + noise[u, t+shift, idx[j]]) for t < steps, j < count, clamped to
+                       +-ctrl_clamp when ctrl_clamp > 0 as csrc/rate_cost.h clamps (c + (s - s): a non-finite sum stays
+                       non-finite); +0.0 everywhere else
+        kcost[j]     = costs[idx[j]] bit for bit, +inf for j >= count
+
+    ValueError on shapes that do not agree or n_keep outside 1..K."""
+    U = np.asarray(U, np.float32)
+    eps = np.asarray(noise, np.float32)
+    c = np.asarray(costs, np.float32)
+    single = U.ndim == 2
+    if single:
+        U, eps, c = U[None], eps[None], c[None]
+    if U.ndim != 3 or eps.ndim != 4 or eps.shape[:3] != U.shape or c.shape != (U.shape[0], eps.shape[3]):
+        raise ValueError("keep_store_ref: need U [B, nu, H], noise [B, nu, H, K] and costs [B, K]")
+    B, nu, H = U.shape
+    K = eps.shape[3]
+    n_keep = int(n_keep)
+    if not 1 <= n_keep <= K:
+        raise ValueError(f"keep_store_ref: n_keep must be in 1..K = {K}")
+    idx, count, _, _ = elite_select_ref(c, n_keep)
+    sh = 1 if shift else 0
+    steps = np.full(B, H - sh, np.int32)
+    v = np.zeros((B, nu, H, n_keep), np.float32)
+    kcost = np.full((B, n_keep), np.inf, np.float32)
+    clamp = np.float32(ctrl_clamp)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(B):
+            m = int(count[b])
+            kcost[b, :m] = c[b, idx[b, :m]]
+            if m == 0 or H - sh == 0:
+                continue
+            s = (U[b][:, sh:, None] + eps[b][:, sh:, :][:, :, idx[b, :m]]).astype(np.float32)
+            if clamp > 0:
+                s = (np.fmin(clamp, np.fmax(-clamp, s)) + (s - s)).astype(np.float32)
+            v[b, :, :H - sh, :m] = s
+    return (v[0], kcost[0], idx[0], count[0], steps[0]) if single else (v, kcost, idx, count, steps)
+
+
+def keep_inject_ref(U, noise, v, count, steps):
+    """The injection of mppi_set_elite_keep in float32 (csrc/elite_keep.h), bitwise what the device computes: U
+    [B, nu, H] (or [nu, H]) the nominal the solve will perturb, noise [B, nu, H, K] (or [nu, H, K]), v [B, nu, H, n_keep]
+    and count / steps [B] (or the row's own) as keep_store_ref returns them -> the noise the rollout sees,
+
+        eps[u, t, j] = float32(v[u, t, j] - U[u, t])     for j < count, t < steps
+
+    and every other element the input's, bit for bit (a copy: the input is not written).  ValueError on shapes that do
+    not agree, count outside 0..n_keep or steps outside 0..H."""
+    U = np.asarray(U, np.float32)
+    out = np.array(noise, np.float32, copy=True)
+    v = np.asarray(v, np.float32)
+    single = U.ndim == 2
+    if single:
+        U, out, v = U[None], out[None], v[None]
+    count = np.atleast_1d(np.asarray(count, np.int64))
+    steps = np.atleast_1d(np.asarray(steps, np.int64))
+    if (U.ndim != 3 or out.ndim != 4 or v.ndim != 4 or out.shape[:3] != U.shape or v.shape[:3] != U.shape
+            or count.shape != (U.shape[0],) or steps.shape != (U.shape[0],)):
+        raise ValueError("keep_inject_ref: need U [B, nu, H], noise [B, nu, H, K], v [B, nu, H, n_keep], count and "
+                         "steps [B]")
+    B, nu, H = U.shape
+    K, n_keep = out.shape[3], v.shape[3]
+    if n_keep > K or ((count < 0) | (count > n_keep)).any() or ((steps < 0) | (steps > H)).any():
+        raise ValueError("keep_inject_ref: need n_keep <= K, count in 0..n_keep and steps in 0..H")
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(B):
+            m, st = int(count[b]), int(steps[b])
+            if m and st:
+                out[b, :, :st, :m] = (v[b, :, :st, :m] - U[b, :, :st, None]).astype(np.float32)
+    return out[0] if single else out

@@ -91,7 +91,12 @@ extern "C" {
  *      Additive, version unchanged: mppi_set_elites / mppi_get_elites / mppi_get_elite_set / mppi_elites_eval (elite
  *      truncation: the softmin weighs only the n_elite best samples of each solve, selected on the device); kernel
  *      name "elites" in mppi_kernel_time.  A handle that never enables it launches exactly the kernels it launched
- *      before, with the same grids and arguments. */
+ *      before, with the same grids and arguments.
+ *      Additive, version unchanged: mppi_set_elite_keep / mppi_get_elite_keep / mppi_get_kept / mppi_set_kept /
+ *      mppi_keep_store_eval / mppi_keep_inject_eval (iCEM's keep / shift elites: the n_keep best sampled control
+ *      sequences of a solve are gathered on the device and injected into the next solve's noise); kernel name "keep"
+ *      in mppi_kernel_time.  A handle that never enables it launches exactly the kernels it launched before, with
+ *      the same grids and arguments. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -569,6 +574,66 @@ int mppi_get_elite_set(mppi_handle* h, int B, int32_t* idx /* [B][n_elite] */, i
 int mppi_elites_eval(mppi_handle* h, int B, const float* costs /* [B][K] host */, int32_t* idx /* [B][n_elite] */,
                      int32_t* count /* [B] */, float* tau /* [B] */, float* ecost /* [B][K] */);
 
+/* Keep / shift elites (iCEM): the n_keep best SAMPLED control sequences of a solve are gathered ON THE DEVICE, held
+ * per handle and batch slot b (as u_prev is), time-shifted when the solve shifts, and injected into the first columns
+ * of the next solve's noise, where they compete again.  Plain, host-pointer, ASYNC, chained, captured-graph and
+ * trajectory-logging streams carry the set with no host round trip.  The rule is csrc/elite_keep.h (host + device);
+ * mppi_hip.stats.keep_store_ref / keep_inject_ref are its numpy restatements, bitwise equal to the device.
+ * STORE (in every solve with the feature on; behind the cost terms and the elites' selection, ahead of the lambda
+ * search and the reduce).  For solve b, with c[0..K) the costs the softmin would weigh AHEAD of any elite masking
+ * (costs [+ control-cost term] [+ rate term]) and eps' the noise as the rollout saw it (projected with bounds on):
+ *     the kept set  = mppi_set_elites' rule with n = n_keep: m = min(n_keep, finite costs), the first m by (c_k, k),
+ *                     idx[b][0..m) in ascending k, idx[b][m..n_keep) = -1   (n_elite == n_keep: one selection serves both)
+ *     shift = 1 with MPPI_FLAG_SHIFT, else 0;  steps[b] = H - shift;  count[b] = m
+ *     v[b][u][t][j] = U[b][u][t+shift] + eps'[b][u][t+shift][idx[j]]   for t < steps, j < m: fp32, one rounding, then the
+ *                     rollouts' clamp to +-ctrl_clamp when ctrl_clamp > 0 -- the control the rollout applied; every
+ *                     other entry is +0.0
+ *     kcost[b][j]   = c[idx[j]] bit for bit, +inf for j >= m
+ * INJECT (at the start of the next solve on slot b; behind whatever filled its noise -- the noise launch, the previous
+ * solve's generator, or the engine's copy of an injected io.noise, never the caller's array -- and ahead of the bounds
+ * projection and the rollout), with U that solve's nominal:
+ *     eps[b][u][t][j] = v[b][u][t][j] - U[b][u][t]    one fp32 subtract, for j < count[b] and t < steps[b]
+ * and every other element untouched, bit for bit: columns count[b].., the pads, and rows t >= steps[b] (after a shift
+ * the last step of a carried sample keeps its freshly drawn noise: iCEM's rule).  count and steps live in device memory
+ * and are read by the kernel, so a captured graph's first solve injects whatever set is stored when it replays.  The set
+ * reads as empty until a solve stores one or mppi_set_kept writes one: the first solve of a handle with the feature on
+ * is bit for bit the solve without it.  mppi_set_U between solves needs no special case: the perturbation is taken
+ * against the nominal in effect.
+ * Everything behind the injection sees the injected eps: the bounds projection, io.costs, the cost terms, the
+ * statistics' moments and so the noise adaptation, and the reduce.  The control-cost term treats a carried column like
+ * any other although those samples were not drawn from the law (iCEM makes the same simplification).  The seed counter
+ * and the key sequence are unchanged.  The analytic cartpole leaves its fused one-launch form while the feature is
+ * on, exactly as for elites.  With K-sharded ranks each rank keeps its own set.
+ * mppi_set_elite_keep: n_keep in 1..K enables, 0 disables; anything else is MPPI_E_ARG and changes nothing.  Any change
+ * destroys captured graphs and empties the stored set (its row length changes); the value already in effect is a no-op
+ * that keeps both.  A prefetched noise is kept (the injection happens in the solve that consumes it).  All buffers are
+ * allocated here, none inside a solve.
+ * mppi_get_elite_keep: *n_keep, 0 while off.
+ * mppi_get_kept: the set stored by the last solve enqueued (or written by mppi_set_kept) -- the planned candidates and
+ * their costs; waits for the stream, each pointer may be NULL.  MPPI_E_STATE before any storing solve or mppi_set_kept
+ * under the n_keep in effect, MPPI_E_ARG for B beyond the slots that hold a set.
+ * mppi_set_kept: host v, count (0..n_keep) and steps (0..H; else MPPI_E_ARG) into slots 0..B, ordered behind enqueued
+ * work: seeds the next solve with candidate sequences of the caller's, or restores a saved set.  v == NULL empties the
+ * slots.  It is data, not a launch argument: it destroys nothing and is allowed between graph launches.  kcost becomes
+ * +inf and idx -1.
+ * mppi_keep_store_eval / mppi_keep_inject_eval: the same selection + gather kernels, and the same inject kernel, on
+ * host arrays with an output slot of their own (the handle's stored set is untouched).  They need only mppi_create and
+ * the feature enabled (MPPI_E_STATE otherwise) and go through the staging noise: a prefetched noise is dropped as by
+ * mppi_stats_eval (key sequence unchanged).  Outputs of the store evaluation may each be NULL. */
+int mppi_set_elite_keep(mppi_handle* h, int n_keep);
+int mppi_get_elite_keep(mppi_handle* h, int* n_keep);
+int mppi_get_kept(mppi_handle* h, int B, float* v /* [B][nu][H][n_keep] */, float* kcost /* [B][n_keep] */,
+                  int32_t* idx /* [B][n_keep] */, int32_t* count /* [B] */, int32_t* steps /* [B] */);
+int mppi_set_kept(mppi_handle* h, int B, const float* v /* [B][nu][H][n_keep] host, or NULL */,
+                  const int32_t* count /* [B] */, const int32_t* steps /* [B] */);
+int mppi_keep_store_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
+                         const float* noise /* [B][nu][H][K] host */, const float* costs /* [B][K] host */, int shift,
+                         float* v, float* kcost, int32_t* idx, int32_t* count, int32_t* steps);
+int mppi_keep_inject_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
+                          const float* noise_in /* [B][nu][H][K] host */, const float* v /* [B][nu][H][n_keep] */,
+                          const int32_t* count /* [B] */, const int32_t* steps /* [B] */,
+                          float* noise_out /* [B][nu][H][K] */);
+
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
  *     eps_m2 [b][u] = 1/H     sum_{t=0..H-1} sum_k w_k eps[b][u][t][k]^2
@@ -623,7 +688,8 @@ int mppi_sync(mppi_handle* h);
  * search of mppi_set_ess_target), "ctrl_cost" (the launches of mppi_set_control_cost, counted as one), "bounds" (the
  * launches of mppi_set_control_bounds ahead of the rollout and behind the update, counted as one per solve),
  * "rate_cost" (the term launches of mppi_set_rate_cost and the store of u_prev, counted as one per solve), "elites"
- * (the selection of mppi_set_elites). */
+ * (the selection of mppi_set_elites), "keep" (the inject, selection and gather launches of mppi_set_elite_keep, counted
+ * as one per solve). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
