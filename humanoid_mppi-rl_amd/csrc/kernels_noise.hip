@@ -8,6 +8,7 @@
 
 #include "mppi_internal.h"
 #include "noise_adapt.h"
+#include "noise_knots.h"
 #include "noise_model.h"
 #include "philox.h"
 
@@ -149,6 +150,92 @@ __global__ __launch_bounds__(256) void noise_ar1_lds_dev_kernel(float* __restric
   noise_ar1_lds_body(inno, noise, nbu, nu, H, Kp, seed, seed_ctr, m);
 }
 
+// ------------------------------------------------------------------------------------------------
+// a1 under a knot law (mppi_set_noise_knots; the rule is noise_knots.h): eps[b][u][t][k] = sigma_u[u] * e[t][k], e the
+// interpolation through the table (kidx, kw: [H][4] taps) of the knot row kn[0..P) = AR(1)(rho) over the normals at
+// counter (k/4, j, u, b), j the knot index.
+// The thread layout of noise_ar1_kernel: one thread = 4 consecutive k of one (b, u), walking t; one 16-B nontemporal
+// store per step into row (b*nu + u)*H + t; the pad lanes K..Kp are written like every other lane.
+// The taps of a step are four consecutive knots around its segment j (noise_knots.h), and j never falls as t grows, so
+// the thread keeps the window W = kn[clamp(jw - 1 .. jw + 2)] of four knot quads in registers and slides it when the
+// table's j passes jw: three moves, and one Philox draw + AR(1) advance while a knot jw + 2 <= P - 1 is left -- P
+// draws per thread instead of H, no array of P knots.  Which window entries a step's taps are is fixed per order:
+// order 3 (W0, W1, W2, W3), order 1 (W1, W2, W1, W1) = (j, j + 1, j, j), order 0 and the one-knot / one-step laws
+// (W1, W1, W1, W1) -- the template parameter, so no select sits in the loop.  t, j and jw are the same in every lane
+// of a block (no divergence); the table is read through the constant address space (scalar loads), one row ahead.
+// What bounds it: the 16 B per thread and step of stores, as for noise_ar1_kernel.
+// No LDS form: noise_ar1_lds_kernel exists because one lane draws H normals one after the other on a grid too small
+// to fill the chip; here a lane draws P <= H, and the H steps behind them are 4 fma and one store each.
+// ------------------------------------------------------------------------------------------------
+typedef float knot_f4 __attribute__((ext_vector_type(4)));
+typedef int knot_i4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) knot_i4* knot_idx_rows;
+typedef const __attribute__((address_space(4))) knot_f4* knot_w_rows;
+
+// kOrder: 3, 1, or 0 (order 0, and every law whose table is idx = one knot, w = (1, 0, 0, 0): P == 1 or H == 1)
+template <int kOrder>
+__global__ __launch_bounds__(256) void noise_knot_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
+                                                         uint64_t seed, const unsigned long long* seed_ctr,
+                                                         NoiseModel m) {
+  const int bu = blockIdx.z * 65535 + blockIdx.y;  // b*nu + u
+  const int kq = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+  if (bu >= nbu || 4 * kq >= Kp) return;
+  const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+  const int u = bu % nu;
+  const int b = bu / nu;
+  const float su = m.sigma_u[u], rho = m.rho, c = m.c;
+  const int last = m.n_knots - 1;
+  const knot_idx_rows kidx = (knot_idx_rows)m.kidx;  // the table is written by the setter only, never during a launch
+  const knot_w_rows kw = (knot_w_rows)m.kw;
+  const int nq = Kp >> 2;
+  knot_f4* dst = reinterpret_cast<knot_f4*>(noise + (long)bu * H * Kp) + kq;  // row t: dst + t * nq
+  int drawn = 0;  // knots 0..drawn-1 exist; `top` is knot drawn - 1
+  knot_f4 top = {0.0f, 0.0f, 0.0f, 0.0f};
+  auto draw = [&]() {  // the next knot of the AR(1) row
+    float z[4];
+    philox_normal4((uint32_t)kq, (uint32_t)drawn, (uint32_t)u, (uint32_t)b, k0, k1, z);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) top[i] = drawn == 0 ? z[i] : ar1_step(rho, c, top[i], z[i]);
+    ++drawn;
+  };
+  // the window at jw = 0: kn[clamp(-1, 0, 1, 2)]
+  draw();
+  knot_f4 w0 = top, w1 = top;
+  if (last >= 1) draw();
+  knot_f4 w2 = top;
+  if (last >= 2) draw();
+  knot_f4 w3 = top;
+  int jw = 0;
+  knot_i4 ix = kidx[0];
+  knot_f4 wt = kw[0];
+  for (int t = 0; t < H; ++t) {
+    const int tn = min(t + 1, H - 1);
+    const knot_i4 ix_next = kidx[tn];  // one row ahead of its use
+    const knot_f4 wt_next = kw[tn];
+    const int j = min(kOrder == 3 ? ix.y : ix.x, last);  // (the table's indices are < n_knots: the draws stay P)
+    while (jw < j) {  // slide: W <- kn[clamp(jw .. jw + 3)]
+      ++jw;
+      w0 = w1, w1 = w2, w2 = w3;
+      if (jw + 2 <= last) {
+        draw();
+        w3 = top;
+      }
+    }
+    const float w[4] = {wt.x, wt.y, wt.z, wt.w};
+    knot_f4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float e = kOrder == 3   ? knot_interp(w, w0[i], w1[i], w2[i], w3[i])
+                      : kOrder == 1 ? knot_interp(w, w1[i], w2[i], w1[i], w1[i])
+                                    : knot_interp(w, w1[i], w1[i], w1[i], w1[i]);
+      v[i] = su * e;
+    }
+    __builtin_nontemporal_store(v, dst + (long)t * nq);
+    ix = ix_next, wt = wt_next;
+  }
+}
+
 // MPPI_NOISE_AR1=direct|lds (read per launch; an A/B and test knob): force one of the two kernels (lds: where its
 // LDS row fits, H <= 256); default: noise_ar1_lds_kernel when noise_ar1_kernel would have fewer waves than SIMDs
 static int ar1_knob() {
@@ -163,6 +250,16 @@ hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64
   if (!model.active) return launch_noise(noise, B, nu, H, Kp, seed, seed_ctr, sigma, stream);
   if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_model refuses such a handle)
   const int nbu = B * nu, nq = Kp / 4;
+  if (model.n_knots > 0) {  // a knot law (mppi_set_noise_knots refuses it on an adapting handle: no device-law form)
+    if (d_law || !model.kidx || !model.kw || model.n_knots > H) return hipErrorInvalidValue;
+    const int threads = nq >= 256 ? 256 : (nq + kWave - 1) / kWave * kWave;
+    const dim3 grid((nq + threads - 1) / threads, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
+    // (one knot or one step: the table is one knot with weight 1 whatever the order)
+    const int order = model.n_knots == 1 || H == 1 ? 0 : model.order;
+    auto* kernel = order == 3 ? noise_knot_kernel<3> : (order == 1 ? noise_knot_kernel<1> : noise_knot_kernel<0>);
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, stream, noise, nbu, nu, H, Kp, seed, seed_ctr, model);
+    return hipGetLastError();
+  }
   const int knob = ar1_knob();
   const long waves = ((long)nbu * nq + kWave - 1) / kWave;
   const bool lds = H <= kAr1LdsMaxH && (knob == 2 || (knob == 0 && waves < 4L * current_device_cus()));

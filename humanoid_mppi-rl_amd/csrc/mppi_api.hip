@@ -21,6 +21,7 @@
 #include "rate_cost.h"  // rate_cost_valid
 #include "term_cells.h"  // term_part_floats
 #include "noise_adapt.h"  // NoiseAdapt
+#include "noise_knots.h"  // knot_table
 #include "noise_model.h"  // ar1_innovation_scale
 
 namespace mppi {
@@ -161,6 +162,12 @@ struct mppi_handle {
   float* d_law_hist = nullptr;
   int hist_slots = 0;
   int law_n = 0;             // history rows of the last adapting solve / graph launch (0: none ran)
+  // the knot law (mppi_set_noise_knots; noise_knots.h, noise_knot_kernel).  noise_model.n_knots / .order are the law;
+  // d_knots holds its table, idx [H][4] int32 then w [H][4] fp32, allocated by the first enabling call and written by
+  // the setter only; knot_idx / knot_w are the host's copy (mppi_get_noise_knots)
+  void* d_knots = nullptr;
+  std::vector<int32_t> knot_idx;
+  std::vector<float> knot_w;
   // ESS targeting (mppi_set_ess_target; ess_target.h, kernels_lambda.hip).  While ess_on, every solve runs
   // lambda_search_kernel between its rollout and its reduce; the reduce and the statistics read the solve's lambda from
   // d_lambda [lambda_slots + 1][max_batch], slot-major like the statistics (a graph's solve i writes slot i; the last
@@ -436,7 +443,7 @@ void mppi_destroy(mppi_handle* h) {
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
-                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist,
+                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist, h->d_knots,
                   h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U, h->d_bcounts,
                   h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev,
                   h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
@@ -1742,12 +1749,17 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
   const bool active = sigma_u != nullptr || rho != 0.0f;
   if (active && nu > kMaxNu)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_model: the model travels as a kernel argument (nu <= 32)");
+  if (!active && h->noise_model.n_knots > 0)
+    return fail(MPPI_E_STATE, "mppi_set_noise_model: (NULL, 0) is the default path, which has no knot law: "
+                              "call mppi_set_noise_knots(h, 0, 0) first");
   HIP_TRY(hipSetDevice(h->device));
   // stale state: a prefetched noise was drawn with the old law (the counter steps back: the key sequence is unchanged),
   // and the captured graphs hold the old model in their kernel arguments (a launch still in flight finishes first)
   HIP_TRY(drop_prefetch(h));
   MPPI_TRY(drop_graphs(h, true));
   NoiseModel m;
+  m.n_knots = h->noise_model.n_knots, m.order = h->noise_model.order;  // the knot law stays (mppi_set_noise_knots)
+  m.kidx = h->noise_model.kidx, m.kw = h->noise_model.kw;
   m.active = active || h->adapt_on ? 1 : 0;  // (an adapting handle's model stays active: (NULL, 0) is its values)
   m.rho = rho;
   m.c = ar1_innovation_scale(rho);
@@ -1780,6 +1792,9 @@ int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigm
   const bool on = rate > 0.0f;
   if (on && h->cfg.nu > kMaxNu)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: the adapted law is an active noise model (nu <= 32)");
+  if (on && h->noise_model.n_knots > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: not together with mppi_set_noise_knots (the moments of "
+                                    "interpolated noise do not estimate sigma_u and rho)");
   if (!on && !h->adapt_on) {  // nothing to disable: only the limits are kept
     h->adapt = NoiseAdapt{0.0f, sigma_min, sigma_max, rho_max};
     return MPPI_OK;
@@ -1850,6 +1865,86 @@ int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active
   return MPPI_OK;
 }
 
+int mppi_set_noise_knots(mppi_handle* h, int n_knots, int order) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_knots: null handle");
+  const mppi_config& c = h->cfg;
+  const bool on = n_knots != 0;
+  if (on && !knot_law_valid(c.H, n_knots, order))
+    return fail(MPPI_E_ARG, "mppi_set_noise_knots: need n_knots in 1..H with order 0, 1 or 3, or n_knots == 0");
+  NoiseModel m = h->noise_model;
+  if (!on && m.n_knots == 0) return MPPI_OK;                                // nothing to disable
+  if (on && m.n_knots == n_knots && m.order == order) return MPPI_OK;  // no change: prefetch and graphs stay
+  if (on && c.nu > kMaxNu)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: a knot law is an active noise model (nu <= 32)");
+  if (on && h->ctrl_gamma > 0.0f)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: not together with mppi_set_control_cost (the term needs the "
+                                    "inverse of the sampling covariance, which a knot law leaves singular)");
+  if (on && h->adapt_on)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: not together with mppi_set_noise_adapt (the moments of "
+                                    "interpolated noise do not estimate sigma_u and rho)");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t n = (size_t)c.H * 4;
+  if (on && !h->d_knots) HIP_TRY(hipMalloc(&h->d_knots, n * (sizeof(int32_t) + sizeof(float))));
+  // stale state, as in mppi_set_noise_model: the prefetched noise (the counter steps back: the key sequence is
+  // unchanged) and the captured graphs, whose generators are those of the other law
+  HIP_TRY(drop_prefetch(h));
+  MPPI_TRY(drop_graphs(h, true));
+  if (on) {
+    std::vector<int32_t> idx(n);
+    std::vector<float> w(n);
+    knot_table(c.H, n_knots, order, idx.data(), w.data());
+    // every launch that reads the table has finished before it changes (the generator stream included: drop_prefetch
+    // made the stream wait for it)
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->d_knots, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((char*)h->d_knots + n * sizeof(int32_t), w.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    h->knot_idx.swap(idx);
+    h->knot_w.swap(w);
+    if (!m.active) {  // the default law as an active model: value for value the same normals
+      m = NoiseModel{};
+      m.active = 1;
+      for (int u = 0; u < c.nu; ++u) m.sigma_u[u] = c.sigma;
+    }
+    m.n_knots = n_knots, m.order = order;
+    m.kidx = (const int32_t*)h->d_knots;
+    m.kw = (const float*)((const char*)h->d_knots + n * sizeof(int32_t));
+  } else {  // sigma_u and rho stay as they stand: the AR(1) generators again
+    m.n_knots = 0, m.order = 0;
+    m.kidx = nullptr, m.kw = nullptr;
+  }
+  h->noise_model = m;
+  return MPPI_OK;
+}
+
+int mppi_get_noise_knots(mppi_handle* h, int* n_knots, int* order, int32_t* idx, float* w) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_knots: null handle");
+  const NoiseModel& m = h->noise_model;
+  if (n_knots) *n_knots = m.n_knots;
+  if (order) *order = m.order;
+  if (m.n_knots > 0) {  // (off: the arrays are left untouched)
+    if (idx) std::memcpy(idx, h->knot_idx.data(), h->knot_idx.size() * sizeof(int32_t));
+    if (w) std::memcpy(w, h->knot_w.data(), h->knot_w.size() * sizeof(float));
+  }
+  return MPPI_OK;
+}
+
+int mppi_noise_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out) {
+  if (!h || !noise_out) return fail(MPPI_E_ARG, "mppi_noise_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_noise_eval: B out of range [1, max_batch]");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  // the generator of a solve's a1 under the law in effect, key = seed (no counter); no projection, no injection
+  HIP_TRY(timed(h, kNoise, [&] {
+    return launch_noise_model(h->d_noise, B, c.nu, c.H, h->Kp, seed, nullptr, c.sigma, h->noise_model, s, gen_law(h));
+  }));
+  HIP_TRY(hipMemcpy2DAsync(noise_out, K * 4, h->d_noise, Kp * 4, K * 4, rows, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MPPI_OK;
+}
+
 int mppi_set_ess_target(mppi_handle* h, float ess_frac, float lambda_min, float lambda_max) {
   if (!h) return fail(MPPI_E_ARG, "mppi_set_ess_target: null handle");
   if (!(ess_frac >= 0.0f && ess_frac <= 1.0f)) return fail(MPPI_E_ARG, "mppi_set_ess_target: ess_frac must be in [0, 1]");
@@ -1912,6 +2007,9 @@ int mppi_set_control_cost(mppi_handle* h, float gamma) {
   if (!(gamma >= 0.0f && std::isfinite(gamma)))
     return fail(MPPI_E_ARG, "mppi_set_control_cost: gamma must be finite and >= 0");
   if (gamma == h->ctrl_gamma) return MPPI_OK;  // no change: captured graphs stay
+  if (gamma > 0.0f && h->noise_model.n_knots > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_control_cost: not together with mppi_set_noise_knots (the term needs the "
+                                    "inverse of the sampling covariance, which a knot law leaves singular)");
   HIP_TRY(hipSetDevice(h->device));
   const mppi_config& c = h->cfg;
   if (gamma > 0.0f && !h->d_wcost) {  // all of the term's buffers, once, or none (every entry is written before it is read)

@@ -278,9 +278,14 @@ struct NoiseModel {
   float rho = 0.0f;
   float c = 1.0f;  // sqrtf(1 - rho*rho), fp32, computed on the host
   float sigma_u[kMaxNu] = {0};
+  // the knot law (mppi_set_noise_knots; noise_knots.h): n_knots = 0: off; else the noise is drawn at n_knots knots and
+  // interpolated through the table (device memory the setter owns: kidx [H][4], kw [H][4])
+  int n_knots = 0, order = 0;
+  const int32_t* kidx = nullptr;
+  const float* kw = nullptr;
 };
 // every explicit generation site: noise_kernel (inactive model, sigma) or, with the model active, noise_ar1_kernel /
-// noise_ar1_lds_kernel (grids too small to fill the chip); kernels_noise.hip.  d_law (or nullptr): the device law of
+// noise_ar1_lds_kernel (grids too small to fill the chip), or noise_knot_kernel (a knot law); kernels_noise.hip.  d_law (or nullptr): the device law of
 // a handle that adapts it on the stream (mppi_set_noise_adapt) -- the same generators reading sigma_u, rho and c from
 // device memory instead of the by-value model (noise_ar1_dev_kernel / noise_ar1_lds_dev_kernel)
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,

@@ -261,6 +261,48 @@ function noise_law(c::Controller; step::Integer = 0)
 end
 
 """
+    set_noise_knots!(c, n_knots; order = 1)
+
+Knot-parameterised sampling noise (mppi_set_noise_knots): the device noise is drawn at `n_knots` knots along the horizon
+(1..H) and interpolated, `order` 0 (hold), 1 (linear) or 3 (Catmull-Rom).  `n_knots = 0` disables and keeps sigma_u and
+rho.  Not together with `set_control_cost!` or `set_noise_adapt!`.
+"""
+function set_noise_knots!(c::Controller, n_knots::Integer; order::Integer = 1)
+    check(ccall((:mppi_set_noise_knots, LIB), Cint, (Ptr{Cvoid}, Cint, Cint), c.handle, n_knots, order))
+    return c
+end
+
+"""
+    noise_knots(c) -> (n_knots, order, idx::Matrix{Int32}, w::Matrix{Float32})
+
+The knot law and its table, four taps per horizon step as (4, H) column-major arrays (mppi_get_noise_knots; 0-based knot
+indices as in C); `n_knots` is 0 and the arrays are zero while the law is off.
+"""
+function noise_knots(c::Controller)
+    n = Ref{Cint}(0)
+    order = Ref{Cint}(0)
+    idx = zeros(Int32, 4, c.cfg.H)
+    w = zeros(Float32, 4, c.cfg.H)
+    GC.@preserve idx w check(ccall((:mppi_get_noise_knots, LIB), Cint,
+                                   (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ptr{Int32}, Ptr{Float32}), c.handle, n, order,
+                                   pointer(idx), pointer(w)))
+    return (Int(n[]), Int(order[]), idx, w)
+end
+
+"""
+    noise_eval(c, seed) -> Array{Float32, 3}
+
+The noise (nu, H, K), column-major as everywhere in this module, that the handle's generator draws for the key `seed`
+under the law in effect (mppi_noise_eval): a solve's noise for that key, ahead of bounds and kept elites.
+"""
+function noise_eval(c::Controller, seed::Integer)
+    nz = zeros(Float32, c.cfg.K, c.cfg.H, c.cfg.nu)   # the C ABI's [nu][H][K]: k fastest
+    GC.@preserve nz check(ccall((:mppi_noise_eval, LIB), Cint, (Ptr{Cvoid}, Cint, UInt64, Ptr{Float32}), c.handle, 1,
+                                UInt64(seed), pointer(nz)))
+    return permutedims(nz, (3, 2, 1))
+end
+
+"""
     set_ess_target!(c, ess_frac; lambda_min = 1e-3, lambda_max = 1e3)
 
 Choose the softmin temperature on the device, per solve, so that the solve's own costs give the effective sample size

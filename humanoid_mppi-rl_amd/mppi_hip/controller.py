@@ -25,7 +25,7 @@ import numpy as np
 from . import _lib as L
 from .engine import Config, Engine
 from .nets import cross_attention_blob, feature_attention_blob, mlp_blob
-from .noise import ar1_filter
+from .noise import ar1_filter, knot_filter
 from .stats import adapt_noise_model
 
 # default cost of each preset (the reference script it mirrors)
@@ -54,6 +54,10 @@ class MPPIModel:
                           (src/cartpole_mppi.py:89), injected into the engine.
     noise_sigma, noise_rho: the sampling law (Engine.set_noise_model): per-actuator standard deviations [nu] (None =
               the preset's sigma) and AR(1) correlation along the horizon; both noise modes sample the same law.
+    noise_knots: None (default), n_knots or (n_knots, order): knot-parameterised noise (Engine.set_noise_knots) -- the
+              law above drawn at n_knots knots along the horizon and interpolated, order 0 (hold), 1 (linear, the
+              default) or 3 (Catmull-Rom); both noise modes sample the same law.  Not together with adapt_noise or
+              control_cost.
     adapt_noise: above 0, mppi_step / mppi_controller request the solve's statistics (Engine.solve(stats=True)) and
               after each step move the law towards the weighted moments of the noise that won
               (stats.adapt_noise_model with this rate and adapt_limits = (sigma_min, sigma_max, rho_max)), through
@@ -90,7 +94,7 @@ class MPPIModel:
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
                  lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, rate_cost=None,
-                 rate_anchor: bool = True, n_elite: int = 0, n_keep: int = 0, **overrides):
+                 rate_anchor: bool = True, n_elite: int = 0, n_keep: int = 0, noise_knots=None, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -158,6 +162,11 @@ class MPPIModel:
         self.noise_rho = float(noise_rho)
         if self._noise_sigma is not None or self._noise_rho != 0.0:
             self.engine.set_noise_model(self._noise_sigma, self._noise_rho)
+        if noise_knots is not None:
+            n_knots, order = (noise_knots, 1) if np.isscalar(noise_knots) else noise_knots
+            if self.adapt_noise > 0.0 or self.control_cost > 0.0:
+                raise ValueError("MPPIModel: noise_knots does not go together with adapt_noise or control_cost")
+            self.engine.set_noise_knots(int(n_knots), int(order))
         if self.device_adapt:
             self.engine.set_noise_adapt(self.adapt_noise, *self.adapt_limits)
         if self.ess_target > 0.0:
@@ -244,6 +253,17 @@ class MPPIModel:
         self._noise_rho = v
 
     @property
+    def noise_knots(self):
+        """(n_knots, order) of the engine's knot law (Engine.noise_knots), or None while it is off."""
+        n, order = self.engine.noise_knots()[:2]
+        return (n, order) if n > 0 else None
+
+    @noise_knots.setter
+    def noise_knots(self, v):
+        n_knots, order = (0, 0) if v is None else ((v, 1) if np.isscalar(v) else v)
+        self.engine.set_noise_knots(int(n_knots), int(order))
+
+    @property
     def K(self):
         return self.config.K
 
@@ -255,6 +275,9 @@ class MPPIModel:
         c = self.config
         if self.noise == "numpy":
             z = np.random.randn(c.nu, c.H, c.K)
+            if self.noise_knots is not None:
+                return knot_filter(z, *self.noise_knots, rho=self.noise_rho,
+                                   sigma_u=c.sigma if self.noise_sigma is None else self.noise_sigma).astype(np.float64)
             if self.noise_sigma is None and self.noise_rho == 0.0:
                 return z * c.sigma
             return ar1_filter(z, self.noise_rho, c.sigma if self.noise_sigma is None else self.noise_sigma)

@@ -147,6 +147,34 @@ class Engine:
         L.check(self.lib.mppi_get_noise_adapt(self._h, *(ctypes.byref(x) for x in v)))
         return tuple(float(x.value) for x in v)
 
+    def set_noise_knots(self, n_knots: int, order: int = 1):
+        """Knot-parameterised sampling noise (mppi_set_noise_knots; noise.knot_table / noise.knot_filter state the
+        law): the device noise is drawn at n_knots knots along the horizon (1..H) and interpolated, order 0 (hold),
+        1 (linear) or 3 (Catmull-Rom).  n_knots = 0 disables and keeps sigma_u and rho.  Makes the noise model active;
+        destroys captured graphs, as set_noise_model does.  Not together with set_control_cost or set_noise_adapt."""
+        L.check(self.lib.mppi_set_noise_knots(self._h, int(n_knots), int(order)))
+        return self
+
+    def noise_knots(self) -> tuple[int, int, np.ndarray | None, np.ndarray | None]:
+        """(n_knots, order, idx [H, 4] int32, w [H, 4] float32) of the handle's knot law (mppi_get_noise_knots);
+        (0, 0, None, None) while off."""
+        H = self.config.H
+        idx, w = np.zeros((H, 4), np.int32), np.zeros((H, 4), np.float32)
+        n, order = ctypes.c_int(), ctypes.c_int()
+        L.check(self.lib.mppi_get_noise_knots(self._h, ctypes.byref(n), ctypes.byref(order), _ptr(idx), _ptr(w)))
+        if n.value == 0:
+            return 0, 0, None, None
+        return int(n.value), int(order.value), idx, w
+
+    def noise_eval(self, B: int, seed: int) -> np.ndarray:
+        """The noise [B, nu, H, K] (float32) the handle's generator draws for the by-value key `seed` under the law in
+        effect (mppi_noise_eval): a solve's noise for that key, ahead of bounds and kept elites.  Drops a prefetched
+        noise (key sequence unchanged); U and every stored state stay."""
+        c = self.config
+        out = np.empty((int(B), c.nu, c.H, c.K), np.float32)
+        L.check(self.lib.mppi_noise_eval(self._h, int(B), ctypes.c_uint64(int(seed) & (2**64 - 1)), _ptr(out)))
+        return out
+
     def noise_law(self, step: int = 0) -> tuple[np.ndarray, float]:
         """(sigma_u [nu], rho) the adapting solve `step` drew its noise from (mppi_get_noise_law; waits for the
         stream): step 0 after a plain or chained solve, 0..n_solves-1 after graph_launch."""

@@ -4,6 +4,9 @@
 
 Every step has unit variance before scaling and corr(e[t], e[s]) = rho^|t-s|.  The device runs the recursion in fp32;
 this restatement is float64 (the reference for tests, and the filter of MPPIModel's noise="numpy" mode).
+
+The knot law (mppi_set_noise_knots; csrc/noise_knots.h) draws the row at P knots and interpolates it to the H steps:
+knot_table and knot_filter restate it in float32, operation by operation, bitwise what the device draws.
 """
 from __future__ import annotations
 
@@ -35,3 +38,97 @@ def ar1_filter(z, rho: float = 0.0, sigma_u=None) -> np.ndarray:
         for t in range(1, H):
             e[..., t, :] = rho * e[..., t - 1, :] + c * z[..., t, :]
     return s[:, None, None] * e
+
+
+# ---- the knot law (include/mppi.h mppi_set_noise_knots; csrc/noise_knots.h), restated bit for bit
+
+def knot_table(H: int, P: int, order: int) -> tuple[np.ndarray, np.ndarray]:
+    """The table of a knot law: (idx [H, 4] int32, w [H, 4] float32), four taps per horizon step.  The numpy
+    restatement of csrc/noise_knots.h knot_table, operation by operation in float64 and rounded to float32 once:
+    bitwise what mppi_get_noise_knots returns.
+
+    order 0 holds knot (t * P) // H; orders 1 (linear) and 3 (uniform Catmull-Rom, clamped ends) interpolate at
+    s = t (P - 1) / (H - 1) between knots j = min(floor(s), P - 2) and j + 1."""
+    H, P, order = int(H), int(P), int(order)
+    if not (1 <= P <= H and order in (0, 1, 3)):
+        raise ValueError("knot_table: need 1 <= P <= H and order in {0, 1, 3}")
+    idx = np.zeros((H, 4), np.int32)
+    w = np.zeros((H, 4), np.float64)
+    t = np.arange(H, dtype=np.int64)
+    if order == 0 or H == 1 or P == 1:
+        idx[:] = ((t * P) // H if order == 0 else 0 * t)[:, None]
+        w[:, 0] = 1.0
+        return idx, w.astype(np.float32)
+    s = (t * (P - 1)).astype(np.float64) / np.float64(H - 1)
+    j = np.minimum(np.floor(s).astype(np.int64), P - 2)
+    a = s - j.astype(np.float64)
+    if order == 1:
+        idx[:] = np.stack([j, j + 1, j, j], axis=1)
+        w[:, 0] = 1.0 - a
+        w[:, 1] = a
+        return idx, w.astype(np.float32)
+    idx[:] = np.clip(np.stack([j - 1, j, j + 1, j + 2], axis=1), 0, P - 1)
+    a2 = a * a
+    a3 = a2 * a
+    w[:, 0] = ((-a3 + 2.0 * a2) - a) * 0.5
+    w[:, 1] = ((3.0 * a3 - 5.0 * a2) + 2.0) * 0.5
+    w[:, 2] = ((-(3.0 * a3) + 4.0 * a2) + a) * 0.5
+    w[:, 3] = (a3 - a2) * 0.5
+    return idx, w.astype(np.float32)
+
+
+def _fma32(a, b, c) -> np.ndarray:
+    """fmaf(a, b, c) of float32 arrays, correctly rounded.  a * b is exact in float64 (48 bits); the sum with c is
+    formed there with its rounding error (TwoSum), and the float64 sum is moved off an exact float32 tie towards the
+    true value before the final rounding: the one case in which rounding twice differs from rounding once."""
+    a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
+    p = a * b
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    f = s.astype(np.float32)
+    d = s - f.astype(np.float64)  # exact
+    g = np.nextafter(f, np.where(d > 0, np.float32(np.inf), np.float32(-np.inf)).astype(np.float32))
+    tie = (d != 0) & (d == g.astype(np.float64) - s) & (err != 0)
+    s = np.where(tie, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+    return s.astype(np.float32)
+
+
+def ar1_filter_f32(z, rho: float = 0.0) -> np.ndarray:
+    """The unit-variance AR(1) row of csrc/noise_model.h in float32, operation by operation, along axis -2 of
+    z [..., H, K]: e[0] = z[0], e[t] = fmaf(rho, e[t-1], c * z[t]), c = sqrtf(1 - rho * rho)."""
+    z = np.asarray(z, np.float32)
+    rho = np.float32(rho)
+    c = np.sqrt(np.float32(1.0) - rho * rho, dtype=np.float32)
+    e = z.copy()
+    for t in range(1, z.shape[-2]):
+        e[..., t, :] = _fma32(rho, e[..., t - 1, :], c * z[..., t, :])
+    return e
+
+
+def knot_filter(z, P: int, order: int, rho: float = 0.0, sigma_u=None) -> np.ndarray:
+    """The knot law over given standard normals z [..., nu, H, K] (float32 result of the same shape): only
+    z[..., :P, :] is read, as the normals of the P knots.  float32 with every fmaf of csrc/noise_knots.h emulated
+    (correctly rounded): bitwise what the device draws (Engine.noise_eval) from the same normals.
+
+        kn = AR(1)(rho) over z[..., :P, :];   e[t] = sum_i w[t][i] kn[idx[t][i]] (in tap order);   eps = sigma_u[u] e[t]
+
+    sigma_u: scalar or [nu] (None = 1)."""
+    z = np.asarray(z, np.float32)
+    if z.ndim < 3:
+        raise ValueError("knot_filter: z must be [..., nu, H, K]")
+    rho = float(rho)
+    if not 0.0 <= rho < 1.0:
+        raise ValueError("knot_filter: rho must be in [0, 1)")
+    nu, H = z.shape[-3], z.shape[-2]
+    idx, w = knot_table(H, P, order)
+    s = np.ones(nu, np.float32) if sigma_u is None else np.asarray(sigma_u, np.float32).ravel()
+    if s.size == 1:
+        s = np.full(nu, s[0], np.float32)
+    if s.shape != (nu,):
+        raise ValueError(f"knot_filter: sigma_u must have {nu} entries, got {s.size}")
+    kn = ar1_filter_f32(z[..., :P, :], rho)
+    e = w[:, 0][:, None] * kn[..., idx[:, 0], :]
+    for i in (1, 2, 3):
+        e = _fma32(w[:, i][:, None], kn[..., idx[:, i], :], e)
+    return (s[:, None, None] * e).astype(np.float32)

@@ -96,7 +96,13 @@ extern "C" {
  *      mppi_keep_store_eval / mppi_keep_inject_eval (iCEM's keep / shift elites: the n_keep best sampled control
  *      sequences of a solve are gathered on the device and injected into the next solve's noise); kernel name "keep"
  *      in mppi_kernel_time.  A handle that never enables it launches exactly the kernels it launched before, with
- *      the same grids and arguments. */
+ *      the same grids and arguments.
+ *      Additive, version unchanged: mppi_set_noise_knots / mppi_get_noise_knots / mppi_noise_eval (knot-parameterised
+ *      sampling noise: the device noise drawn at n_knots knots along the horizon and interpolated, order 0, 1 or 3;
+ *      and the noise the handle's generator draws for a key, on host arrays).  A handle that never enables it launches
+ *      exactly the kernels it launched before, with the same grids.  BEHAVIOUR while a knot law is on only:
+ *      mppi_set_noise_model(NULL, 0) returns MPPI_E_STATE, mppi_set_control_cost(gamma > 0) and
+ *      mppi_set_noise_adapt(rate > 0) return MPPI_E_UNSUPPORTED. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -327,6 +333,55 @@ int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active
 int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigma_max, float rho_max);
 int mppi_get_noise_adapt(mppi_handle* h, float* rate, float* sigma_min, float* sigma_max, float* rho_max);
 int mppi_get_noise_law(mppi_handle* h, int step, float* sigma_u, float* rho);
+
+/* Knot-parameterised sampling noise: the DEVICE noise of one (b, u, k) drawn at P = n_knots knots along the horizon
+ * and interpolated to its H steps (MuJoCo MPC's spline points, STORM's control knots), generated on the device in every
+ * stream form.  The law (n_knots, order), 1 <= n_knots <= H and order in {0, 1, 3}, is part of the handle's sampling
+ * law next to sigma_u and rho; the rule is csrc/noise_knots.h, its numpy restatements mppi_hip.noise.knot_table /
+ * knot_filter (bitwise).
+ *   Table, four taps per step, built once by the setter (in double, rounded to fp32 once), idx[t][4] in 0..P-1, w[t][4]:
+ *     order 0 (hold):   idx[t][.] = (t * P) / H in integers, w = (1, 0, 0, 0)
+ *     H == 1 or P == 1: idx = 0, w = (1, 0, 0, 0)
+ *     otherwise         s = t (P - 1) / (H - 1),  j = min(floor(s), P - 2),  a = s - j
+ *     order 1 (linear): idx = (j, j + 1, j, j),  w = (1 - a, a, 0, 0)
+ *     order 3 (uniform Catmull-Rom, clamped ends): idx = (j - 1, j, j + 1, j + 2) each clamped to [0, P - 1],
+ *                       w = ((-a^3 + 2a^2 - a) / 2, (3a^3 - 5a^2 + 2) / 2, (-3a^3 + 4a^2 + a) / 2, (a^3 - a^2) / 2)
+ *   Knots: z[j], j < P, are the standard normals of the default law at Philox counter (k/4, j, u, b) -- t replaced by
+ *   the knot index, under the key the solve draws anyway -- and kn[0..P) is the handle's AR(1) row over them
+ *   (kn[0] = z[0], kn[j] = fmaf(rho, kn[j-1], c z[j]); rho = 0: independent knots).
+ *   Noise, fp32 in this order:  e[t] = w[t][0] kn[idx[t][0]];  e[t] = fmaf(w[t][i], kn[idx[t][i]], e[t]), i = 1, 2, 3;
+ *   eps[b][u][t][k] = sigma_u[u] e[t].
+ * n_knots == H with order 0 or 1 reproduces the handle's AR(1) / white noise value for value; n_knots == 1 gives rows
+ * constant in t.  VARIANCE: sigma_u is the scale at the knots; between knots the variance of e[t] is sum_i w_i^2 < 1
+ * (0.5 halfway between two knots of order 1), as in MuJoCo MPC and STORM.  eps_m2 of MPPI_FLAG_STATS reports what was
+ * actually drawn.  The dense noise [B][nu][H][Kp] is still written: everything behind the generator (control bounds,
+ * the rate term, elites, kept elites, the ESS target, statistics, the env step, trajectory logging, the seed counter)
+ * works unchanged, and plain, host-pointer, ASYNC, chained, captured-graph and trajectory-logging streams give bit for
+ * bit what a loop of plain counter solves gives.
+ * mppi_set_noise_knots: n_knots in 1..H with order in {0, 1, 3} enables, n_knots == 0 disables (order ignored); anything
+ * else is MPPI_E_ARG and changes nothing.  Enabling makes the noise model active exactly as mppi_set_noise_adapt does
+ * (an inactive one becomes sigma_u = cfg.sigma, rho = 0) and so needs nu <= 32 (MPPI_E_UNSUPPORTED otherwise); the
+ * first enabling call allocates the table's device memory (nothing is allocated inside a solve).  Disabling leaves
+ * sigma_u and rho as they stand (an active model without knots); mppi_set_noise_model(NULL, 0) still returns to the
+ * default path but is refused with MPPI_E_STATE while a knot law is on (disable the knots first); every other
+ * mppi_set_noise_model keeps the knot law.  Any change drops a prefetched noise and destroys captured graphs exactly as
+ * mppi_set_noise_model does; the key sequence is unchanged.  Setting the value already in effect keeps both.
+ * Not together with the control-cost term (it needs the inverse of the sampling covariance, singular for n_knots < H;
+ * n_knots == H is not special-cased) nor with mppi_set_noise_adapt (eps_m2 / eps_m11 of interpolated noise are biased
+ * estimates of sigma^2 and rho): mppi_set_noise_knots with either on, and mppi_set_control_cost(gamma > 0) /
+ * mppi_set_noise_adapt(rate > 0) with a knot law on, return MPPI_E_UNSUPPORTED, change nothing and name the pair in
+ * mppi_last_error.
+ * mppi_get_noise_knots: *n_knots (0 while off), *order, and the table idx [H][4], w [H][4] (written only while a law is
+ * on); each pointer may be NULL.
+ * mppi_noise_eval: the noise the handle's generator draws under the law in effect (default, AR(1), adapted, knots) for
+ * the by-value key `seed` (the seed counter is not added), noise_out [B][nu][H][K] host: exactly a solve's noise for
+ * that key ahead of its bounds projection and kept-elite injection.  Needs only mppi_create.  It goes through the
+ * handle's staging noise: a prefetched noise is dropped as by mppi_stats_eval (key sequence unchanged); U and every
+ * feature's stored state stay untouched. */
+int mppi_set_noise_knots(mppi_handle* h, int n_knots, int order);
+int mppi_get_noise_knots(mppi_handle* h, int* n_knots, int* order, int32_t* idx /* [H][4] or NULL */,
+                         float* w /* [H][4] or NULL */);
+int mppi_noise_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out /* [B][nu][H][K] host */);
 
 /* ESS targeting: the softmin temperature chosen ON THE DEVICE, per solve, so that the solve's own costs give a requested
  * effective sample size -- lambda made scale-free, with no host round trip: plain solves (host or device pointers),
