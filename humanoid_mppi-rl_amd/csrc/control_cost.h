@@ -62,3 +62,22 @@ MPPI_HD void ctrl_lin_row(float gamma, float sigma, float rho, const float* U, f
   const float scale = ctrl_lin_scale(gamma, sigma, rho, H);
   for (int t = 0; t < H; ++t) lin[t] = ctrl_lin_entry(scale, rho, U, t, H);
 }
+
+// Under a cross-actuator covariance (mppi_set_noise_cov; noise_cov.h) the law's covariance is Sigma (x) C, so
+//   lin[u][t] = gamma * sum_v Sinv[u][v] * (P U[v][:])[t]
+// in fp32 and in this fixed order, with pv_v[t] = ctrl_lin_entry(1.0f, rho, U[v][:], t, H) = (P U_v)[t] (1 - rho^2):
+//   om = H > 1 ? fmaf(-rho, rho, 1) : 1;    scale0 = gamma / om
+//   acc = Sinv[u][0] * pv_0[t];    acc = fmaf(Sinv[u][v], pv_v[t], acc)   v = 1..nu-1;    lin[u][t] = scale0 * acc
+// Roundings: 3 u of its majorant A_v on each pv_v, one per product / fmaf of the sum, 2 u on scale0, 1 u on the last
+// product: |lin_f32 - lin_f64| <= (nu + 8) u * scale0 * sum_v |Sinv[u][v]| A_v.
+// Ub: the solve's U [nu][H]; Sinv_row: row u of Sinv [nu][nu]
+MPPI_HD float ctrl_lin_cov_entry(float gamma, float rho, const float* Sinv_row, int nu, const float* Ub, int t, int H) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float om = H > 1 ? fmaf(-rho, rho, 1.0f) : 1.0f;
+  const float scale0 = gamma / om;
+  float acc = Sinv_row[0] * ctrl_lin_entry(1.0f, rho, Ub, t, H);
+  for (int v = 1; v < nu; ++v) acc = fmaf(Sinv_row[v], ctrl_lin_entry(1.0f, rho, Ub + (long)v * H, t, H), acc);
+  return scale0 * acc;
+}

@@ -1,5 +1,6 @@
 // The control-cost term of information-theoretic MPPI (mppi_set_control_cost; the rule for lin is control_cost.h):
 //   lin  [b][u][t] = gamma / sigma_u[u]^2 * (P U[b][u][:])[t]          ctrl_lin_kernel (B nu H values: tiny)
+//                    under mppi_set_noise_cov: gamma * sum_v Sinv[u][v] (P U[b][v][:])[t]
 //   term [b][k]    = sum_{u,t} lin[b][u][t] * eps[b][u][t][k]          ctrl_term_*_kernel (the whole noise once: the hot part)
 //   wcost[b][k]    = costs[b][k] + term[b][k]                          (pads K..Kp: costs copied through, term 0)
 // Two launches (three in the split form) between the rollout and everything that weighs the solve's costs; read-only
@@ -17,6 +18,11 @@ __global__ __launch_bounds__(256) void ctrl_lin_kernel(CtrlArgs a) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.B * a.nu * a.H) return;
   const int bu = i / a.H, t = i - bu * a.H, u = bu % a.nu;
+  if (a.sinv) {  // a cross-actuator covariance: the row of Sigma^-1 over every actuator's P U (never with d_law)
+    // (Sinv is written by the setter only, never during a launch)
+    a.lin[i] = ctrl_lin_cov_entry(a.law.gamma, a.law.rho, a.sinv + u * a.nu, a.nu, a.U + (long)(bu - u) * a.H, t, a.H);
+    return;
+  }
   const float sigma = a.d_law ? a.d_law[u] : (a.law.per_u ? a.law.sigma_u[u] : a.law.sigma);
   const float rho = a.d_law ? a.d_law[kLawRho] : a.law.rho;
   a.lin[i] = ctrl_lin_entry(ctrl_lin_scale(a.law.gamma, sigma, rho, a.H), rho, a.U + (long)bu * a.H, t, a.H);

@@ -1,6 +1,8 @@
 // The configurable sampling law (mppi_set_noise_model): per-actuator scale and AR(1) correlation along the horizon.
 // The law itself is noise_model.h; the default law (white noise of one sigma) stays noise_kernel and the fused
 // generators of kernels_common.hip / kernels_cartpole.hip.
+// Two laws build on it: knots along the horizon (mppi_set_noise_knots; noise_knots.h, noise_knot_kernel) and a full
+// covariance across the actuators (mppi_set_noise_cov; noise_cov.h, noise_cov_kernel).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -8,6 +10,7 @@
 
 #include "mppi_internal.h"
 #include "noise_adapt.h"
+#include "noise_cov.h"
 #include "noise_knots.h"
 #include "noise_model.h"
 #include "philox.h"
@@ -236,6 +239,120 @@ __global__ __launch_bounds__(256) void noise_knot_kernel(float* __restrict__ noi
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// a1 under a cross-actuator covariance (mppi_set_noise_cov; the rule is noise_cov.h): eps[b][u][t][k] =
+// sum_{v <= u} L[u][v] e_v[t][k], e_v the unit-variance AR(1) row of actuator v over the normals at counter
+// (k/4, t, v, b) -- what noise_ar1_kernel draws for (b, v) before its scale.  One pass over the noise buffer: the
+// rows e_v never leave the CU.
+// A block owns one b and 64 k-quads (256 k); lane = k-quad, as in noise_ar1_kernel, so every store is the same 16-B
+// nontemporal store, 1 KiB contiguous per wave and (u, t).  Its waves are drawers and mixers, one step apart:
+//   drawers (nd = min(nu, 8) waves): wave d advances the rows v = d, d + nd, ... (at most kCovRows = 4, unrolled: the
+//          chain state stays in registers, no indexed register array) to step s and writes e[v][lane] as 16-B quads
+//          into LDS buffer s & 1 (consecutive lanes hold consecutive 16 B: ds_write_b128 / ds_read_b128 without bank
+//          conflicts);
+//   mixers (nm = min(ceil(nu / 2), 8) waves): in the same pass of the loop a mixer forms, for step s - 1 out of buffer
+//          (s - 1) & 1, the output rows of its pairs (2p, 2p + 1), walking v = 0..2p: two rows per LDS read (half the
+//          LDS traffic of the triangle), 8 fmaf per read, L through the constant address space (scalar loads: the wave
+//          index and p are wave-uniform).  The pairs go to the mixers longest first in serpentine order.
+// One barrier per step: behind it the drawers overwrite the buffer the mixers have just left.  The Philox / Box-Muller
+// work of step s (VALU) and the LDS and scalar-load latencies of the mix of step s - 1 overlap on every SIMD (a CU
+// holds one such block at config #4: 256 blocks), which a block whose waves all draw, then all mix, cannot do.
+// LDS: 2 nu KiB (42 KiB at nu = 21, 64 KiB at the limit nu = 32: at least two blocks per CU).  L's rows are padded to
+// kMaxNu floats: every row starts 128-B aligned.
+// The operations per element are cov_mix's in cov_mix's order: host and device agree bit for bit.
+// Lanes past Kp (the last block along k when Kp / 4 is no multiple of 64) draw and store nothing but meet every barrier.
+// ------------------------------------------------------------------------------------------------
+constexpr int kCovWaves = 8;                  // drawers at most, and mixers at most
+constexpr int kCovRows = kMaxNu / kCovWaves;  // AR(1) rows a drawer advances at most
+typedef const __attribute__((address_space(4))) float* cov_factor_rows;
+
+__global__ __launch_bounds__(2 * kCovWaves * kWave) void noise_cov_kernel(float* __restrict__ noise, int B, int nu,
+                                                                           int H, int Kp, uint64_t seed,
+                                                                           const unsigned long long* seed_ctr,
+                                                                           NoiseModel m) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  extern __shared__ __attribute__((aligned(16))) float cov_lds[];  // [2][nu][kWave] quads
+  const int b = blockIdx.z * 65535 + blockIdx.y;
+  if (b >= B) return;  // (uniform per block: before any barrier)
+  const int lane = threadIdx.x & (kWave - 1);
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int nd = nu < kCovWaves ? nu : kCovWaves;  // drawers: waves 0..nd-1
+  const int nm = blockDim.x / kWave - nd;          // mixers: waves nd..nd+nm-1
+  const int kq = blockIdx.x * kWave + lane;
+  const bool live = 4 * kq < Kp;
+  knot_f4* lds = reinterpret_cast<knot_f4*>(cov_lds) + lane;  // e_v of step s: lds[((s & 1) * nu + v) * kWave]
+  if (w < nd) {
+    const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+    const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+    const float rho = m.rho, c = m.c;
+    knot_f4 e[kCovRows];
+#pragma unroll
+    for (int r = 0; r < kCovRows; ++r) e[r] = knot_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s = 0; s <= H; ++s) {
+      if (live && s < H) {
+        knot_f4* buf = lds + (s & 1) * nu * kWave;
+#pragma unroll
+        for (int r = 0; r < kCovRows; ++r) {
+          const int v = w + r * nd;
+          if (v < nu) {
+            float z[4];
+            philox_normal4((uint32_t)kq, (uint32_t)s, (uint32_t)v, (uint32_t)b, k0, k1, z);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) e[r][i] = s == 0 ? z[i] : ar1_step(rho, c, e[r][i], z[i]);
+            buf[v * kWave] = e[r];
+          }
+        }
+      }
+      __syncthreads();
+    }
+    return;
+  }
+  const int wm = w - nd;
+  const cov_factor_rows L = (cov_factor_rows)m.cov_L;  // [nu][kMaxNu]; written by the setter only, never during a launch
+  const int nq = Kp >> 2;
+  const long row_q = (long)H * nq;  // quads per (b, u)
+  knot_f4* dst = reinterpret_cast<knot_f4*>(noise) + (long)b * nu * row_q + kq;  // (u, t): dst + u * row_q + t * nq
+  const int np = (nu + 1) >> 1;     // pairs of output rows
+  for (int s = 0; s <= H; ++s) {
+    if (live && s > 0) {
+      const int t = s - 1;
+      const knot_f4* buf = lds + (t & 1) * nu * kWave;
+      for (int g = 0; g * nm < np; ++g) {
+        const int p = np - 1 - (g * nm + ((g & 1) ? nm - 1 - wm : wm));
+        if (p < 0) break;
+        const int ua = 2 * p, ub = ua + 1;
+        const bool two = ub < nu;
+        const cov_factor_rows La = L + ua * kMaxNu, Lb = L + (two ? ub : ua) * kMaxNu;
+        knot_f4 ev = buf[0];
+        knot_f4 acc_a, acc_b;
+        {
+          const float la = La[0], lb = Lb[0];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc_a[i] = la * ev[i], acc_b[i] = lb * ev[i];
+        }
+#pragma unroll 4
+        for (int v = 1; v <= ua; ++v) {
+          ev = buf[v * kWave];
+          const float la = La[v], lb = Lb[v];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc_a[i] = fmaf(la, ev[i], acc_a[i]), acc_b[i] = fmaf(lb, ev[i], acc_b[i]);
+        }
+        __builtin_nontemporal_store(acc_a, dst + ua * row_q + (long)t * nq);
+        if (two) {
+          ev = buf[ub * kWave];
+          const float lb = Lb[ub];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc_b[i] = fmaf(lb, ev[i], acc_b[i]);
+          __builtin_nontemporal_store(acc_b, dst + ub * row_q + (long)t * nq);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // MPPI_NOISE_AR1=direct|lds (read per launch; an A/B and test knob): force one of the two kernels (lds: where its
 // LDS row fits, H <= 256); default: noise_ar1_lds_kernel when noise_ar1_kernel would have fewer waves than SIMDs
 static int ar1_knob() {
@@ -250,6 +367,15 @@ hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64
   if (!model.active) return launch_noise(noise, B, nu, H, Kp, seed, seed_ctr, sigma, stream);
   if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_model refuses such a handle)
   const int nbu = B * nu, nq = Kp / 4;
+  if (model.cov_L) {  // a cross-actuator covariance (mppi_set_noise_cov refuses it beside a knot law or an adapted one)
+    if (d_law || model.n_knots > 0) return hipErrorInvalidValue;
+    const int nd = nu < kCovWaves ? nu : kCovWaves, np = (nu + 1) / 2;  // drawers and mixers (noise_cov_kernel)
+    const int nm = np < kCovWaves ? np : kCovWaves;
+    const dim3 grid((nq + kWave - 1) / kWave, B < 65535 ? B : 65535, (B + 65534) / 65535);
+    hipLaunchKernelGGL(noise_cov_kernel, grid, dim3((nd + nm) * kWave), (size_t)2 * nu * kWave * 4 * sizeof(float),
+                       stream, noise, B, nu, H, Kp, seed, seed_ctr, model);
+    return hipGetLastError();
+  }
   if (model.n_knots > 0) {  // a knot law (mppi_set_noise_knots refuses it on an adapting handle: no device-law form)
     if (d_law || !model.kidx || !model.kw || model.n_knots > H) return hipErrorInvalidValue;
     const int threads = nq >= 256 ? 256 : (nq + kWave - 1) / kWave * kWave;

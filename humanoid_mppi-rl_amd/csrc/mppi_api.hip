@@ -21,6 +21,7 @@
 #include "rate_cost.h"  // rate_cost_valid
 #include "term_cells.h"  // term_part_floats
 #include "noise_adapt.h"  // NoiseAdapt
+#include "noise_cov.h"    // cov_factor
 #include "noise_knots.h"  // knot_table
 #include "noise_model.h"  // ar1_innovation_scale
 
@@ -168,6 +169,11 @@ struct mppi_handle {
   void* d_knots = nullptr;
   std::vector<int32_t> knot_idx;
   std::vector<float> knot_w;
+  // the cross-actuator covariance (mppi_set_noise_cov; noise_cov.h, noise_cov_kernel).  noise_model.cov_L != nullptr
+  // is the law; d_cov holds L [nu][kMaxNu] (rows padded) then Sinv [nu][nu], allocated by the first enabling call and written by the
+  // setter only; cov_host is the host's copy, Sigma, L, Sinv [nu][nu] each (mppi_get_noise_cov)
+  float* d_cov = nullptr;
+  std::vector<float> cov_host;
   // ESS targeting (mppi_set_ess_target; ess_target.h, kernels_lambda.hip).  While ess_on, every solve runs
   // lambda_search_kernel between its rollout and its reduce; the reduce and the statistics read the solve's lambda from
   // d_lambda [lambda_slots + 1][max_batch], slot-major like the statistics (a graph's solve i writes slot i; the last
@@ -443,7 +449,7 @@ void mppi_destroy(mppi_handle* h) {
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
-                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist, h->d_knots,
+                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist, h->d_knots, h->d_cov,
                   h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U, h->d_bcounts,
                   h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev,
                   h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
@@ -899,6 +905,7 @@ static hipError_t enqueue_ctrl(mppi_handle* h, int B, const float* U, const floa
   ca.law.per_u = m.active;
   if (m.active) std::memcpy(ca.law.sigma_u, m.sigma_u, sizeof(ca.law.sigma_u));
   ca.d_law = gen_law(h);
+  ca.sinv = m.cov_L ? h->d_cov + (size_t)c.nu * kMaxNu : nullptr;
   return launch_ctrl_cost(ca, h->stream);
 }
 
@@ -1752,6 +1759,12 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
   if (!active && h->noise_model.n_knots > 0)
     return fail(MPPI_E_STATE, "mppi_set_noise_model: (NULL, 0) is the default path, which has no knot law: "
                               "call mppi_set_noise_knots(h, 0, 0) first");
+  if (h->noise_model.cov_L && !active)
+    return fail(MPPI_E_STATE, "mppi_set_noise_model: (NULL, 0) is the default path, which has no covariance: "
+                              "call mppi_set_noise_cov(h, NULL) first");
+  if (h->noise_model.cov_L && sigma_u)
+    return fail(MPPI_E_STATE, "mppi_set_noise_model: the scales are the covariance's while mppi_set_noise_cov is on: "
+                              "pass sigma_u = NULL (rho alone), or call mppi_set_noise_cov(h, NULL) first");
   HIP_TRY(hipSetDevice(h->device));
   // stale state: a prefetched noise was drawn with the old law (the counter steps back: the key sequence is unchanged),
   // and the captured graphs hold the old model in their kernel arguments (a launch still in flight finishes first)
@@ -1760,11 +1773,13 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
   NoiseModel m;
   m.n_knots = h->noise_model.n_knots, m.order = h->noise_model.order;  // the knot law stays (mppi_set_noise_knots)
   m.kidx = h->noise_model.kidx, m.kw = h->noise_model.kw;
+  m.cov_L = h->noise_model.cov_L;  // ... and so does the covariance (mppi_set_noise_cov): only rho changes under it
   m.active = active || h->adapt_on ? 1 : 0;  // (an adapting handle's model stays active: (NULL, 0) is its values)
   m.rho = rho;
   m.c = ar1_innovation_scale(rho);
   if (m.active)
-    for (int u = 0; u < nu; ++u) m.sigma_u[u] = sigma_u ? sigma_u[u] : h->cfg.sigma;
+    for (int u = 0; u < nu; ++u)
+      m.sigma_u[u] = sigma_u ? sigma_u[u] : (m.cov_L ? h->noise_model.sigma_u[u] : h->cfg.sigma);
   if (h->adapt_on) HIP_TRY(launch_noise_law_set(h->d_law, m, h->stream));  // the device law starts again from here
   h->noise_model = m;
   return MPPI_OK;
@@ -1795,6 +1810,9 @@ int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigm
   if (on && h->noise_model.n_knots > 0)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: not together with mppi_set_noise_knots (the moments of "
                                     "interpolated noise do not estimate sigma_u and rho)");
+  if (on && h->noise_model.cov_L)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: not together with mppi_set_noise_cov (the rule adapts "
+                                    "sigma_u, which is not the law under a full covariance)");
   if (!on && !h->adapt_on) {  // nothing to disable: only the limits are kept
     h->adapt = NoiseAdapt{0.0f, sigma_min, sigma_max, rho_max};
     return MPPI_OK;
@@ -1882,6 +1900,9 @@ int mppi_set_noise_knots(mppi_handle* h, int n_knots, int order) {
   if (on && h->adapt_on)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: not together with mppi_set_noise_adapt (the moments of "
                                     "interpolated noise do not estimate sigma_u and rho)");
+  if (on && m.cov_L)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: not together with mppi_set_noise_cov (the knot generator "
+                                    "does not mix the actuators)");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)c.H * 4;
   if (on && !h->d_knots) HIP_TRY(hipMalloc(&h->d_knots, n * (sizeof(int32_t) + sizeof(float))));
@@ -1924,6 +1945,74 @@ int mppi_get_noise_knots(mppi_handle* h, int* n_knots, int* order, int32_t* idx,
   if (m.n_knots > 0) {  // (off: the arrays are left untouched)
     if (idx) std::memcpy(idx, h->knot_idx.data(), h->knot_idx.size() * sizeof(int32_t));
     if (w) std::memcpy(w, h->knot_w.data(), h->knot_w.size() * sizeof(float));
+  }
+  return MPPI_OK;
+}
+
+int mppi_set_noise_cov(mppi_handle* h, const float* Sigma) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_cov: null handle");
+  const mppi_config& c = h->cfg;
+  const size_t nn = (size_t)c.nu * c.nu;
+  NoiseModel m = h->noise_model;
+  if (!Sigma && !m.cov_L) return MPPI_OK;  // nothing to disable
+  std::vector<float> host;
+  if (Sigma) {
+    if (c.nu > kMaxNu)
+      return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov: a covariance is an active noise model (nu <= 32)");
+    host.resize(3 * nn);
+    std::vector<double> scratch(3 * nn);
+    float sig[kMaxNu];
+    std::memcpy(host.data(), Sigma, nn * sizeof(float));
+    if (!cov_factor(Sigma, c.nu, host.data() + nn, host.data() + 2 * nn, sig, scratch.data(), scratch.data() + nn))
+      return fail(MPPI_E_ARG, "mppi_set_noise_cov: Sigma must be finite, symmetric bit for bit and positive definite "
+                              "(every Cholesky pivot > 0)");
+    // the value in effect, bitwise: prefetch and graphs stay
+    if (m.cov_L && std::memcmp(host.data(), h->cov_host.data(), nn * sizeof(float)) == 0) return MPPI_OK;
+    if (m.n_knots > 0)
+      return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov: not together with mppi_set_noise_knots (the knot generator "
+                                      "does not mix the actuators)");
+    if (h->adapt_on)
+      return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov: not together with mppi_set_noise_adapt (the rule adapts "
+                                      "sigma_u, which is not the law under a full covariance)");
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->d_cov) HIP_TRY(hipMalloc(&h->d_cov, ((size_t)c.nu * kMaxNu + nn) * sizeof(float)));
+    if (!m.active) {  // the default law as an active model: rho = 0, the same normals
+      const NoiseModel none{};
+      m.active = 1, m.rho = none.rho, m.c = none.c;
+    }
+    for (int u = 0; u < c.nu; ++u) m.sigma_u[u] = sig[u];
+  } else {
+    HIP_TRY(hipSetDevice(h->device));
+  }
+  // stale state, as in mppi_set_noise_model: the prefetched noise (the counter steps back: the key sequence is
+  // unchanged) and the captured graphs, whose generators are those of the other law
+  HIP_TRY(drop_prefetch(h));
+  MPPI_TRY(drop_graphs(h, true));
+  if (Sigma) {
+    // every launch that reads L or Sinv has finished before they change (the generator stream included: drop_prefetch
+    // made the stream wait for it)
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy2D(h->d_cov, kMaxNu * sizeof(float), host.data() + nn, c.nu * sizeof(float), c.nu * sizeof(float),
+                        c.nu, hipMemcpyHostToDevice));  // (the pad of a row is never read)
+    HIP_TRY(hipMemcpy(h->d_cov + (size_t)c.nu * kMaxNu, host.data() + 2 * nn, nn * sizeof(float), hipMemcpyHostToDevice));
+    h->cov_host.swap(host);
+    m.cov_L = h->d_cov;
+  } else {  // sigma_u (= sqrt of the diagonal) and rho stay as they stand: the AR(1) generators again
+    m.cov_L = nullptr;
+  }
+  h->noise_model = m;
+  return MPPI_OK;
+}
+
+int mppi_get_noise_cov(mppi_handle* h, float* Sigma, float* L, float* Sinv, int* active) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_cov: null handle");
+  const bool on = h->noise_model.cov_L != nullptr;
+  if (active) *active = on ? 1 : 0;
+  if (on) {  // (off: the arrays are left untouched)
+    const size_t nn = (size_t)h->cfg.nu * h->cfg.nu;
+    if (Sigma) std::memcpy(Sigma, h->cov_host.data(), nn * sizeof(float));
+    if (L) std::memcpy(L, h->cov_host.data() + nn, nn * sizeof(float));
+    if (Sinv) std::memcpy(Sinv, h->cov_host.data() + 2 * nn, nn * sizeof(float));
   }
   return MPPI_OK;
 }

@@ -283,9 +283,13 @@ struct NoiseModel {
   int n_knots = 0, order = 0;
   const int32_t* kidx = nullptr;
   const float* kw = nullptr;
+  // the cross-actuator covariance (mppi_set_noise_cov; noise_cov.h): nullptr: off; else the factor L [nu][kMaxNu] (device
+  // memory the setter owns) that mixes the unit-variance AR(1) rows; sigma_u is then sqrt(diag Sigma) and not read
+  const float* cov_L = nullptr;
 };
 // every explicit generation site: noise_kernel (inactive model, sigma) or, with the model active, noise_ar1_kernel /
-// noise_ar1_lds_kernel (grids too small to fill the chip), or noise_knot_kernel (a knot law); kernels_noise.hip.  d_law (or nullptr): the device law of
+// noise_ar1_lds_kernel (grids too small to fill the chip), noise_knot_kernel (a knot law) or noise_cov_kernel (a
+// cross-actuator covariance); kernels_noise.hip.  d_law (or nullptr): the device law of
 // a handle that adapts it on the stream (mppi_set_noise_adapt) -- the same generators reading sigma_u, rho and c from
 // device memory instead of the by-value model (noise_ar1_dev_kernel / noise_ar1_lds_dev_kernel)
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
@@ -404,6 +408,7 @@ struct CtrlArgs {
   float* part;          // [term_part_floats (term_cells.h)] scratch: the split form's per-cell partial sums
   CtrlLaw law;
   const float* d_law;   // the device law [kLawFloats] of an adapting handle, or nullptr: `law`
+  const float* sinv;    // Sigma^-1 [nu][nu] of a cross-actuator covariance (mppi_set_noise_cov), or nullptr: per actuator
 };
 hipError_t launch_ctrl_cost(const CtrlArgs& a, hipStream_t stream);  // lin, then the term and wcost (one of two forms)
 // kernels_bounds.hip: per-actuator control bounds (mppi_set_control_bounds; the rule: ctrl_bounds.h), by value like

@@ -290,6 +290,44 @@ function noise_knots(c::Controller)
 end
 
 """
+    set_noise_cov!(c, Sigma)
+
+Cross-actuator sampling covariance (mppi_set_noise_cov): the device noise of one step is drawn with the full covariance
+`Sigma` (nu x nu, Float32: symmetric bit for bit, positive definite), `eps[:, t, k] = L e[:, t, k]` with
+`Sigma = L L'` and `e` the handle's unit-variance AR(1) rows.  `nothing` disables and keeps sigma_u = sqrt(diag Sigma)
+and rho.  Not together with `set_noise_knots!` or `set_noise_adapt!`.
+"""
+function set_noise_cov!(c::Controller, Sigma::Union{Nothing, AbstractMatrix})
+    if Sigma === nothing
+        check(ccall((:mppi_set_noise_cov, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), c.handle, C_NULL))
+        return c
+    end
+    size(Sigma) == (c.cfg.nu, c.cfg.nu) || throw(ArgumentError("Sigma must be nu x nu"))
+    S = Matrix{Float32}(permutedims(Sigma))   # the C ABI's [nu][nu] is row-major
+    GC.@preserve S check(ccall((:mppi_set_noise_cov, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}), c.handle, pointer(S)))
+    return c
+end
+
+"""
+    noise_cov(c) -> (Sigma, L, Sinv) or nothing
+
+The handle's covariance as given, its lower Cholesky factor and its inverse (mppi_get_noise_cov), nu x nu Float32
+matrices indexed [u, v] as in C; `nothing` while the law is off.
+"""
+function noise_cov(c::Controller)
+    nu = c.cfg.nu
+    S = zeros(Float32, nu, nu)
+    L = zeros(Float32, nu, nu)
+    Si = zeros(Float32, nu, nu)
+    active = Ref{Cint}(0)
+    GC.@preserve S L Si check(ccall((:mppi_get_noise_cov, LIB), Cint,
+                                    (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ref{Cint}), c.handle,
+                                    pointer(S), pointer(L), pointer(Si), active))
+    active[] == 0 && return nothing
+    return (permutedims(S), permutedims(L), permutedims(Si))   # row-major C -> [u, v]
+end
+
+"""
     noise_eval(c, seed) -> Array{Float32, 3}
 
 The noise (nu, H, K), column-major as everywhere in this module, that the handle's generator draws for the key `seed`

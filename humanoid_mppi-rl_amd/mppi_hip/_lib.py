@@ -28,7 +28,7 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_kernel_clock_read", "mppi_build_id", "mppi_x3_layer1", "mppi_rollout_kernel", "mppi_x3_f16",
             "mppi_set_noise_model", "mppi_get_noise_model", "mppi_get_stats", "mppi_device_stats", "mppi_stats_eval",
             "mppi_set_noise_adapt", "mppi_get_noise_adapt", "mppi_get_noise_law", "mppi_set_noise_knots",
-            "mppi_get_noise_knots", "mppi_noise_eval", "mppi_set_ess_target",
+            "mppi_get_noise_knots", "mppi_noise_eval", "mppi_set_noise_cov", "mppi_get_noise_cov", "mppi_set_ess_target",
             "mppi_get_ess_target", "mppi_get_lambda", "mppi_lambda_eval", "mppi_set_control_cost",
             "mppi_get_control_cost", "mppi_get_control_term", "mppi_control_term_eval", "mppi_set_control_bounds",
             "mppi_get_control_bounds", "mppi_get_bound_counts", "mppi_bounds_eval", "mppi_set_rate_cost",
@@ -122,6 +122,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_get_noise_adapt": (i32, [vp] + [ctypes.POINTER(ctypes.c_float)] * 4),
         "mppi_set_noise_knots": (i32, [vp, i32, i32]),
         "mppi_get_noise_knots": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp]),
+        "mppi_set_noise_cov": (i32, [vp, vp]),
+        "mppi_get_noise_cov": (i32, [vp, vp, vp, vp, ctypes.POINTER(i32)]),
         "mppi_noise_eval": (i32, [vp, i32, ctypes.c_uint64, vp]),
         "mppi_get_noise_law": (i32, [vp, i32, _fp, ctypes.POINTER(ctypes.c_float)]),
         "mppi_set_ess_target": (i32, [vp] + [ctypes.c_float] * 3),

@@ -166,6 +166,32 @@ class Engine:
             return 0, 0, None, None
         return int(n.value), int(order.value), idx, w
 
+    def set_noise_cov(self, Sigma):
+        """Cross-actuator sampling covariance (mppi_set_noise_cov; noise.cov_factor / noise.cov_filter state the law):
+        the device noise of one step is drawn with the full covariance Sigma [nu, nu] (float32: symmetric bit for bit,
+        positive definite), eps[:, t, k] = L e[:, t, k] with Sigma = L L^T and e the handle's unit-variance AR(1) rows.
+        None disables and keeps sigma_u = sqrt(diag Sigma) and rho.  Makes the noise model active; destroys captured
+        graphs, as set_noise_model does.  Not together with set_noise_knots or set_noise_adapt."""
+        if Sigma is None:
+            L.check(self.lib.mppi_set_noise_cov(self._h, None))
+            return self
+        S = _f32(Sigma)
+        nu = self.config.nu
+        if S.shape != (nu, nu):
+            raise ValueError(f"set_noise_cov: Sigma must be [{nu}, {nu}], got {list(S.shape)}")
+        L.check(self.lib.mppi_set_noise_cov(self._h, _ptr(S)))
+        return self
+
+    def noise_cov(self) -> tuple[np.ndarray, np.ndarray, np.ndarray] | None:
+        """(Sigma, L, Sinv), each [nu, nu] float32, of the handle's covariance (mppi_get_noise_cov): Sigma as given,
+        its Cholesky factor (bitwise noise.cov_factor(Sigma)) and the inverse the control-cost term uses; None while
+        off."""
+        nu = self.config.nu
+        S, Lf, Si = (np.zeros((nu, nu), np.float32) for _ in range(3))
+        active = ctypes.c_int()
+        L.check(self.lib.mppi_get_noise_cov(self._h, _ptr(S), _ptr(Lf), _ptr(Si), ctypes.byref(active)))
+        return (S, Lf, Si) if active.value else None
+
     def noise_eval(self, B: int, seed: int) -> np.ndarray:
         """The noise [B, nu, H, K] (float32) the handle's generator draws for the by-value key `seed` under the law in
         effect (mppi_noise_eval): a solve's noise for that key, ahead of bounds and kept elites.  Drops a prefetched

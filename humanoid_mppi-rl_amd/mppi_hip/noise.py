@@ -7,6 +7,9 @@ this restatement is float64 (the reference for tests, and the filter of MPPIMode
 
 The knot law (mppi_set_noise_knots; csrc/noise_knots.h) draws the row at P knots and interpolates it to the H steps:
 knot_table and knot_filter restate it in float32, operation by operation, bitwise what the device draws.
+
+The cross-actuator covariance (mppi_set_noise_cov; csrc/noise_cov.h) mixes the unit-variance rows of the actuators with
+the Cholesky factor of a full Sigma: cov_factor, cov_mix and cov_filter restate it the same way, bitwise.
 """
 from __future__ import annotations
 
@@ -132,3 +135,68 @@ def knot_filter(z, P: int, order: int, rho: float = 0.0, sigma_u=None) -> np.nda
     for i in (1, 2, 3):
         e = _fma32(w[:, i][:, None], kn[..., idx[:, i], :], e)
     return (s[:, None, None] * e).astype(np.float32)
+
+
+# ---- the cross-actuator covariance (include/mppi.h mppi_set_noise_cov; csrc/noise_cov.h), restated bit for bit
+
+def cov_factor(Sigma) -> np.ndarray:
+    """The Cholesky factor L [nu, nu] (float32, lower, the strict upper triangle 0) of Sigma [nu, nu] (float32): the
+    restatement of csrc/noise_cov.h cov_factor in Python doubles, operation by operation (Cholesky-Banachiewicz, row by
+    row, one product and one difference at a time), rounded to float32 once: bitwise what mppi_get_noise_cov returns.
+    ValueError when Sigma is not finite, not symmetric bit for bit or a pivot is not > 0 and finite."""
+    S = np.asarray(Sigma, np.float32)
+    if S.ndim != 2 or S.shape[0] != S.shape[1] or S.shape[0] < 1:
+        raise ValueError("cov_factor: Sigma must be [nu, nu]")
+    nu = S.shape[0]
+    if not np.all(np.isfinite(S)) or not np.array_equal(S, S.T):
+        raise ValueError("cov_factor: Sigma must be finite and symmetric bit for bit")
+    Sd = [[float(S[u, v]) for v in range(nu)] for u in range(nu)]
+    Ld = [[0.0] * nu for _ in range(nu)]
+    for u in range(nu):
+        for v in range(u + 1):
+            a = Sd[u][v]
+            for j in range(v):
+                p = Ld[u][j] * Ld[v][j]
+                a = a - p
+            if u == v:
+                if not (a > 0.0 and np.isfinite(a)):
+                    raise ValueError(f"cov_factor: Sigma is not positive definite (pivot {u} is {a})")
+                Ld[u][u] = float(np.sqrt(a))
+            else:
+                Ld[u][v] = a / Ld[v][v]
+    return np.array(Ld, np.float64).astype(np.float32)
+
+
+def cov_mix(e, L) -> np.ndarray:
+    """eps[..., u, t, k] = sum_{v <= u} L[u][v] e[..., v, t, k] in float32 in the order of csrc/noise_cov.h (the first
+    product, then one fmaf per v, correctly rounded): bitwise what the device writes.  e [..., nu, H, K], L [nu, nu]
+    (only the lower triangle is read)."""
+    e = np.asarray(e, np.float32)
+    L = np.asarray(L, np.float32)
+    if e.ndim < 3 or L.shape != (e.shape[-3], e.shape[-3]):
+        raise ValueError("cov_mix: e must be [..., nu, H, K] and L [nu, nu]")
+    out = np.empty_like(e)
+    for u in range(L.shape[0]):
+        acc = L[u, 0] * e[..., 0, :, :]
+        for v in range(1, u + 1):
+            acc = _fma32(L[u, v], e[..., v, :, :], acc)
+        out[..., u, :, :] = acc
+    return out
+
+
+def cov_filter(z, Sigma_or_L, rho: float = 0.0, is_factor: bool | None = None) -> np.ndarray:
+    """The covariance law over given standard normals z [..., nu, H, K] (float32 result of the same shape):
+    cov_mix(ar1_filter_f32(z, rho), L).  Sigma_or_L: a lower-triangular matrix (its strict upper triangle exactly 0) is
+    taken as the factor L itself -- what Engine.noise_cov reports --, anything else as Sigma and factored by
+    cov_factor.  A diagonal matrix (nu = 1 included) is therefore read as L: say is_factor=False for a diagonal Sigma
+    (is_factor=True / False settles the reading whatever the matrix looks like)."""
+    M = np.asarray(Sigma_or_L, np.float32)
+    rho = float(rho)
+    if not 0.0 <= rho < 1.0:
+        raise ValueError("cov_filter: rho must be in [0, 1)")
+    if M.ndim != 2 or M.shape[0] != M.shape[1]:
+        raise ValueError("cov_filter: Sigma_or_L must be [nu, nu]")
+    if is_factor is None:
+        is_factor = not np.any(np.triu(M, 1))
+    L = M if is_factor else cov_factor(M)
+    return cov_mix(ar1_filter_f32(z, rho), L)

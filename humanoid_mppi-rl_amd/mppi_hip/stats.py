@@ -307,7 +307,7 @@ def ar1_precision(H: int, rho: float) -> np.ndarray:
     return P / (1.0 - rho * rho)
 
 
-def control_term_ref(U, noise, sigma_u, rho: float, gamma: float):
+def control_term_ref(U, noise, sigma_u, rho: float, gamma: float, Sinv=None):
     """The control-cost term in float64 (include/mppi.h mppi_set_control_cost): U [B, nu, H] (or [nu, H]), noise
     [B, nu, H, K] (or [nu, H, K]), sigma_u [nu] (or a scalar: every actuator's), rho in [0, 1), gamma >= 0 ->
     (term [B, K], lin [B, nu, H], majorant [B, nu, H]).
@@ -317,6 +317,12 @@ def control_term_ref(U, noise, sigma_u, rho: float, gamma: float):
                                             term non-finite (0 * inf = NaN), as on the device
         majorant = gamma / sigma_u^2 * |P| |U|: the absolute-value bound of lin that the fp32 rule's rounding error is
                    stated against (csrc/control_cost.h: |lin_f32 - lin| <= 8 * 2^-24 * majorant)
+
+    Sinv [nu, nu] (default None): the inverse of a cross-actuator covariance (mppi_set_noise_cov); sigma_u is then not
+    read and
+        lin[u]      = gamma * sum_v Sinv[u][v] (P U[v])
+        majorant[u] = gamma * sum_v |Sinv[u][v]| (|P| |U[v]|)      (csrc/control_cost.h: (nu + 8) * 2^-24 * majorant)
+    With Sinv = diag(1 / sigma_u^2) this is the per-actuator form above.
 
     ValueError on gamma negative or non-finite, rho outside [0, 1), negative or non-finite sigma_u, or shapes that do
     not agree."""
@@ -335,15 +341,22 @@ def control_term_ref(U, noise, sigma_u, rho: float, gamma: float):
         raise ValueError("control_term_ref: gamma must be finite and >= 0")
     if not 0.0 <= rho < 1.0:
         raise ValueError("control_term_ref: rho must be in [0, 1)")
-    s = np.asarray(sigma_u, np.float64)
-    s = np.full(nu, float(s)) if s.ndim == 0 else s.ravel()
-    if s.size != nu or not (np.all(np.isfinite(s)) and np.all(s >= 0.0)):
-        raise ValueError(f"control_term_ref: sigma_u must be {nu} finite entries >= 0")
     P = ar1_precision(H, rho)
-    scale = np.zeros(nu)
-    scale[s > 0.0] = gamma / s[s > 0.0] ** 2
-    lin = scale[None, :, None] * np.einsum("ts,bus->but", P, U)
-    majorant = scale[None, :, None] * np.einsum("ts,bus->but", np.abs(P), np.abs(U))
+    if Sinv is not None:
+        Si = np.asarray(Sinv, np.float64)
+        if Si.shape != (nu, nu) or not np.all(np.isfinite(Si)):
+            raise ValueError(f"control_term_ref: Sinv must be [{nu}, {nu}] and finite")
+        lin = gamma * np.einsum("uv,ts,bvs->but", Si, P, U)
+        majorant = gamma * np.einsum("uv,ts,bvs->but", np.abs(Si), np.abs(P), np.abs(U))
+    else:
+        s = np.asarray(sigma_u, np.float64)
+        s = np.full(nu, float(s)) if s.ndim == 0 else s.ravel()
+        if s.size != nu or not (np.all(np.isfinite(s)) and np.all(s >= 0.0)):
+            raise ValueError(f"control_term_ref: sigma_u must be {nu} finite entries >= 0")
+        scale = np.zeros(nu)
+        scale[s > 0.0] = gamma / s[s > 0.0] ** 2
+        lin = scale[None, :, None] * np.einsum("ts,bus->but", P, U)
+        majorant = scale[None, :, None] * np.einsum("ts,bus->but", np.abs(P), np.abs(U))
     with np.errstate(invalid="ignore"):  # (a non-finite noise entry makes its sample's term non-finite, as on the device)
         term = np.einsum("but,butk->bk", lin, e)
     if single:

@@ -102,6 +102,12 @@ extern "C" {
  *      and the noise the handle's generator draws for a key, on host arrays).  A handle that never enables it launches
  *      exactly the kernels it launched before, with the same grids.  BEHAVIOUR while a knot law is on only:
  *      mppi_set_noise_model(NULL, 0) returns MPPI_E_STATE, mppi_set_control_cost(gamma > 0) and
+ *      mppi_set_noise_adapt(rate > 0) return MPPI_E_UNSUPPORTED.
+ *      Additive, version unchanged: mppi_set_noise_cov / mppi_get_noise_cov (cross-actuator sampling covariance: the
+ *      device noise of one step drawn with a full nu x nu Sigma, mixed on the device; the control-cost term then uses
+ *      the true Sigma^-1).  A handle that never enables it launches exactly the kernels it launched before, with the
+ *      same grids.  BEHAVIOUR while a covariance is on only: mppi_set_noise_model(NULL, 0) and
+ *      mppi_set_noise_model(sigma_u != NULL, .) return MPPI_E_STATE, mppi_set_noise_knots(n_knots > 0) and
  *      mppi_set_noise_adapt(rate > 0) return MPPI_E_UNSUPPORTED. */
 #define MPPI_ABI_VERSION 4
 
@@ -382,6 +388,47 @@ int mppi_set_noise_knots(mppi_handle* h, int n_knots, int order);
 int mppi_get_noise_knots(mppi_handle* h, int* n_knots, int* order, int32_t* idx /* [H][4] or NULL */,
                          float* w /* [H][4] or NULL */);
 int mppi_noise_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out /* [B][nu][H][K] host */);
+
+/* Cross-actuator sampling covariance: the DEVICE noise of one (b, t, k) drawn with a full covariance Sigma [nu][nu]
+ * across the actuators (the Sigma of information-theoretic MPPI, pytorch_mppi's noise_sigma) instead of one independent
+ * sigma_u per actuator, generated on the device in every stream form in one pass over the noise buffer.  The rule is
+ * csrc/noise_cov.h, its numpy restatements mppi_hip.noise.cov_factor / cov_mix / cov_filter (bitwise).
+ *   Factor, once by the setter, in double (Cholesky-Banachiewicz, row by row):
+ *     for u in 0..nu-1, v in 0..u:  a = Sigma[u][v] - sum_{j < v} Ld[u][j] Ld[v][j]  (one product, one difference at a
+ *     time, j ascending);  u == v: Ld[u][u] = sqrt(a), a > 0 required;  else Ld[u][v] = a / Ld[v][v]
+ *     L = (float)Ld, rounded once after the whole factorisation, 0 above the diagonal;  Sinv = Sigma^-1 from Ld in double
+ *     (triangular solves), rounded to fp32 once;  sigma_u[u] = (float)sqrt((double)Sigma[u][u]).
+ *   Noise: e_v[t] is the handle's unit-variance AR(1) row of actuator v (mppi_set_noise_model's recursion over the
+ *   normals at Philox counter (k/4, t, v, b), under the key the solve draws anyway; rho = 0: the normals themselves), and
+ *     acc = L[u][0] e_0[t];  acc = fmaf(L[u][v], e_v[t], acc), v = 1..u;  eps[b][u][t][k] = acc        (fp32, this order)
+ *   so cov(eps[:, t], eps[:, s]) = Sigma rho^|t-s|.  sigma_u does not enter again.  Sigma = I gives the noise of
+ *   mppi_set_noise_model(ones, rho) value for value; the pad lanes K..Kp are written like every other lane.
+ * The dense noise [B][nu][H][Kp] is still written: everything behind the generator (control bounds, kept elites, the rate
+ * term, elites, the ESS target, statistics -- eps_m2[u] then estimates Sigma[u][u] --, the env step, trajectory logging,
+ * the seed counter) works unchanged, and plain, chained, captured-graph and trajectory-logging streams give bit for bit
+ * what a loop of plain counter solves gives.  The analytic cartpole leaves its fused generator as for any active model.
+ * mppi_set_noise_cov: Sigma [nu][nu] host, fp32: finite, symmetric bit for bit (Sigma[u][v] == Sigma[v][u]) and positive
+ * definite in the sense that every pivot a above is > 0 and finite; anything else is MPPI_E_ARG and changes nothing.
+ * Enabling makes the noise model active as mppi_set_noise_knots does (an inactive one becomes rho = 0) and needs nu <= 32
+ * (MPPI_E_UNSUPPORTED otherwise); sigma_u = sqrt(diag Sigma) becomes the model's per-actuator scale, which
+ * mppi_get_noise_model reports.  The first enabling call allocates the device memory of L and Sinv (nothing is allocated
+ * inside a solve).  NULL disables: sigma_u (the square roots of the diagonal) and rho stay as they stand, an active
+ * model without a covariance.  Any change drops a prefetched noise and destroys captured graphs exactly as
+ * mppi_set_noise_model does; the key sequence is unchanged.  Setting the value already in effect (bitwise) keeps both.
+ * While a covariance is on, mppi_set_noise_model(NULL, 0) returns MPPI_E_STATE (disable with mppi_set_noise_cov(h, NULL)
+ * first), mppi_set_noise_model(NULL, rho > 0) sets rho and keeps the covariance, and a non-NULL sigma_u returns
+ * MPPI_E_STATE (the scales are the covariance's).
+ * Not together with mppi_set_noise_knots (the mix would compose, but the knot generator does not mix) nor with
+ * mppi_set_noise_adapt (its rule adapts sigma_u, which no longer is the law): either order of either pair returns
+ * MPPI_E_UNSUPPORTED, changes nothing and names both setters in mppi_last_error.
+ * The control-cost term (mppi_set_control_cost) uses the true inverse under the law (csrc/control_cost.h):
+ *   lin[b][u][t] = gamma / (1 - rho^2) * sum_v Sinv[u][v] ((1 - rho^2) P U[b][v][:])[t]   (v ascending, fmaf chain)
+ * and a covariance enabled or changed while the term is on takes effect in the next solve; mppi_control_term_eval and
+ * mppi_noise_eval use the law in effect.
+ * mppi_get_noise_cov: *active (0 / 1) and, while on, Sigma as given, L and Sinv as computed, [nu][nu] each
+ * (written only while on); each pointer may be NULL. */
+int mppi_set_noise_cov(mppi_handle* h, const float* Sigma /* [nu][nu] host, or NULL: off */);
+int mppi_get_noise_cov(mppi_handle* h, float* Sigma, float* L, float* Sinv /* each [nu][nu] or NULL */, int* active);
 
 /* ESS targeting: the softmin temperature chosen ON THE DEVICE, per solve, so that the solve's own costs give a requested
  * effective sample size -- lambda made scale-free, with no host round trip: plain solves (host or device pointers),
