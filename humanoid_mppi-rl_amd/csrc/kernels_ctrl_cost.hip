@@ -19,7 +19,8 @@ __global__ __launch_bounds__(256) void ctrl_lin_kernel(CtrlArgs a) {
   if (i >= a.B * a.nu * a.H) return;
   const int bu = i / a.H, t = i - bu * a.H, u = bu % a.nu;
   if (a.sinv) {  // a cross-actuator covariance: the row of Sigma^-1 over every actuator's P U (never with d_law)
-    // (Sinv is written by the setter only, never during a launch)
+    // (Sinv is written by the setter and, on a handle that adapts its covariance, by noise_cov_adapt_kernel: a launch of
+    // its own behind this solve's statistics on the same stream, so never while this kernel runs)
     a.lin[i] = ctrl_lin_cov_entry(a.law.gamma, a.law.rho, a.sinv + u * a.nu, a.nu, a.U + (long)(bu - u) * a.H, t, a.H);
     return;
   }

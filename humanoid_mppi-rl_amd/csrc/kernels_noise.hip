@@ -11,6 +11,7 @@
 #include "mppi_internal.h"
 #include "noise_adapt.h"
 #include "noise_cov.h"
+#include "noise_cov_adapt.h"
 #include "noise_knots.h"
 #include "noise_model.h"
 #include "philox.h"
@@ -310,7 +311,9 @@ __global__ __launch_bounds__(2 * kCovWaves * kWave) void noise_cov_kernel(float*
     return;
   }
   const int wm = w - nd;
-  const cov_factor_rows L = (cov_factor_rows)m.cov_L;  // [nu][kMaxNu]; written by the setter only, never during a launch
+  // [nu][kMaxNu]; written by the setter and, on a handle that adapts its covariance, by noise_cov_adapt_kernel: a launch
+  // of its own ahead of this one on the same stream (the generator never runs beside it), so never during this launch
+  const cov_factor_rows L = (cov_factor_rows)m.cov_L;
   const int nq = Kp >> 2;
   const long row_q = (long)H * nq;  // quads per (b, u)
   knot_f4* dst = reinterpret_cast<knot_f4*>(noise) + (long)b * nu * row_q + kq;  // (u, t): dst + u * row_q + t * nq
@@ -453,6 +456,105 @@ __global__ __launch_bounds__(64) void noise_adapt_kernel(float* __restrict__ law
     law[kLawRho] = r;
     law[kLawC] = ar1_innovation_scale(r);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The adapted covariance (mppi_set_noise_cov_adapt; the rule: noise_cov_adapt.h).  One block behind a solve's cross
+// moments.  It records the Sigma the solve drew its noise from into hist [nu][nu], then all of its threads form the
+// batch means of the cross moments and the blended S1 (one pair (u, v <= u) per thread and trip: the reads of a pair's
+// B moments are na_sum's, sixteen ahead of the ordered additions), and ONE wave runs the rest with lane u owning row
+// u: the clamp, cov_factor's chains column by column (the pivot travels by a shuffle, every lane takes its root),
+// Ld^-1 one column per lane, Sigma^-1 one row per lane -- each element by the header's function, so the result is the
+// host's bit for bit.  Nothing is written until the step is known to stand; a rejected step counts one in *rejects.
+// The other waves leave behind the one block barrier; the wave's own exchanges through LDS are ordered by wave_lds_sync.
+// Ordinary stores: L, Sinv and Sigma are visible to the next launch on the stream.
+// ------------------------------------------------------------------------------------------------
+constexpr int kCovAdaptThreads = 256;
+
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(kCovAdaptThreads) void noise_cov_adapt_kernel(CovLaw law, float* __restrict__ hist,
+                                                                           const mppi_solve_stats* __restrict__ st,
+                                                                           const float* __restrict__ mx, int B, int nu,
+                                                                           NoiseCovAdapt a) {
+  __shared__ float s_s[kMaxNu][kMaxNu + 1];   // S1, then S2 in place (the lower triangle)
+  __shared__ float s_si[kMaxNu][kMaxNu + 1];  // Sigma^-1 in fp32 (the lower triangle)
+  __shared__ float s_g[kMaxNu];
+  __shared__ double s_L[kMaxNu * kMaxNu], s_W[kMaxNu * kMaxNu];  // Ld, Wd = Ld^-1 (row pitch kMaxNu)
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int nn = nu * nu;
+  for (int i = tid; i < nn; i += kCovAdaptThreads) hist[i] = law.S[i];
+  int dead = 0;  // a solve without a finite cost: the law stays (every wave looks at every solve: uniform over the block)
+  for (int b = lane; b < B; b += kWave) dead |= st[b].n_finite == 0;
+  if (__any(dead)) return;
+  for (int p = tid; p < nu * (nu + 1) / 2; p += kCovAdaptThreads) {
+    int u = 0;
+    while ((u + 1) * (u + 2) / 2 <= p) ++u;
+    const int v = p - u * (u + 1) / 2;
+    s_s[u][v] = nca_blend(a, law.S[u * nu + v], nca_mean(mx, B, nn, u * nu + v));
+  }
+  __syncthreads();
+  if (tid >= kWave) return;
+  auto reject = [&]() {
+    if (lane == 0) *law.rejects = *law.rejects + 1ull;
+  };
+  const bool on = lane < nu;
+  float s = 1.0f, c = 1.0f, g = 1.0f;
+  bool ok = true;
+  if (on) {
+    s = sqrtf(s_s[lane][lane]);
+    ok = nca_scale_ok(s);
+    c = nca_clamp(a, s);
+    g = nca_gain(c, s);
+    s_g[lane] = g;
+  }
+  if (__any(!ok)) return reject();
+  wave_lds_sync();
+  if (on) {
+    for (int v = 0; v < lane; ++v) s_s[lane][v] = nca_offdiag(s_s[lane][v], g, s_g[v]);
+    s_s[lane][lane] = nca_diag(s_s[lane][lane], s, c);
+  }
+  for (int v = 0; v < nu; ++v) {
+    double x = 0.0;
+    if (on && lane >= v) x = nca_chol_chain(s_L + lane * kMaxNu, s_L + v * kMaxNu, v, s_s[lane][v]);
+    const double piv = __shfl(x, v);
+    if (!nca_pivot_ok(piv)) return reject();  // (uniform over the wave)
+    const double d = sqrt(piv);
+    if (on && lane >= v) s_L[lane * kMaxNu + v] = lane == v ? d : x / d;
+    wave_lds_sync();
+  }
+  if (on)
+    for (int r = lane; r < nu; ++r) s_W[r * kMaxNu + lane] = nca_winv_elem(s_L, s_W, kMaxNu, r, lane);
+  wave_lds_sync();
+  bool bad = false;
+  if (on)
+    for (int v = 0; v <= lane; ++v) {
+      const double x = nca_sinv_elem(s_W, kMaxNu, nu, lane, v);
+      bad |= !nca_sinv_ok(x);
+      s_si[lane][v] = (float)x;
+    }
+  if (__any(bad)) return reject();
+  wave_lds_sync();
+  if (on) {
+    for (int v = 0; v < nu; ++v) {
+      const bool lo = v <= lane;
+      law.S[lane * nu + v] = lo ? s_s[lane][v] : s_s[v][lane];
+      law.L[lane * kMaxNu + v] = lo ? (float)s_L[lane * kMaxNu + v] : 0.0f;
+      law.Sinv[lane * nu + v] = lo ? s_si[lane][v] : s_si[v][lane];
+    }
+    law.sigma_u[lane] = nca_sigma(s_s[lane][lane]);
+  }
+}
+
+hipError_t launch_noise_cov_adapt(const CovLaw& law, float* hist, const mppi_solve_stats* stats, const float* mx,
+                                  int B, int nu, const NoiseCovAdapt& a, hipStream_t stream) {
+  if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_cov refuses such a handle)
+  hipLaunchKernelGGL(noise_cov_adapt_kernel, dim3(1), dim3(kCovAdaptThreads), 0, stream, law, hist, stats, mx, B, nu, a);
+  return hipGetLastError();
 }
 
 hipError_t launch_noise_law_set(float* d_law, const NoiseModel& model, hipStream_t stream) {

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "cross_moments.h"
 #include "mppi_internal.h"
 #include "wave_reduce.h"
 
@@ -281,12 +282,9 @@ __global__ __launch_bounds__(256) void stats_finish_kernel(StatsArgs a, int nbu,
 }
 
 // the cells of one (b, u) row: wave-chunks x segments (fixed by H and Kp, so by the handle)
-static void stats_cells(int H, int Kp, int* nwc, int* L, int* nseg) {
-  *nwc = (Kp / 4 + kWave - 1) / kWave;
-  const int smax = H < kStatsSegs ? H : kStatsSegs;
-  *L = (H + smax - 1) / smax;
-  *nseg = (H + *L - 1) / *L;
-}
+// (moment_cells of cross_moments.h: the one statement of the split, shared with the cross moments)
+static_assert(kStatsSegs == kMomentSegs && kWave == kMomentLanes, "stats_moment_kernel's cells are moment_cells'");
+static void stats_cells(int H, int Kp, int* nwc, int* L, int* nseg) { moment_cells(H, Kp, nwc, L, nseg); }
 
 size_t stats_part_floats(int B, int nu, int H, int Kp) {
   int nwc, L, nseg;

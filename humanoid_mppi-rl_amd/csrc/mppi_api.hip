@@ -22,6 +22,7 @@
 #include "term_cells.h"  // term_part_floats
 #include "noise_adapt.h"  // NoiseAdapt
 #include "noise_cov.h"    // cov_factor
+#include "noise_cov_adapt.h"  // NoiseCovAdapt
 #include "noise_knots.h"  // knot_table
 #include "noise_model.h"  // ar1_innovation_scale
 
@@ -61,10 +62,12 @@ enum KernelId {
   kRate = 8,
   kElites = 9,
   kKeep = 10,
-  kNumKernels = 11
+  kCross = 11,
+  kCovAdapt = 12,
+  kNumKernels = 13
 };
 const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost",
-                                         "bounds", "rate_cost", "elites", "keep"};
+                                         "bounds", "rate_cost", "elites", "keep", "cross", "cov_adapt"};
 
 struct PendingEvt {
   int id;
@@ -76,6 +79,8 @@ struct PendingEvt {
 // launches by it, note_ran records by it, and a captured graph keeps the one it was captured under.
 struct SolveOpts {
   bool stats = false;   // MPPI_FLAG_STATS
+  bool cross = false;   // MPPI_FLAG_CROSS
+  bool cov_adapt = false;  // mppi_set_noise_cov_adapt
   bool adapt = false;   // mppi_set_noise_adapt
   bool ess = false;     // mppi_set_ess_target
   bool ctrl = false;    // mppi_set_control_cost
@@ -153,6 +158,13 @@ struct mppi_handle {
   float *d_stats_w = nullptr, *d_stats_part = nullptr;  // scratch: normalised weights [max_batch][Kp], cell partials
   int stats_slots = 0;
   int stats_B = 0, stats_n = 0;  // batch and slot count of the last flagged solve / graph launch (0: none ran)
+  // the weighted cross moments (MPPI_FLAG_CROSS; cross_moments.h, kernels_cross.hip), allocated by ensure_cross before
+  // the first flagged solve or capture, slot-major like the statistics: cross_slots slots for solves and one more, the
+  // last, for mppi_cross_moments_eval
+  float* d_cross_mx = nullptr;    // [cross_slots + 1][max_batch][nu][nu]
+  float* d_cross_part = nullptr;  // scratch: the per-cell partial sums [cross_part_floats]
+  int cross_slots = 0;
+  int cross_B = 0, cross_n = 0;   // batch and slot count of the last solve / graph launch with the flag (0: none ran)
   // the law adapted on the device (mppi_set_noise_adapt; noise_adapt.h, kernels_noise.hip).  While adapt_on, d_law is
   // the law: the generators read it, noise_adapt_kernel moves it behind every solve's statistics, and noise_model
   // only keeps active = 1.  d_law_hist [hist_slots + 1][nu + 1]: the law solve i of the last solve / graph launch drew
@@ -171,9 +183,21 @@ struct mppi_handle {
   std::vector<float> knot_w;
   // the cross-actuator covariance (mppi_set_noise_cov; noise_cov.h, noise_cov_kernel).  noise_model.cov_L != nullptr
   // is the law; d_cov holds L [nu][kMaxNu] (rows padded) then Sinv [nu][nu], allocated by the first enabling call and written by the
-  // setter only; cov_host is the host's copy, Sigma, L, Sinv [nu][nu] each (mppi_get_noise_cov)
+  // setter and, while cov_adapt_on, by noise_cov_adapt_kernel; cov_host is the host's copy, Sigma, L, Sinv [nu][nu] each
+  // (mppi_get_noise_cov; refreshed from the device while cov_adapt_on)
   float* d_cov = nullptr;
   std::vector<float> cov_host;
+  // the covariance adapted on the device (mppi_set_noise_cov_adapt; noise_cov_adapt.h, noise_cov_adapt_kernel).  While
+  // cov_adapt_on every solve carries MPPI_FLAG_CROSS and runs the kernel behind its cross moments: it moves d_cov (L,
+  // Sinv) and d_cov_law -- the count of rejected steps (8 bytes), Sigma [nu][nu], sqrt of its diagonal [kMaxNu] --
+  // allocated by the first enabling call.  d_cov_hist [cov_hist_slots + 1][nu][nu]: the Sigma solve i of the last solve /
+  // graph launch drew its noise from, one row per statistics slot (ensure_cov_hist).
+  bool cov_adapt_on = false;
+  NoiseCovAdapt cov_adapt{0.0f, 1e-3f, 10.0f};
+  float* d_cov_law = nullptr;
+  float* d_cov_hist = nullptr;
+  int cov_hist_slots = 0;
+  int cov_law_n = 0;         // history rows of the last adapting solve / graph launch (0: none ran)
   // ESS targeting (mppi_set_ess_target; ess_target.h, kernels_lambda.hip).  While ess_on, every solve runs
   // lambda_search_kernel between its rollout and its reduce; the reduce and the statistics read the solve's lambda from
   // d_lambda [lambda_slots + 1][max_batch], slot-major like the statistics (a graph's solve i writes slot i; the last
@@ -449,7 +473,7 @@ void mppi_destroy(mppi_handle* h) {
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
-                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_law, h->d_law_hist, h->d_knots, h->d_cov,
+                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_cross_mx, h->d_cross_part, h->d_cov_law, h->d_cov_hist, h->d_law, h->d_law_hist, h->d_knots, h->d_cov,
                   h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U, h->d_bcounts,
                   h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev,
                   h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
@@ -835,6 +859,61 @@ static int ensure_stats(mppi_handle* h, int slots) {
   return MPPI_OK;
 }
 
+// The cross moments' buffers for `slots` solve slots (+ 1 for mppi_cross_moments_eval), beside the statistics' (whose
+// weights the cross pass reads: the caller runs ensure_stats first).  Growing them waits for the stream and forgets the
+// moments held so far.  Never called inside a capture.
+static int ensure_cross(mppi_handle* h, int slots) {
+  const mppi_config& c = h->cfg;
+  if (c.nu > kMaxNu) return fail(MPPI_E_UNSUPPORTED, "cross moments (MPPI_FLAG_CROSS) need nu <= 32");
+  if (!h->d_cross_part) {
+    const size_t np = cross_part_floats(c.max_batch, c.nu, c.H, h->Kp) * 4;
+    HIP_TRY(hipMalloc(&h->d_cross_part, np));
+    HIP_TRY(hipMemset(h->d_cross_part, 0, np));
+  }
+  if (slots <= h->cross_slots) return MPPI_OK;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->d_cross_mx) (void)hipFree(h->d_cross_mx);
+  h->d_cross_mx = nullptr;
+  h->cross_slots = 0;
+  h->cross_B = h->cross_n = 0;
+  const size_t n = (size_t)(slots + 1) * c.max_batch * c.nu * c.nu * 4;
+  HIP_TRY(hipMalloc(&h->d_cross_mx, n));
+  HIP_TRY(hipMemsetAsync(h->d_cross_mx, 0, n, h->stream));  // in stream order, ahead of the kernels that write slots
+  h->cross_slots = slots;
+  return MPPI_OK;
+}
+
+// The adapted covariance's history for `slots` solve slots, grown like the cross moments' slots.  Never called inside
+// a capture.
+static int ensure_cov_hist(mppi_handle* h, int slots) {
+  if (slots <= h->cov_hist_slots) return MPPI_OK;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->d_cov_hist) (void)hipFree(h->d_cov_hist);
+  h->d_cov_hist = nullptr;
+  h->cov_hist_slots = 0;
+  h->cov_law_n = 0;
+  const size_t n = (size_t)(slots + 1) * h->cfg.nu * h->cfg.nu * 4;
+  HIP_TRY(hipMalloc(&h->d_cov_hist, n));
+  HIP_TRY(hipMemsetAsync(h->d_cov_hist, 0, n, h->stream));  // in stream order, ahead of the kernels that write rows
+  h->cov_hist_slots = slots;
+  return MPPI_OK;
+}
+
+// the device covariance of an adapting handle (d_cov_law: the rejects counter, Sigma, sigma_u; d_cov: L, Sinv)
+static CovLaw cov_law(const mppi_handle* h) {
+  const size_t nu = (size_t)h->cfg.nu;
+  float* S = h->d_cov_law + 2;
+  return CovLaw{S, h->d_cov, h->d_cov + nu * kMaxNu, S + nu * nu, reinterpret_cast<unsigned long long*>(h->d_cov_law)};
+}
+
+// Behind the cross moments of slot `slot`: record the Sigma the solve drew from, move the device covariance one step.
+static hipError_t enqueue_cov_adapt(mppi_handle* h, int B, int slot) {
+  const mppi_config& c = h->cfg;
+  const size_t nn = (size_t)c.nu * c.nu, off = (size_t)slot * c.max_batch;
+  return launch_noise_cov_adapt(cov_law(h), h->d_cov_hist + (size_t)slot * nn, h->d_stats + off,
+                                h->d_cross_mx + off * nn, B, c.nu, h->cov_adapt, h->stream);
+}
+
 // The per-solve lambdas of ESS targeting for `slots` solve slots (+ 1 for mppi_lambda_eval).  Growing them waits for the
 // stream and forgets the values held so far.  Never called inside a capture.
 static int ensure_lambda(mppi_handle* h, int slots) {
@@ -876,6 +955,15 @@ static hipError_t enqueue_stats(mppi_handle* h, int B, const float* costs, const
   const StatsArgs sa{B, c.nu, c.H, c.K, h->Kp, c.lambda, c.norm_eps, costs, noise, h->d_stats_w, h->d_stats_part,
                      h->d_stats + off, h->d_stats_m2 + off * c.nu, h->d_stats_m11 + off * c.nu, lambda_dev};
   return launch_stats(sa, h->stream);
+}
+
+// The cross moments of B solves from noise [B][nu][H][Kp] into output slot `slot`, behind enqueue_stats of the same
+// solves (d_stats_w holds their weights).
+static hipError_t enqueue_cross(mppi_handle* h, int B, const float* noise, int slot) {
+  const mppi_config& c = h->cfg;
+  const CrossArgs ca{B, c.nu, c.H, h->Kp, h->d_stats_w, noise, h->d_cross_part,
+                     h->d_cross_mx + (size_t)slot * c.max_batch * c.nu * c.nu};
+  return launch_cross(ca, h->stream);
 }
 
 // The control-cost launches of B solves into output slot `slot` (0: a solve, 1: mppi_control_term_eval): lin from U
@@ -1067,6 +1155,8 @@ struct NoiseStep {
 static SolveOpts solve_opts(const mppi_handle* h, int flags) {
   SolveOpts o;
   o.stats = (flags & MPPI_FLAG_STATS) != 0;
+  o.cross = (flags & MPPI_FLAG_CROSS) != 0;
+  o.cov_adapt = h->cov_adapt_on;
   o.adapt = h->adapt_on;
   o.ess = h->ess_on;
   o.ctrl = h->ctrl_gamma > 0.0f;
@@ -1085,7 +1175,12 @@ static void note_ran(mppi_handle* h, const SolveOpts& o, int B, int n) {
     h->stats_B = B;
     h->stats_n = n;
   }
+  if (o.cross) {
+    h->cross_B = B;
+    h->cross_n = n;
+  }
   if (o.adapt) h->law_n = n;
+  if (o.cov_adapt) h->cov_law_n = n;
   if (o.ess) {
     h->lam_B = B;
     h->lam_n = n;
@@ -1124,7 +1219,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   a.shift_fill = c.shift_fill;
   a.terminal_weight = c.terminal_weight;
   a.update_mode = c.update_mode;
-  a.flags = flags & ~MPPI_FLAG_STATS;  // (host-side only: the kernels see the arguments of a solve without it)
+  a.flags = flags & ~(MPPI_FLAG_STATS | MPPI_FLAG_CROSS);  // (host-side only: the kernels see the arguments of a solve without it)
   a.cost_kind = h->cost_kind;
   std::memcpy(a.ctx_default, h->cost_params, sizeof(a.ctx_default));
   a.noise = ns ? ns->cur : h->d_noise;
@@ -1285,10 +1380,17 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // behind it (ev_red), only ever write the OTHER buffer of the pair before this point
   if (o.stats)
     HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, wcost, a.noise, stats_slot, lam); }));
+  // the cross moments (MPPI_FLAG_CROSS; every such solve carries MPPI_FLAG_STATS): behind the statistics, whose weights
+  // they read, and like them ahead of everything that may write a.noise
+  if (o.cross) HIP_TRY(timed(h, kCross, [&] { return enqueue_cross(h, B, a.noise, stats_slot); }));
   // the adapted law (mppi_set_noise_adapt; every such solve carries the flag): one wave directly behind the statistics
   // and ahead of the launch below that draws the next solve's noise, so chained and captured streams draw solve i + 1
   // from the law adapted on solve i, as a loop of plain solves does
   if (o.adapt) HIP_TRY(timed(h, kStats, [&] { return enqueue_adapt(h, B, stats_slot); }));
+  // the adapted covariance (mppi_set_noise_cov_adapt; every such solve carries MPPI_FLAG_CROSS): one block directly
+  // behind the cross moments and, like the law's kernel above, ahead of the launch that draws the next solve's noise
+  // from L; this solve's control-cost term (far above) has read the Sinv its own noise was drawn under
+  if (o.cov_adapt) HIP_TRY(timed(h, kCovAdapt, [&] { return enqueue_cov_adapt(h, B, stats_slot); }));
   if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
     HIP_TRY(timed(h, kNoise, [&] {
       return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s,
@@ -1421,7 +1523,7 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   MPPI_TRY(ensure_stream_buffers(h));
   // (an adapting handle ignores the overlap arm, as a capture does: it would draw the next noise ahead of this
   // solve's update of the law)
-  const bool overlap = gen_overlap() && !h->capturing && !h->adapt_on;
+  const bool overlap = gen_overlap() && !h->capturing && !h->adapt_on && !h->cov_adapt_on;
   if (!overlap) HIP_TRY(wait_gen(h));  // leaving overlap mode: the solve stream behind the last generator launch
   MPPI_TRY(prime_prefetch(h, B, seed));
   float* buf[2] = {h->d_noise, h->d_noise2};
@@ -1625,7 +1727,11 @@ int mppi_solve_ex(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int f
   HIP_TRY(hipSetDevice(h->device));
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;
   if (h->adapt_on) flags |= MPPI_FLAG_STATS;  // the adaptation reads the solve's moments
+  if (h->cov_adapt_on) flags |= MPPI_FLAG_CROSS;  // the covariance's adaptation reads the solve's cross moments
+  if (flags & MPPI_FLAG_CROSS) flags |= MPPI_FLAG_STATS;  // the cross pass reads the statistics' weights
   if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, 1)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_CROSS) && (rc = ensure_cross(h, 1)) != MPPI_OK) return rc;
+  if (h->cov_adapt_on && (rc = ensure_cov_hist(h, 1)) != MPPI_OK) return rc;
   if (h->ess_on && (rc = ensure_lambda(h, 1)) != MPPI_OK) return rc;
   if (flags & MPPI_FLAG_CHAIN) return chain_solve(h, B, io, seed, flags);
   HIP_TRY(drop_prefetch(h));  // a plain solve generates its own noise into d_noise
@@ -1652,6 +1758,8 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   int rc = check_solve(h, B, io, flags);
   if (rc != MPPI_OK) return rc;
   if (h->adapt_on) flags |= MPPI_FLAG_STATS;  // the adaptation reads solve i's moments out of slot i
+  if (h->cov_adapt_on) flags |= MPPI_FLAG_CROSS;  // ... and the covariance's its cross moments
+  if (flags & MPPI_FLAG_CROSS) flags |= MPPI_FLAG_STATS;  // the cross pass reads the statistics' weights
   HIP_TRY(hipSetDevice(h->device));
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;  // before the capture: it synchronises the stream
   MPPI_TRY(drop_graphs(h, false));
@@ -1661,6 +1769,8 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   if (const int e = ensure_stream_buffers(h); e != MPPI_OK) return e;
   // the statistics' slots exist before the capture begins: solve i's launches carry slot i's pointers
   if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, n_solves)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_CROSS) && (rc = ensure_cross(h, n_solves)) != MPPI_OK) return rc;
+  if (h->cov_adapt_on && (rc = ensure_cov_hist(h, n_solves)) != MPPI_OK) return rc;
   if (h->ess_on && (rc = ensure_lambda(h, n_solves)) != MPPI_OK) return rc;  // ... and the lambdas' slots
   float* buf[2] = {h->d_noise, h->d_noise2};
   const bool prof = h->prof;
@@ -1785,6 +1895,8 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
   return MPPI_OK;
 }
 
+static int fetch_cov_law(mppi_handle* h);  // (below, beside mppi_set_noise_cov_adapt)
+
 // the device law -> h->noise_model (waits for the stream); c is the host's, as for every by-value model
 static int fetch_law(mppi_handle* h) {
   float law[kLawFloats];
@@ -1875,6 +1987,10 @@ int mppi_get_noise_model(mppi_handle* h, float* sigma_u, float* rho, int* active
     HIP_TRY(hipSetDevice(h->device));
     MPPI_TRY(fetch_law(h));
   }
+  if (h->cov_adapt_on) {  // ... an adapted covariance's scales: sqrt of its live diagonal
+    HIP_TRY(hipSetDevice(h->device));
+    MPPI_TRY(fetch_cov_law(h));
+  }
   const NoiseModel& m = h->noise_model;
   if (sigma_u)
     for (int u = 0; u < h->cfg.nu; ++u) sigma_u[u] = m.active ? m.sigma_u[u] : h->cfg.sigma;
@@ -1949,12 +2065,106 @@ int mppi_get_noise_knots(mppi_handle* h, int* n_knots, int* order, int32_t* idx,
   return MPPI_OK;
 }
 
+// the host's covariance (cov_host's Sigma, noise_model.sigma_u) -> d_cov_law; the stream is idle.  reset: the count of
+// rejected steps starts again
+static int upload_cov_law(mppi_handle* h, bool reset) {
+  const size_t nn = (size_t)h->cfg.nu * h->cfg.nu;
+  const CovLaw law = cov_law(h);
+  if (reset) HIP_TRY(hipMemset(law.rejects, 0, sizeof(unsigned long long)));
+  HIP_TRY(hipMemcpy(law.S, h->cov_host.data(), nn * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(law.sigma_u, h->noise_model.sigma_u, kMaxNu * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipDeviceSynchronize());  // (the null stream's copies are not ordered against the handle's stream)
+  return MPPI_OK;
+}
+
+// the device covariance -> cov_host (Sigma, L, Sinv) and noise_model.sigma_u (waits for the stream)
+static int fetch_cov_law(mppi_handle* h) {
+  const int nu = h->cfg.nu;
+  const size_t nn = (size_t)nu * nu;
+  const CovLaw law = cov_law(h);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  float* host = h->cov_host.data();
+  HIP_TRY(hipMemcpy(host, law.S, nn * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy2D(host + nn, nu * sizeof(float), law.L, kMaxNu * sizeof(float), nu * sizeof(float), nu,
+                      hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(host + 2 * nn, law.Sinv, nn * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h->noise_model.sigma_u, law.sigma_u, (size_t)nu * sizeof(float), hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_set_noise_cov_adapt(mppi_handle* h, float rate, float sigma_min, float sigma_max) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_cov_adapt: null handle");
+  if (!(rate >= 0.0f && rate <= 1.0f)) return fail(MPPI_E_ARG, "mppi_set_noise_cov_adapt: rate must be in [0, 1]");
+  if (!(sigma_min > 0.0f && sigma_min <= sigma_max && std::isfinite(sigma_max)))
+    return fail(MPPI_E_ARG, "mppi_set_noise_cov_adapt: need 0 < sigma_min <= sigma_max < inf");
+  const bool on = rate > 0.0f;
+  if (on && h->cfg.nu > kMaxNu)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov_adapt: the adapted covariance needs nu <= 32");
+  if (on && !h->noise_model.cov_L)
+    return fail(MPPI_E_STATE, "mppi_set_noise_cov_adapt: no covariance to adapt: call mppi_set_noise_cov first");
+  if (!on && !h->cov_adapt_on) {  // nothing to disable: only the limits are kept
+    h->cov_adapt = NoiseCovAdapt{0.0f, sigma_min, sigma_max};
+    return MPPI_OK;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state, as in mppi_set_noise_adapt: the prefetched noise (the counter steps back: the key sequence is
+  // unchanged) and the captured graphs, which hold the settings in their kernel arguments
+  HIP_TRY(drop_prefetch(h));
+  MPPI_TRY(drop_graphs(h, true));
+  if (on && !h->cov_adapt_on) {
+    const size_t bytes = 8 + ((size_t)h->cfg.nu * h->cfg.nu + kMaxNu) * sizeof(float);
+    if (!h->d_cov_law) HIP_TRY(hipMalloc(&h->d_cov_law, bytes));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    MPPI_TRY(upload_cov_law(h, true));
+    h->cov_adapt_on = true;
+    h->cov_law_n = 0;
+  } else if (!on) {  // back to the setter's law with the covariance as it stands
+    MPPI_TRY(fetch_cov_law(h));
+    h->cov_adapt_on = false;
+  }
+  h->cov_adapt = NoiseCovAdapt{rate, sigma_min, sigma_max};
+  return MPPI_OK;
+}
+
+int mppi_get_noise_cov_adapt(mppi_handle* h, float* rate, float* sigma_min, float* sigma_max, uint64_t* rejects) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_cov_adapt: null handle");
+  if (rate) *rate = h->cov_adapt_on ? h->cov_adapt.rate : 0.0f;
+  if (sigma_min) *sigma_min = h->cov_adapt.sigma_min;
+  if (sigma_max) *sigma_max = h->cov_adapt.sigma_max;
+  if (rejects) {
+    unsigned long long r = 0;
+    if (h->d_cov_law) {  // (it stays readable after the adaptation was disabled)
+      HIP_TRY(hipSetDevice(h->device));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      HIP_TRY(hipMemcpy(&r, h->d_cov_law, sizeof(r), hipMemcpyDeviceToHost));
+    }
+    *rejects = r;
+  }
+  return MPPI_OK;
+}
+
+int mppi_get_noise_cov_law(mppi_handle* h, int step, float* Sigma) {
+  if (!h || !Sigma) return fail(MPPI_E_ARG, "mppi_get_noise_cov_law: null argument");
+  if (h->cov_law_n == 0)
+    return fail(MPPI_E_STATE, "mppi_get_noise_cov_law: no solve that adapts the covariance has run on the handle");
+  if (step < 0 || step >= h->cov_law_n)
+    return fail(MPPI_E_ARG, "mppi_get_noise_cov_law: step beyond the solves of the last adapting solve or graph");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  const size_t nn = (size_t)h->cfg.nu * h->cfg.nu;
+  HIP_TRY(hipMemcpy(Sigma, h->d_cov_hist + (size_t)step * nn, nn * sizeof(float), hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
 int mppi_set_noise_cov(mppi_handle* h, const float* Sigma) {
   if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_cov: null handle");
   const mppi_config& c = h->cfg;
   const size_t nn = (size_t)c.nu * c.nu;
   NoiseModel m = h->noise_model;
   if (!Sigma && !m.cov_L) return MPPI_OK;  // nothing to disable
+  if (!Sigma && h->cov_adapt_on)
+    return fail(MPPI_E_STATE, "mppi_set_noise_cov: the covariance is being adapted: disable it first "
+                              "(mppi_set_noise_cov_adapt with rate 0)");
   std::vector<float> host;
   if (Sigma) {
     if (c.nu > kMaxNu)
@@ -1966,8 +2176,8 @@ int mppi_set_noise_cov(mppi_handle* h, const float* Sigma) {
     if (!cov_factor(Sigma, c.nu, host.data() + nn, host.data() + 2 * nn, sig, scratch.data(), scratch.data() + nn))
       return fail(MPPI_E_ARG, "mppi_set_noise_cov: Sigma must be finite, symmetric bit for bit and positive definite "
                               "(every Cholesky pivot > 0)");
-    // the value in effect, bitwise: prefetch and graphs stay
-    if (m.cov_L && std::memcmp(host.data(), h->cov_host.data(), nn * sizeof(float)) == 0) return MPPI_OK;
+    // the value in effect, bitwise: prefetch and graphs stay (an adapting handle's law has moved: it is reset below)
+    if (m.cov_L && !h->cov_adapt_on && std::memcmp(host.data(), h->cov_host.data(), nn * sizeof(float)) == 0) return MPPI_OK;
     if (m.n_knots > 0)
       return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov: not together with mppi_set_noise_knots (the knot generator "
                                       "does not mix the actuators)");
@@ -1997,6 +2207,10 @@ int mppi_set_noise_cov(mppi_handle* h, const float* Sigma) {
     HIP_TRY(hipMemcpy(h->d_cov + (size_t)c.nu * kMaxNu, host.data() + 2 * nn, nn * sizeof(float), hipMemcpyHostToDevice));
     h->cov_host.swap(host);
     m.cov_L = h->d_cov;
+    if (h->cov_adapt_on) {  // the device law starts again from here (the count of rejected steps goes on)
+      h->noise_model = m;
+      MPPI_TRY(upload_cov_law(h, false));
+    }
   } else {  // sigma_u (= sqrt of the diagonal) and rho stay as they stand: the AR(1) generators again
     m.cov_L = nullptr;
   }
@@ -2008,6 +2222,10 @@ int mppi_get_noise_cov(mppi_handle* h, float* Sigma, float* L, float* Sinv, int*
   if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_cov: null handle");
   const bool on = h->noise_model.cov_L != nullptr;
   if (active) *active = on ? 1 : 0;
+  if (h->cov_adapt_on) {  // the live law: every enqueued solve's update included
+    HIP_TRY(hipSetDevice(h->device));
+    MPPI_TRY(fetch_cov_law(h));
+  }
   if (on) {  // (off: the arrays are left untouched)
     const size_t nn = (size_t)h->cfg.nu * h->cfg.nu;
     if (Sigma) std::memcpy(Sigma, h->cov_host.data(), nn * sizeof(float));
@@ -2659,6 +2877,44 @@ int mppi_stats_eval(mppi_handle* h, int B, const float* costs, const float* nois
   HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, h->d_costs, noise ? h->d_noise : nullptr, slot); }));
   HIP_TRY(hipStreamSynchronize(s));
   return copy_stats(h, B, slot, stats, noise ? eps_m2 : nullptr, noise ? eps_m11 : nullptr);
+}
+
+int mppi_get_cross_moments(mppi_handle* h, int B, int step, float* mx) {
+  if (!h || !mx) return fail(MPPI_E_ARG, "mppi_get_cross_moments: null argument");
+  if (h->cross_n == 0)
+    return fail(MPPI_E_STATE, "mppi_get_cross_moments: no solve with MPPI_FLAG_CROSS has run on the handle");
+  if (B < 1 || B > h->cross_B)
+    return fail(MPPI_E_ARG, "mppi_get_cross_moments: B beyond the batch of the last flagged solve");
+  if (step < 0 || step >= h->cross_n)
+    return fail(MPPI_E_ARG, "mppi_get_cross_moments: step beyond the solves of the last flagged solve or graph");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  const size_t nn = (size_t)h->cfg.nu * h->cfg.nu;
+  HIP_TRY(hipMemcpy(mx, h->d_cross_mx + (size_t)step * h->cfg.max_batch * nn, (size_t)B * nn * 4,
+                    hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_cross_moments_eval(mppi_handle* h, int B, const float* costs, const float* noise, float* mx) {
+  if (!h || !costs || !noise || !mx) return fail(MPPI_E_ARG, "mppi_cross_moments_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_cross_moments_eval: B out of range [1, max_batch]");
+  if (c.nu > kMaxNu) return fail(MPPI_E_UNSUPPORTED, "mppi_cross_moments_eval: needs nu <= 32");
+  HIP_TRY(hipSetDevice(h->device));
+  MPPI_TRY(ensure_stats(h, 1));
+  MPPI_TRY(ensure_cross(h, 1));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  MPPI_TRY(stage_costs(h, costs, B));
+  MPPI_TRY(stage_noise(h, noise, (size_t)B * c.nu * c.H));
+  // the evaluations' own slots: the statistics and cross moments of the last solve stay readable
+  HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, h->d_costs, h->d_noise, h->stats_slots); }));
+  HIP_TRY(timed(h, kCross, [&] { return enqueue_cross(h, B, h->d_noise, h->cross_slots); }));
+  HIP_TRY(hipStreamSynchronize(s));
+  const size_t nn = (size_t)c.nu * c.nu;
+  HIP_TRY(hipMemcpy(mx, h->d_cross_mx + (size_t)h->cross_slots * c.max_batch * nn, (size_t)B * nn * 4,
+                    hipMemcpyDeviceToHost));
+  return MPPI_OK;
 }
 
 int mppi_solve(mppi_handle* h, int B, const float* x0, float* U, const float* noise, uint64_t seed, float* costs_out,

@@ -10,6 +10,7 @@
 
 struct NoiseAdapt;  // noise_adapt.h: the settings of mppi_set_noise_adapt
 struct EssTarget;   // ess_target.h: the settings of mppi_set_ess_target
+struct NoiseCovAdapt;  // noise_cov_adapt.h: the settings of mppi_set_noise_cov_adapt
 
 namespace mppi {
 
@@ -302,6 +303,20 @@ constexpr int kLawRho = kMaxNu, kLawC = kMaxNu + 1, kLawFloats = kMaxNu + 2;
 hipError_t launch_noise_law_set(float* d_law, const NoiseModel& model, hipStream_t stream);
 hipError_t launch_noise_adapt(float* d_law, float* hist, const mppi_solve_stats* stats, const float* m2,
                               const float* m11, int B, int nu, const NoiseAdapt& a, hipStream_t stream);
+// The device covariance of a handle that adapts it (mppi_set_noise_cov_adapt): Sigma [nu][nu], the factors where the
+// generator and the control-cost term read them (L [nu][kMaxNu], Sinv [nu][nu]), sqrt of the diagonal [kMaxNu] and the
+// count of rejected steps.  noise_cov_adapt_kernel records Sigma into hist [nu][nu], then moves all of it one step by
+// the rule of noise_cov_adapt.h from one slot of statistics (stats [B]) and cross moments (mx [B][nu][nu]).  One block;
+// capturable.
+struct CovLaw {
+  float* S;
+  float* L;
+  float* Sinv;
+  float* sigma_u;
+  unsigned long long* rejects;
+};
+hipError_t launch_noise_cov_adapt(const CovLaw& law, float* hist, const mppi_solve_stats* stats, const float* mx,
+                                  int B, int nu, const NoiseCovAdapt& a, hipStream_t stream);
 // fc-stack rollout: fc_route (fc_route.h) decides the kernel from the shape, the image, the probe outcomes and the
 // knobs; launch_fc_route launches a given route (the engine's probe passes routes of its own)
 struct FcRoute;
@@ -359,6 +374,17 @@ struct StatsArgs {
 };
 size_t stats_part_floats(int B, int nu, int H, int Kp);
 hipError_t launch_stats(const StatsArgs& a, hipStream_t stream);  // cost part, moment part, fixed-order finish
+// Weighted cross moments (kernels_cross.hip; MPPI_FLAG_CROSS, mppi_cross_moments_eval; the definition: cross_moments.h),
+// by value like StatsArgs and behind its launches, whose weights they read; nu <= kMaxNu.
+struct CrossArgs {
+  int B, nu, H, Kp;
+  const float* w;      // [B][Kp] the normalised softmin weights stats_cost_kernel wrote (pads 0)
+  const float* noise;  // [B][nu][H][Kp]
+  float* part;         // [cross_part_floats] scratch: the per-cell partial sums, [B][pair][cell]
+  float* mx;           // [B][nu][nu] out
+};
+size_t cross_part_floats(int B, int nu, int H, int Kp);
+hipError_t launch_cross(const CrossArgs& a, hipStream_t stream);  // moment part, fixed-order finish
 // kernels_lambda.hip: per solve b, lambda_out[b] = the lambda in [lambda_min, lambda_max] at which costs [B][Kp] give
 // the target effective sample size (the rule: ess_target.h); one block per solve, read-only on the costs, capturable
 hipError_t launch_lambda_search(const float* costs, int B, int K, int Kp, const EssTarget& s, float cfg_lambda,

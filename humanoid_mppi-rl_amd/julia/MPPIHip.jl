@@ -33,6 +33,7 @@ const COST = Dict(:cartpole => Cint(1), :cartpole_est => Cint(2), :humanoid_v3 =
                   :quad_jl => Cint(4), :quad_est => Cint(5), :humanoid_v1 => Cint(6))
 const FLAG_SHIFT, FLAG_COLMAJOR, FLAG_U0_BEFORE = Cint(0x1), Cint(0x2), Cint(0x10)
 const FLAG_STATS = Cint(0x200)   # also compute the solve's diagnostics (solve_stats)
+const FLAG_CROSS = Cint(0x400)   # ... and the weighted cross moments of its noise (cross_moments); implies FLAG_STATS
 const CTX_MAX = 8
 
 # must match `mppi_io` in include/mppi.h (7 pointers)
@@ -325,6 +326,78 @@ function noise_cov(c::Controller)
                                     pointer(S), pointer(L), pointer(Si), active))
     active[] == 0 && return nothing
     return (permutedims(S), permutedims(L), permutedims(Si))   # row-major C -> [u, v]
+end
+
+"""
+    set_noise_cov_adapt!(c, rate; sigma_min = 1f-3, sigma_max = 10f0)
+
+Adapt the full sampling covariance on the device behind every solve (mppi_set_noise_cov_adapt): Sigma moves towards the
+weighted cross moments of the solve's noise, its standard deviations are clipped to [sigma_min, sigma_max] with the
+correlations kept, and L and Sigma^-1 are factored again on the device.  `rate` in (0, 1] enables (after
+`set_noise_cov!`), 0 disables and keeps the law as it stands.
+"""
+function set_noise_cov_adapt!(c::Controller, rate::Real; sigma_min::Real = 1f-3, sigma_max::Real = 10f0)
+    check(ccall((:mppi_set_noise_cov_adapt, LIB), Cint, (Ptr{Cvoid}, Cfloat, Cfloat, Cfloat), c.handle,
+                Float32(rate), Float32(sigma_min), Float32(sigma_max)))
+    return c
+end
+
+"""
+    noise_cov_adapt(c) -> (rate, sigma_min, sigma_max, rejects)
+
+The settings of mppi_get_noise_cov_adapt (rate 0 while off) and the number of steps the device rejected.
+"""
+function noise_cov_adapt(c::Controller)
+    r, lo, hi = Ref{Cfloat}(0), Ref{Cfloat}(0), Ref{Cfloat}(0)
+    n = Ref{UInt64}(0)
+    check(ccall((:mppi_get_noise_cov_adapt, LIB), Cint,
+                (Ptr{Cvoid}, Ref{Cfloat}, Ref{Cfloat}, Ref{Cfloat}, Ref{UInt64}), c.handle, r, lo, hi, n))
+    return (r[], lo[], hi[], Int(n[]))
+end
+
+"""
+    noise_cov_law(c, step = 0) -> Matrix{Float32}
+
+The Sigma (nu x nu, indexed [u, v]) the adapting solve `step` drew its noise from (mppi_get_noise_cov_law).
+"""
+function noise_cov_law(c::Controller, step::Integer = 0)
+    nu = c.cfg.nu
+    S = zeros(Float32, nu, nu)
+    GC.@preserve S check(ccall((:mppi_get_noise_cov_law, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle,
+                               Cint(step), pointer(S)))
+    return permutedims(S)
+end
+
+"""
+    cross_moments(c, step = 0) -> Matrix{Float32}
+
+The weighted cross moments eps_mx (nu x nu, symmetric) of the last solve made with `FLAG_CROSS`
+(mppi_get_cross_moments): 1/H sum_t sum_k w_k eps_u eps_v; its diagonal is eps_m2.
+"""
+function cross_moments(c::Controller, step::Integer = 0)
+    nu = c.cfg.nu
+    mx = zeros(Float32, nu, nu)
+    GC.@preserve mx check(ccall((:mppi_get_cross_moments, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float32}),
+                                c.handle, Cint(1), Cint(step), pointer(mx)))
+    return mx   # (symmetric: row-major C == column-major)
+end
+
+"""
+    cross_moments_eval(c, costs, noise) -> Matrix{Float32}
+
+The same kernels on host arrays (mppi_cross_moments_eval): `costs` (K), `noise` (nu, H, K) column-major as everywhere
+in this module.  Touches no solve state and never adapts.
+"""
+function cross_moments_eval(c::Controller, costs::AbstractVector, noise::AbstractArray{<:Real, 3})
+    nu, H, K = c.cfg.nu, c.cfg.H, c.cfg.K
+    (length(costs) == K && size(noise) == (nu, H, K)) || throw(ArgumentError("costs (K), noise (nu, H, K)"))
+    cs = Vector{Float32}(costs)
+    nz = Array{Float32}(permutedims(noise, (3, 2, 1)))   # C's [nu][H][K]: K fastest
+    mx = zeros(Float32, nu, nu)
+    GC.@preserve cs nz mx check(ccall((:mppi_cross_moments_eval, LIB), Cint,
+                                      (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}), c.handle, Cint(1),
+                                      pointer(cs), pointer(nz), pointer(mx)))
+    return mx
 end
 
 """

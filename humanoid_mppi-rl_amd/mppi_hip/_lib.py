@@ -18,6 +18,7 @@ UPDATE_ADD, UPDATE_REPLACE = 0, 1
 PREC_FP32, PREC_BF16, PREC_BF16X3 = 0, 1, 2  # BF16X3: fp32-accurate split bf16 (fc nets)
 FLAG_SHIFT, FLAG_COLMAJOR, FLAG_DEVICE, FLAG_ASYNC, FLAG_U0_BEFORE, FLAG_RESIDENT_U = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 FLAG_ENV_STEP, FLAG_SEED_COUNTER, FLAG_CHAIN, FLAG_STATS = 0x40, 0x80, 0x100, 0x200
+FLAG_CROSS = 0x400  # implies FLAG_STATS
 CTX_MAX = 8
 
 EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", "mppi_set_cost", "mppi_solve",
@@ -35,7 +36,8 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_get_rate_cost", "mppi_set_prev_control", "mppi_get_prev_control", "mppi_get_rate_term",
             "mppi_rate_term_eval", "mppi_set_elites", "mppi_get_elites", "mppi_get_elite_set", "mppi_elites_eval",
             "mppi_set_elite_keep", "mppi_get_elite_keep", "mppi_get_kept", "mppi_set_kept", "mppi_keep_store_eval",
-            "mppi_keep_inject_eval"]
+            "mppi_keep_inject_eval", "mppi_get_cross_moments", "mppi_cross_moments_eval",
+            "mppi_set_noise_cov_adapt", "mppi_get_noise_cov_adapt", "mppi_get_noise_cov_law"]
 
 
 class MPPIError(RuntimeError):
@@ -157,6 +159,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_get_stats": (i32, [vp, i32, i32, vp, vp, vp]),
         "mppi_device_stats": (i32, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)]),
         "mppi_stats_eval": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+        "mppi_get_cross_moments": (i32, [vp, i32, i32, vp]),
+        "mppi_cross_moments_eval": (i32, [vp, i32, vp, vp, vp]),
+        "mppi_set_noise_cov_adapt": (i32, [vp, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
+        "mppi_get_noise_cov_adapt": (i32, [vp, vp, vp, vp, vp]),
+        "mppi_get_noise_cov_law": (i32, [vp, i32, vp]),
         "mppi_kernel_clock_read": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_double)]),
     }

@@ -192,6 +192,32 @@ class Engine:
         L.check(self.lib.mppi_get_noise_cov(self._h, _ptr(S), _ptr(Lf), _ptr(Si), ctypes.byref(active)))
         return (S, Lf, Si) if active.value else None
 
+    def set_noise_cov_adapt(self, rate: float, sigma_min: float = 1e-3, sigma_max: float = 10.0):
+        """Adapt the full sampling covariance on the device behind every solve (mppi_set_noise_cov_adapt; the rule is
+        stats.adapt_noise_cov_f32): Sigma moves towards the batch mean of the weighted cross moments, its standard
+        deviations are clipped to [sigma_min, sigma_max] with the correlations kept, and L and Sigma^-1 are re-factored
+        on the device.  rate in (0, 1] enables (needs set_noise_cov first), 0 disables and keeps the law as it
+        stands.  Chained solves and graph streams adapt step by step with no host round trip.  Destroys captured
+        graphs, as set_noise_adapt does."""
+        L.check(self.lib.mppi_set_noise_cov_adapt(self._h, float(rate), float(sigma_min), float(sigma_max)))
+        return self
+
+    def noise_cov_adapt(self) -> tuple[float, float, float, int]:
+        """(rate, sigma_min, sigma_max, rejects) of mppi_get_noise_cov_adapt; rate 0.0 while adaptation is off; rejects:
+        the steps the device refused (a non-finite or rank-deficient blend) since it was enabled."""
+        v = [ctypes.c_float() for _ in range(3)]
+        r = ctypes.c_uint64()
+        L.check(self.lib.mppi_get_noise_cov_adapt(self._h, *(ctypes.byref(x) for x in v), ctypes.byref(r)))
+        return v[0].value, v[1].value, v[2].value, int(r.value)
+
+    def noise_cov_law(self, step: int = 0) -> np.ndarray:
+        """The Sigma [nu, nu] the adapting solve `step` drew its noise from (mppi_get_noise_cov_law; waits for the
+        stream): step 0 after a plain or chained solve, 0..n_solves-1 after graph_launch."""
+        nu = self.config.nu
+        S = np.zeros((nu, nu), np.float32)
+        L.check(self.lib.mppi_get_noise_cov_law(self._h, step, _ptr(S)))
+        return S
+
     def noise_eval(self, B: int, seed: int) -> np.ndarray:
         """The noise [B, nu, H, K] (float32) the handle's generator draws for the by-value key `seed` under the law in
         effect (mppi_noise_eval): a solve's noise for that key, ahead of bounds and kept elites.  Drops a prefetched
@@ -530,10 +556,11 @@ class Engine:
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,
-              raise_nonfinite: bool = False, stats: bool = False) -> SolveResult:
+              raise_nonfinite: bool = False, stats: bool = False, cross: bool = False) -> SolveResult:
         """One batched solve. x0 [B,nx] (or [nx]); U [B,nu,H] (or [nu,H]); noise None (device Philox) or
         [B,nu,H,K] (or [nu,H,K]). Returns the updated (and optionally shifted) U plus diagnostics.
-        stats: also compute the solve's statistics on the device (MPPI_FLAG_STATS) into SolveResult.stats."""
+        stats: also compute the solve's statistics on the device (MPPI_FLAG_STATS) into SolveResult.stats.
+        cross: the statistics plus the weighted cross moments (MPPI_FLAG_CROSS): SolveResult.stats["eps_mx"] [B,nu,nu]."""
         c = self.config
         single = np.ndim(x0) == 1
         x0 = _f32(x0).reshape(-1, c.nx)
@@ -549,12 +576,14 @@ class Engine:
         u0 = np.empty((B, c.nu), np.float32)
         io = L.mppi_io(_ptr(x0), _ptr(Uo), _ptr(nz), _ptr(costs), _ptr(weights), _ptr(u0), _ptr(cx))
         flags = (L.FLAG_SHIFT if shift else 0) | (L.FLAG_U0_BEFORE if u0_before else 0) | (
-            L.FLAG_COLMAJOR if colmajor else 0) | (L.FLAG_STATS if stats else 0)
+            L.FLAG_COLMAJOR if colmajor else 0) | (L.FLAG_STATS if stats else 0) | (L.FLAG_CROSS if cross else 0)
         rc = self.lib.mppi_solve_ex(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags)
         if rc != L.MPPI_E_NONFINITE or raise_nonfinite:
             L.check(rc)
         sq = (lambda a: a[0]) if single else (lambda a: a)
-        st = {k: sq(v) for k, v in self.stats(B).items()} if stats else None
+        st = {k: sq(v) for k, v in self.stats(B).items()} if stats or cross else None
+        if cross:
+            st["eps_mx"] = sq(self.cross_moments(B))
         return SolveResult(U=sq(Uo), costs=None if costs is None else sq(costs),
                            weights=None if weights is None else sq(weights), u0=sq(u0), status=rc, stats=st)
 
@@ -563,8 +592,9 @@ class Engine:
                      costs_ptr: int | None = None, u0_ptr: int | None = None, ctx_ptr: int | None = None,
                      weights_ptr: int | None = None, shift: bool = False, resident_U: bool = False,
                      asynchronous: bool = True, env_step: bool = False, seed_counter: bool = False,
-                     chain: bool = False, stats: bool = False) -> int:
+                     chain: bool = False, stats: bool = False, cross: bool = False) -> int:
         """stats: also compute the solve's statistics (MPPI_FLAG_STATS; read with Engine.stats);
+        cross: the statistics plus the weighted cross moments (MPPI_FLAG_CROSS; read with Engine.cross_moments);
         env_step: advance x0 in place by one dynamics step with u0 (MPPI_FLAG_ENV_STEP);
         seed_counter: noise key = seed + the handle's device counter (MPPI_FLAG_SEED_COUNTER);
         chain: a chained solve (MPPI_FLAG_CHAIN: the previous chained solve's reduce generated this one's noise;
@@ -572,7 +602,7 @@ class Engine:
         io = L.mppi_io(x0_ptr, U_ptr, noise_ptr, costs_ptr, weights_ptr, u0_ptr, ctx_ptr)
         flags = self._dev_flags(shift, resident_U, env_step) | (L.FLAG_ASYNC if asynchronous else 0) | (
             L.FLAG_SEED_COUNTER if seed_counter else 0) | (L.FLAG_CHAIN if chain else 0) | (
-            L.FLAG_STATS if stats else 0)
+            L.FLAG_STATS if stats else 0) | (L.FLAG_CROSS if cross else 0)
         return L.check(self.lib.mppi_solve_ex(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags))
 
     @staticmethod
@@ -583,19 +613,22 @@ class Engine:
     # -- receding-horizon stream as one hipGraph (mppi_graph_capture / mppi_graph_launch)
     def graph_capture(self, B: int, n_solves: int, x0_ptr: int, U_ptr: int | None = None, u0_ptr: int | None = None,
                       ctx_ptr: int | None = None, costs_ptr: int | None = None, seed: int = 0, shift: bool = True,
-                      resident_U: bool = False, env_step: bool = True, stats: bool = False):
+                      resident_U: bool = False, env_step: bool = True, stats: bool = False, cross: bool = False):
         return self.graph_capture_traj(B, n_solves, x0_ptr, U_ptr, u0_ptr, ctx_ptr, costs_ptr, seed, shift,
-                                       resident_U, env_step, stats=stats)
+                                       resident_U, env_step, stats=stats, cross=cross)
 
     def graph_capture_traj(self, B: int, n_solves: int, x0_ptr: int, U_ptr: int | None = None,
                            u0_ptr: int | None = None, ctx_ptr: int | None = None, costs_ptr: int | None = None,
                            seed: int = 0, shift: bool = True, resident_U: bool = False, env_step: bool = True,
-                           traj_x_ptr: int | None = None, traj_u_ptr: int | None = None, stats: bool = False):
+                           traj_x_ptr: int | None = None, traj_u_ptr: int | None = None, stats: bool = False,
+                           cross: bool = False):
         """Capture n_solves chained solves; with traj_*_ptr (device [n][B][nx] / [n][B][nu]) the env steps log
-        the (state, control) trajectory.  stats: solve i also writes its statistics, Engine.stats(B, step=i)."""
+        the (state, control) trajectory.  stats: solve i also writes its statistics, Engine.stats(B, step=i); cross:
+        and its weighted cross moments, Engine.cross_moments(B, step=i)."""
         io = L.mppi_io(x0_ptr, U_ptr, None, costs_ptr, None, u0_ptr, ctx_ptr)
         self._graph_io = io  # the graph holds these device pointers
-        flags = self._dev_flags(shift, resident_U, env_step) | (L.FLAG_STATS if stats else 0)
+        flags = self._dev_flags(shift, resident_U, env_step) | (L.FLAG_STATS if stats else 0) | (
+            L.FLAG_CROSS if cross else 0)
         L.check(self.lib.mppi_graph_capture_traj(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags,
                                                  n_solves, traj_x_ptr, traj_u_ptr))
         return self
@@ -643,6 +676,27 @@ class Engine:
         m11 = None if nz is None else np.zeros((B, c.nu), np.float32)
         L.check(self.lib.mppi_stats_eval(self._h, B, _ptr(costs), _ptr(nz), _ptr(rec), _ptr(m2), _ptr(m11)))
         return self._stats_dict(rec, m2, m11)
+
+    # -- weighted cross moments (MPPI_FLAG_CROSS; mppi_hip.stats.cross_moments_ref states the definition)
+    def cross_moments(self, B: int = 1, step: int = 0) -> np.ndarray:
+        """eps_mx [B, nu, nu] of the last solve made with cross=True (mppi_get_cross_moments; waits for the stream):
+        1/H sum_t sum_k w_k eps_u eps_v, symmetric, its diagonal eps_m2 bit for bit.  step as for Engine.stats."""
+        nu = self.config.nu
+        mx = np.zeros((B, nu, nu), np.float32)
+        L.check(self.lib.mppi_get_cross_moments(self._h, B, step, _ptr(mx)))
+        return mx
+
+    def cross_moments_eval(self, costs, noise) -> np.ndarray:
+        """The same kernels on host arrays (mppi_cross_moments_eval): costs [B, K] (or [K]), noise [B, nu, H, K] ->
+        eps_mx [B, nu, nu].  Uses the handle's lambda_ and norm_eps; no dynamics or cost need be loaded; touches no
+        solve state."""
+        c = self.config
+        costs = _f32(costs).reshape(-1, c.K)
+        B = costs.shape[0]
+        nz = _f32(noise).reshape(B, c.nu, c.H, c.K)
+        mx = np.zeros((B, c.nu, c.nu), np.float32)
+        L.check(self.lib.mppi_cross_moments_eval(self._h, B, _ptr(costs), _ptr(nz), _ptr(mx)))
+        return mx
 
     def device_stats(self) -> dict:
         """Device pointers of the statistics' buffers (mppi_device_stats), slot-major with max_batch as the batch

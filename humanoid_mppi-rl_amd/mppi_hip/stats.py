@@ -57,6 +57,18 @@ Keep / shift elites (mppi_set_elite_keep; csrc/elite_keep.h is the rule): the n_
 a solve, v = clamp(U + eps') taken at step t + shift, are stored and become the first columns of the next solve's noise
 as eps = v - U.  keep_store_ref and keep_inject_ref are the float32 restatements -- one add, the clamp form of
 rate_cost_v, one subtract -- and equal the device bit for bit.
+
+Weighted cross moments (MPPI_FLAG_CROSS; csrc/cross_moments.h is the fp32 definition):
+
+    eps_mx[u, v] = 1/H sum_t sum_k w_k eps[u,t,k] eps[v,t,k]
+
+cross_moments_ref is the float64 restatement (from the costs, with the weights above); cross_moments_f32 is the device's
+own summation -- the cell scheme of csrc/cross_moments.h, float32 operation by operation -- from float32 weights, and
+equals the device bit for bit.
+
+The adapted covariance (mppi_set_noise_cov_adapt; csrc/noise_cov_adapt.h is the fp32 rule): Sigma moves towards the
+batch mean of eps_mx, its standard deviations are clipped with the correlations kept, and L and Sigma^-1 are factored
+again.  adapt_noise_cov is the float64 restatement, adapt_noise_cov_f32 the step as the device takes it, bit for bit.
 """
 from __future__ import annotations
 
@@ -557,3 +569,243 @@ def keep_inject_ref(U, noise, v, count, steps):
             if m and st:
                 out[b, :, :st, :m] = (v[b, :, :st, :m] - U[b, :, :st, None]).astype(np.float32)
     return out[0] if single else out
+
+
+# ---- weighted cross moments (MPPI_FLAG_CROSS; csrc/cross_moments.h)
+
+def softmin_weights_ref(costs, lam: float = 1.0, norm_eps: float = 0.0) -> np.ndarray:
+    """costs [B, K] -> the normalised softmin weights w [B, K] of solve_stats_ref (float64; 0 on non-finite costs and
+    for a solve without a finite cost)."""
+    c = np.asarray(costs, np.float64)
+    c = c.reshape(-1, c.shape[-1])
+    w = np.zeros(c.shape)
+    for b in range(c.shape[0]):
+        fin = np.isfinite(c[b])
+        if fin.any():
+            wt = np.zeros(c.shape[1])
+            wt[fin] = np.exp(-(c[b][fin] - c[b][fin].min()) / lam)
+            w[b] = wt / (wt.sum() + norm_eps)
+    return w
+
+
+def cross_moments_ref(costs, noise, lam: float = 1.0, norm_eps: float = 0.0, absolute: bool = False) -> np.ndarray:
+    """costs [B, K], noise [B, nu, H, K] -> eps_mx [B, nu, nu] in float64.  absolute: the same sum over |e_u e_v|, the
+    scale the fp32 summation's error is measured against (off-diagonal terms cancel)."""
+    w = softmin_weights_ref(costs, lam, norm_eps)
+    e = np.asarray(noise, np.float64)
+    e = e.reshape(w.shape[0], -1, e.shape[-2], w.shape[1])
+    if absolute:
+        e = np.abs(e)
+    return np.einsum("bk,buhk,bvhk->buv", w, e, e) / e.shape[2]
+
+
+def _fma32_vec(a, b, c):
+    """fmaf(a, b, c) elementwise on float32 arrays, exactly: the product of two floats is exact in float64, the sum is
+    formed in float64 rounded TO ODD (the TwoSum residual decides), and rounding that to float32 is then the single
+    rounding of the exact a * b + c (53 >= 24 + 2 bits)."""
+    p = a.astype(np.float64) * b.astype(np.float64)
+    c = c.astype(np.float64)
+    with np.errstate(all="ignore"):
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        odd = (s.view(np.int64) & 1) != 0
+        fix = np.isfinite(s) & (err != 0.0) & ~odd
+        toward = np.where(err > 0.0, np.inf, -np.inf)
+        s = np.where(fix, np.nextafter(s, toward), s)
+        return s.astype(np.float32)
+
+
+_BUTTERFLY = [np.arange(64) ^ o for o in (32, 16, 8, 4, 2, 1)]
+
+
+def _wave_sum32(v):
+    """wave_sum of csrc/wave_reduce.h over the last axis (64 lanes): the butterfly of offsets 32, 16, ..., 1 in float32;
+    every lane ends with the same bits, lane 0 is returned."""
+    v = np.asarray(v, np.float32)
+    for perm in _BUTTERFLY:
+        v = v + v[..., perm]
+    return v[..., 0]
+
+
+def moment_cells(H: int, Kp: int):
+    """(nwc, L, nseg): the cells of one noise row (csrc/cross_moments.h moment_cells): wave-chunks of 256 k, at most 16
+    horizon segments of L steps."""
+    nwc = (Kp // 4 + 63) // 64
+    smax = min(H, 16)
+    L = (H + smax - 1) // smax
+    return nwc, L, (H + L - 1) // L
+
+
+def cross_moments_f32(w, noise) -> np.ndarray:
+    """w [B, K] float32 (the normalised weights, as the device holds them), noise [B, nu, H, K] float32 -> eps_mx
+    [B, nu, nu] float32 by the cell scheme of csrc/cross_moments.h, operation by operation: per cell (256 k x L steps)
+    and lane one chain p = w_i * e_u_i; acc = fmaf(p, e_v_i, acc) in t order and x, y, z, w within a step, the wave's
+    butterfly, then the finish pass over the cells and the division by float32(H).  Bitwise equal to the device and to
+    the header through g++."""
+    w = np.ascontiguousarray(w, np.float32)
+    e = np.ascontiguousarray(noise, np.float32)
+    B, K = w.shape
+    e = e.reshape(B, -1, e.shape[-2], K)
+    nu, H = e.shape[1], e.shape[2]
+    Kp = (K + 63) // 64 * 64
+    nwc, L, nseg = moment_cells(H, Kp)
+    nq = Kp // 4
+    # lanes beyond the row's last quad: weight 0 on the row's last quad (the device's clamp)
+    q = np.minimum(np.arange(nwc * 64), nq - 1)
+    act = np.arange(nwc * 64) < nq
+    wp = np.zeros((B, Kp), np.float32)
+    wp[:, :K] = w
+    ep = np.zeros((B, nu, H, Kp), np.float32)
+    ep[..., :K] = e
+    wl = np.where(act[None, :, None], wp.reshape(B, nq, 4)[:, q], np.float32(0.0))   # [B, lanes, 4]
+    el = ep.reshape(B, nu, H, nq, 4)[:, :, :, q]                                # [B, nu, H, lanes, 4]
+    iu, iv = np.tril_indices(nu)
+    npair = iu.size
+    part = np.zeros((B, npair, nwc, nseg), np.float32)
+    for s in range(nseg):
+        acc = np.zeros((B, npair, nwc * 64), np.float32)
+        for t in range(s * L, min(H, (s + 1) * L)):
+            for i in range(4):
+                et = el[:, :, t, :, i]                                          # [B, nu, lanes]
+                p = wl[:, None, :, i] * et
+                acc = _fma32_vec(p[:, iu], et[:, iv], acc)
+        part[:, :, :, s] = _wave_sum32(acc.reshape(B, npair, nwc, 64))
+    cells = part.reshape(B, npair, nwc * nseg)
+    ncell = nwc * nseg
+    lanes = np.zeros((B, npair, 64), np.float32)
+    for i0 in range(0, ncell, 64):
+        n = min(64, ncell - i0)
+        lanes[:, :, :n] = lanes[:, :, :n] + cells[:, :, i0:i0 + n]
+    m = _wave_sum32(lanes) / np.float32(H)
+    mx = np.zeros((B, nu, nu), np.float32)
+    mx[:, iu, iv] = m
+    mx[:, iv, iu] = m
+    return mx
+
+
+# ---- the adapted covariance (mppi_set_noise_cov_adapt; csrc/noise_cov_adapt.h)
+
+def _check_cov_adapt(rate, sigma_min, sigma_max):
+    if not 0.0 <= float(rate) <= 1.0:
+        raise ValueError("adapt_noise_cov: rate must be in [0, 1]")
+    if not (0.0 < sigma_min <= sigma_max and np.isfinite(sigma_max)):
+        raise ValueError("adapt_noise_cov: need 0 < sigma_min <= sigma_max < inf")
+
+
+def adapt_noise_cov(Sigma, eps_mx, rate: float, sigma_min: float = 1e-3, sigma_max: float = 10.0) -> np.ndarray:
+    """One step of the sampling covariance towards the noise that won the last solve(s), in float64: Sigma [nu, nu],
+    eps_mx [B, nu, nu] (or [nu, nu]) the weighted cross moments of Engine.cross_moments -> the new Sigma.  Pure.
+
+        S1 = (1 - rate) Sigma + rate mean_b eps_mx
+        s = sqrt(diag S1);  c = clip(s, sigma_min, sigma_max);  Sigma' = diag(c / s) S1 diag(c / s)
+
+    The clip is a congruence: it moves the standard deviations into the limits and keeps every correlation and the
+    positive definiteness.  ValueError on bad settings or shapes, or a diagonal of S1 that is not finite and > 0."""
+    _check_cov_adapt(rate, sigma_min, sigma_max)
+    S = np.asarray(Sigma, np.float64)
+    M = np.asarray(eps_mx, np.float64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1] or M.shape[-2:] != S.shape or M.ndim not in (2, 3):
+        raise ValueError("adapt_noise_cov: Sigma must be [nu, nu] and eps_mx [B, nu, nu] or [nu, nu]")
+    S1 = (1.0 - rate) * S + rate * M.reshape(-1, *S.shape).mean(axis=0)
+    d = np.diag(S1)
+    if not (np.all(np.isfinite(d)) and np.all(d > 0.0)):
+        raise ValueError("adapt_noise_cov: the blended diagonal must be finite and > 0")
+    s = np.sqrt(d)
+    g = np.clip(s, sigma_min, sigma_max) / s
+    return S1 * np.outer(g, g)  # (symmetric to the bit)
+
+
+def _cov_factor_full(S):
+    """csrc/noise_cov.h cov_factor in Python doubles, operation by operation: S [nu, nu] float32 (only its lower
+    triangle is read) -> (L, Sinv, sigma_u) float32, or None where a pivot is not > 0 and finite or an entry of the
+    inverse leaves float32."""
+    nu = S.shape[0]
+    Ld = [[0.0] * nu for _ in range(nu)]
+    for u in range(nu):
+        for v in range(u + 1):
+            a = float(S[u, v])
+            for j in range(v):
+                p = Ld[u][j] * Ld[v][j]
+                a = a - p
+            if u == v:
+                if not (a > 0.0 and np.isfinite(a)):
+                    return None
+                Ld[u][u] = float(np.sqrt(a))
+            else:
+                Ld[u][v] = a / Ld[v][v]
+    Wd = [[0.0] * nu for _ in range(nu)]
+    for c in range(nu):
+        for r in range(c, nu):
+            a = 1.0 if r == c else 0.0
+            for j in range(c, r):
+                p = Ld[r][j] * Wd[j][c]
+                a = a - p
+            Wd[r][c] = a / Ld[r][r]
+    Sinv = np.zeros((nu, nu), np.float32)
+    with np.errstate(over="ignore"):
+        for u in range(nu):
+            for v in range(u + 1):
+                a = 0.0
+                for j in range(u, nu):
+                    p = Wd[j][u] * Wd[j][v]
+                    a = a + p
+                f = np.float32(a)
+                if not np.isfinite(f):
+                    return None
+                Sinv[u, v] = Sinv[v, u] = f
+    L = np.array(Ld, np.float64).astype(np.float32)
+    sig = np.sqrt(np.diag(S).astype(np.float64)).astype(np.float32)
+    return L, Sinv, sig
+
+
+def adapt_noise_cov_f32(Sigma, eps_mx, rate, sigma_min=1e-3, sigma_max=10.0, n_finite=None):
+    """The device's step (csrc/noise_cov_adapt.h), float32 operation by operation and the factor in doubles as
+    noise.cov_factor runs it: Sigma [nu, nu] float32 (symmetric bit for bit, positive definite), eps_mx [B, nu, nu]
+    float32, n_finite [B] or None -> (Sigma, L, Sinv, sigma_u, status), all float32 and bitwise what the device holds
+    after the step.  status 1: the law moved; 0: some solve had no finite cost, nothing changed; -1: the step was
+    rejected (a blended scale not finite or not > 0, a pivot not > 0 and finite, an inverse beyond float32), nothing
+    changed.
+
+        Mbar = sequential float32 sum over b, / float32(B);   S1 = fmaf(rate, Mbar, (1 - rate) * Sigma)   (v <= u)
+        s_u = sqrt(S1[u][u]);  c_u = min(max(s_u, sigma_min), sigma_max);  g_u = c_u / s_u
+        S2[u][v] = (S1[u][v] * g_u) * g_v (v < u, mirrored);  S2[u][u] = S1[u][u] if c_u == s_u else c_u * c_u"""
+    from .noise import cov_factor
+    _check_cov_adapt(rate, sigma_min, sigma_max)
+    f = np.float32
+    S = np.ascontiguousarray(Sigma, np.float32)
+    nu = S.shape[0]
+    M = np.ascontiguousarray(eps_mx, np.float32).reshape(-1, nu, nu)
+    B = M.shape[0]
+
+    def held(status):
+        L, Sinv, sig = _cov_factor_full(S)
+        return S.copy(), L, Sinv, sig, status
+
+    if n_finite is not None and np.any(np.asarray(n_finite).reshape(-1) == 0):
+        return held(0)
+    rate, lo, hi = f(rate), f(sigma_min), f(sigma_max)
+    with np.errstate(all="ignore"):
+        acc = np.zeros((nu, nu), np.float32)
+        for b in range(B):
+            acc = acc + M[b]
+        Mbar = acc / f(B)
+        keep = f(1.0) - rate
+        S1 = _fma32_vec(np.full((nu, nu), rate, np.float32), Mbar, keep * S)
+        s = np.sqrt(np.diag(S1)).astype(np.float32)
+        if not (np.all(np.isfinite(s)) and np.all(s > 0.0)):
+            return held(-1)
+        c = np.minimum(np.maximum(s, lo), hi).astype(np.float32)
+        g = (c / s).astype(np.float32)
+        S2 = np.zeros((nu, nu), np.float32)
+        for u in range(nu):
+            for v in range(u):
+                S2[u, v] = S2[v, u] = f(f(S1[u, v] * g[u]) * g[v])
+            S2[u, u] = S1[u, u] if c[u] == s[u] else f(c[u] * c[u])
+    full = _cov_factor_full(S2)
+    if full is None:
+        return held(-1)
+    L, Sinv, sig = full
+    if np.all(np.isfinite(S2)):
+        assert np.array_equal(L.view(np.uint32), cov_factor(S2).view(np.uint32))  # one factor, two statements
+    return S2, L, Sinv, sig, 1

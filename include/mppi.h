@@ -108,7 +108,14 @@ extern "C" {
  *      the true Sigma^-1).  A handle that never enables it launches exactly the kernels it launched before, with the
  *      same grids.  BEHAVIOUR while a covariance is on only: mppi_set_noise_model(NULL, 0) and
  *      mppi_set_noise_model(sigma_u != NULL, .) return MPPI_E_STATE, mppi_set_noise_knots(n_knots > 0) and
- *      mppi_set_noise_adapt(rate > 0) return MPPI_E_UNSUPPORTED. */
+ *      mppi_set_noise_adapt(rate > 0) return MPPI_E_UNSUPPORTED.
+ *      Additive, version unchanged: MPPI_FLAG_CROSS, mppi_get_cross_moments / mppi_cross_moments_eval (the weighted
+ *      cross moments of a solve's noise across the actuators); kernel name "cross" in mppi_kernel_time.  A solve
+ *      without the flag launches exactly the kernels it launched before.
+ *      Additive, version unchanged: mppi_set_noise_cov_adapt / mppi_get_noise_cov_adapt / mppi_get_noise_cov_law (the
+ *      full sampling covariance adapted on the device from the cross moments); kernel name "cov_adapt".  BEHAVIOUR
+ *      while it is on only: mppi_set_noise_cov(h, NULL) returns MPPI_E_STATE, mppi_set_noise_cov(h, Sigma) resets the
+ *      device law even for the value last set, mppi_get_noise_cov / mppi_get_noise_model wait for the stream. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -196,6 +203,10 @@ extern "C" {
                                        it (plain, chained, ASYNC, host pointers, captured graphs).  U, u0, costs,
                                        weights, the seed counter and a prefetched noise are bit for bit what they are
                                        without it */
+#define MPPI_FLAG_CROSS 0x400       /* MPPI_FLAG_STATS (implied) plus the weighted CROSS moments eps_mx [nu][nu] of the
+                                       solve's noise (below), computed behind the statistics on the handle's stream;
+                                       read with mppi_get_cross_moments.  Every solve form takes it; needs nu <= 32
+                                       (MPPI_E_UNSUPPORTED otherwise).  Nothing else a solve returns changes by a bit */
 
 #define MPPI_CTX_MAX 8 /* floats of per-solve cost context */
 
@@ -429,6 +440,40 @@ int mppi_noise_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out /* [B
  * (written only while on); each pointer may be NULL. */
 int mppi_set_noise_cov(mppi_handle* h, const float* Sigma /* [nu][nu] host, or NULL: off */);
 int mppi_get_noise_cov(mppi_handle* h, float* Sigma, float* L, float* Sinv /* each [nu][nu] or NULL */, int* active);
+
+/* The covariance adapted on the device (mppi_set_noise_cov_adapt): while on, every solve of every stream form behaves as
+ * if MPPI_FLAG_CROSS were set and runs one more one-block kernel directly behind its cross moments, ahead of the launch
+ * that draws the next solve's noise.  With Mbar[u][v] the batch mean of eps_mx (below) and S the device's Sigma (the
+ * fp32 rule is csrc/noise_cov_adapt.h, its numpy restatement mppi_hip.stats.adapt_noise_cov_f32):
+ *   any n_finite[b] == 0: nothing changes
+ *   S1[u][v] = fmaf(rate, Mbar[u][v], (1 - rate) * S[u][v])
+ *   s_u = sqrtf(S1[u][u]);  c_u = clamp(s_u, sigma_min, sigma_max);  g_u = c_u / s_u
+ *   S2[u][v] = (S1[u][v] * g_u) * g_v  (v != u);   S2[u][u] = c_u == s_u ? S1[u][u] : c_u * c_u
+ * -- the clamp scales row and column u together: it clips the standard deviations and keeps the correlations -- and S2
+ * is factored by the arithmetic of mppi_set_noise_cov (in double, the same chains in the same order, L and Sinv rounded
+ * to fp32 once), so the device's L and Sinv are bit for bit what the setter computes from the same Sigma.  The step is
+ * rejected whole -- Sigma, L, Sinv, sigma_u as they were, the device counter `rejects` one up -- when some s_u is not
+ * finite or not > 0, a pivot is not > 0 and finite, or an entry of Sigma^-1 leaves fp32.  rho is not adapted.
+ * Plain, chained, captured-graph and trajectory-logging streams give bit for bit what a loop of plain solves gives;
+ * MPPI_GEN_OVERLAP=1 is ignored while it is on.  The control-cost term reads the adapted Sinv from the next solve on;
+ * mppi_control_term_eval and mppi_noise_eval use the law in effect; mppi_cross_moments_eval never adapts.
+ * mppi_set_noise_cov_adapt: rate in (0, 1] enables, rate == 0 disables and keeps the law as it stands (the host copies
+ * of Sigma, L, Sinv and sigma_u are refreshed from the device); 0 < sigma_min <= sigma_max < inf; anything else is
+ * MPPI_E_ARG and changes nothing.  Enabling needs a covariance to be on (MPPI_E_STATE otherwise: call mppi_set_noise_cov
+ * first) and nu <= 32 (MPPI_E_UNSUPPORTED).  Enabling, disabling and changing the settings drop a prefetched noise and
+ * destroy captured graphs exactly as mppi_set_noise_adapt does; the key sequence is unchanged.  The first enabling call
+ * allocates the device law; the history grows with the statistics' slots, never inside a solve.
+ * While it is on: mppi_set_noise_cov(h, Sigma) keeps its checks and resets the device law; mppi_set_noise_cov(h, NULL)
+ * returns MPPI_E_STATE (disable the adaptation first); mppi_get_noise_cov and mppi_get_noise_model wait for the stream
+ * and return the current device law.
+ * mppi_get_noise_cov_adapt: rate (0 while off), the limits, and the count of rejected steps since it was enabled.
+ * mppi_get_noise_cov_law: the Sigma [nu][nu] solve `step` drew its noise from; step as for mppi_get_stats;
+ * MPPI_E_STATE if no adapting solve has run.
+ * A stream resumes bit for bit on a fresh handle from Sigma (mppi_get_noise_cov), U, the seed counter and u_prev / the
+ * kept elites where used: mppi_set_noise_cov(Sigma) recomputes on the host the very L and Sinv the device held. */
+int mppi_set_noise_cov_adapt(mppi_handle* h, float rate, float sigma_min, float sigma_max);
+int mppi_get_noise_cov_adapt(mppi_handle* h, float* rate, float* sigma_min, float* sigma_max, uint64_t* rejects);
+int mppi_get_noise_cov_law(mppi_handle* h, int step, float* Sigma /* [nu][nu] */);
 
 /* ESS targeting: the softmin temperature chosen ON THE DEVICE, per solve, so that the solve's own costs give a requested
  * effective sample size -- lambda made scale-free, with no host round trip: plain solves (host or device pointers),
@@ -760,6 +805,23 @@ int mppi_device_stats(mppi_handle* h, void** d_stats, void** d_m2, void** d_m11)
 int mppi_stats_eval(mppi_handle* h, int B, const float* costs, const float* noise, mppi_solve_stats* stats,
                     float* eps_m2, float* eps_m11);
 
+/* Weighted cross moments (MPPI_FLAG_CROSS): the full second-moment matrix of the noise the solve used across the
+ * actuators, weighted with the statistics' w and taken about zero like eps_m2,
+ *     eps_mx[b][u][v] = 1/H sum_{t=0..H-1} sum_k w_k eps[b][u][t][k] eps[b][v][t][k]
+ * -- what a CEM / CMA-style update of a full sampling covariance (mppi_set_noise_cov) is driven by.  The matrix is
+ * symmetric bit for bit and its diagonal equals eps_m2 bit for bit: the sums are fp32 in the cell order of the
+ * per-actuator moments (csrc/cross_moments.h states it; mppi_hip.stats.cross_moments_f32 is the numpy restatement,
+ * bitwise equal), whatever the form of the kernel (env MPPI_CROSS_FORM=direct|seg, read per launch, forces one).
+ * Works with any noise (injected, default, AR(1), knots, covariance).  Needs nu <= 32.
+ * mppi_get_cross_moments: mx [B][nu][nu]; waits for the stream; step as for mppi_get_stats.  MPPI_E_STATE if no solve
+ * with the flag has run on the handle (a solve with MPPI_FLAG_STATS alone carries none).
+ * mppi_cross_moments_eval: the same kernels on host arrays, costs [B][K] and noise [B][nu][H][K], behind the
+ * statistics' cost pass with cfg.lambda -- offline analysis and host-side covariance adaptation.  Needs only
+ * mppi_create.  Like mppi_stats_eval it goes through the staging buffers (a prefetched noise is dropped, key sequence
+ * unchanged) and leaves the last solve's statistics and cross moments readable.  Kernel name "cross". */
+int mppi_get_cross_moments(mppi_handle* h, int B, int step, float* mx /* [B][nu][nu] */);
+int mppi_cross_moments_eval(mppi_handle* h, int B, const float* costs, const float* noise, float* mx /* [B][nu][nu] */);
+
 /* MPPI_PREC_BF16X3 with a CrossAttention net: *products = the products layer 1 runs with (2 or 3; 0 = not a split CA
  * handle, or no solve yet), *probe_rel_err = the probe's max relative cost difference between the two forms (-1: no
  * probe ran: forced by env, or H > 64).  Either pointer may be NULL. */
@@ -791,7 +853,8 @@ int mppi_sync(mppi_handle* h);
  * launches of mppi_set_control_bounds ahead of the rollout and behind the update, counted as one per solve),
  * "rate_cost" (the term launches of mppi_set_rate_cost and the store of u_prev, counted as one per solve), "elites"
  * (the selection of mppi_set_elites), "keep" (the inject, selection and gather launches of mppi_set_elite_keep, counted
- * as one per solve). */
+ * as one per solve), "cross" (the two launches of MPPI_FLAG_CROSS), "cov_adapt" (the update kernel of
+ * mppi_set_noise_cov_adapt). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
