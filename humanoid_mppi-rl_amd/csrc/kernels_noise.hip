@@ -3,6 +3,8 @@
 // generators of kernels_common.hip / kernels_cartpole.hip.
 // Two laws build on it: knots along the horizon (mppi_set_noise_knots; noise_knots.h, noise_knot_kernel) and a full
 // covariance across the actuators (mppi_set_noise_cov; noise_cov.h, noise_cov_kernel).
+// A third horizon law stands beside AR(1) and the knots: a dense basis (mppi_set_noise_basis; noise_basis.h,
+// noise_basis_mfma_kernel on the matrix cores up to H = 128, noise_basis_kernel beyond).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -10,6 +12,7 @@
 
 #include "mppi_internal.h"
 #include "noise_adapt.h"
+#include "noise_basis.h"
 #include "noise_cov.h"
 #include "noise_cov_adapt.h"
 #include "noise_knots.h"
@@ -356,6 +359,167 @@ __global__ __launch_bounds__(2 * kCovWaves * kWave) void noise_cov_kernel(float*
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// a1 under a horizon basis (mppi_set_noise_basis; the rule is noise_basis.h): eps[b][u][t][k] = sigma_u[u] * e[t][k],
+// e[t] = sum_r M[t][r] z[r] as ONE fmaf chain over r ascending, z[r] the white normals at counter (k/4, r, u, b).
+// H * R multiply-adds per (b, u, k) behind R draws: the first generator whose arithmetic weighs as much as its stores.
+// This is the VALU form: horizons past the MFMA form below (H > 128) run it, and MPPI_NOISE_BASIS=valu forces it (the
+// tests run both at every shape; at config #4's shape with R = 64 it takes 1.9x the MFMA form's time).
+// A block owns one (b, u) and kb = blockDim.x consecutive k (256, or 128 where R > 64: [R][kb] floats of LDS, 64 KiB at
+// most).  Its threads first draw the R x kb / 4 (r, k-quad) normals side by side into LDS (16-B writes, a row of the
+// block contiguous); behind one barrier the lane is ONE k and walks the horizon in tiles of kBasisTile = 16 steps: per r
+// one 4-B LDS read of z[r][k] (consecutive lanes, consecutive banks) feeds 16 fmaf into 16 accumulators, so the LDS
+// moves 1/16 of a float per multiply-add and the chain of every e[t] still runs over r in order.  The 16 coefficients
+// M[t0 .. t0 + 15][r] are uniform over the block: the setter stores M transposed ([R][basis_pitch(H)], pad zero) and they
+// arrive as one scalar load through the constant address space into SGPRs, which the fmaf reads directly.
+// One 4-B nontemporal store per lane and step, as in noise_ar1_lds_kernel: 256 contiguous bytes per wave, 1 KiB per
+// block and step.  The pad lanes K..Kp are written like every other lane; waves past Kp (Kp is a multiple of 64: whole
+// waves) draw and store nothing but meet the barrier.  Steps H..pitch of the last tile are mixed (zeros) and not stored.
+// The operations per element are basis_mix's in basis_mix's order: host and device agree bit for bit.
+// ------------------------------------------------------------------------------------------------
+typedef float basis_f16 __attribute__((ext_vector_type(16)));
+typedef const __attribute__((address_space(4))) basis_f16* basis_rows;
+static_assert(sizeof(basis_f16) == kBasisTile * sizeof(float), "one scalar load per tile and r");
+constexpr int kBasisWideR = 64;  // up to here a block owns 256 k (R KiB of LDS), beyond 128 k (R / 2 KiB)
+
+__global__ __launch_bounds__(256) void noise_basis_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
+                                                          uint64_t seed, const unsigned long long* seed_ctr,
+                                                          NoiseModel m) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  extern __shared__ __attribute__((aligned(16))) float basis_z[];  // [R][kb]
+  const int bu = blockIdx.z * 65535 + blockIdx.y;  // b*nu + u
+  const int kb = blockDim.x;
+  const int k_base = blockIdx.x * kb;
+  if (bu >= nbu || k_base >= Kp) return;  // (uniform per block: before the barrier)
+  const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+  const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+  const int u = bu % nu;
+  const int b = bu / nu;
+  const int R = m.n_basis;
+  const int nq = kb >> 2;  // k-quads per row of the block
+  for (int i = threadIdx.x; i < R * nq; i += kb) {
+    const int r = i / nq, q = i - r * nq;
+    if (k_base + 4 * q < Kp) {
+      float z[4];
+      philox_normal4((uint32_t)(k_base / 4 + q), (uint32_t)r, (uint32_t)u, (uint32_t)b, k0, k1, z);
+      reinterpret_cast<knot_f4*>(basis_z)[i] = knot_f4{z[0], z[1], z[2], z[3]};  // [r][4 q .. 4 q + 3]
+    }
+  }
+  __syncthreads();
+  const int k = k_base + threadIdx.x;
+  if (k >= Kp) return;
+  const float su = m.sigma_u[u];
+  const float* zk = basis_z + threadIdx.x;  // z[r] of this k: zk[r * kb]
+  const int tiles = basis_pitch(H) / kBasisTile;
+  const basis_rows MT = (basis_rows)m.basis_T;  // the table is written by the setter only, never during a launch
+  float* dst = noise + (long)bu * H * Kp + k;   // row t: dst + t * Kp
+  for (int tt = 0; tt < tiles; ++tt) {
+    float e[kBasisTile];
+    {
+      const basis_f16 c = MT[tt];
+      const float z = zk[0];
+#pragma unroll
+      for (int i = 0; i < kBasisTile; ++i) e[i] = c[i] * z;
+    }
+#pragma unroll 4
+    for (int r = 1; r < R; ++r) {
+      const basis_f16 c = MT[r * tiles + tt];
+      const float z = zk[r * kb];
+#pragma unroll
+      for (int i = 0; i < kBasisTile; ++i) e[i] = fmaf(c[i], z, e[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < kBasisTile; ++i) {
+      const int t = tt * kBasisTile + i;
+      if (t < H) __builtin_nontemporal_store(su * e[i], dst + (long)t * Kp);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same law on the matrix cores, for H <= 16 kNT (noise_basis_mfma_kernel<kNT>): v_mfma_f32_16x16x4_f32 is exact
+// fp32 and accumulates its four k in ascending order, one rounding per product -- an fmaf chain -- so with rows = steps,
+// columns = samples and the MFMA's k = the basis index r, a chain of R / 4 instructions IS basis_mix's chain.  Two
+// details make it so to the bit: the accumulators start at -0.0f (fmaf(a, b, -0) = a * b for every finite a b, signed
+// zeros included: the rule's first operation is a product, not an fmaf onto +0), and R is padded to a multiple of 4
+// with coefficients -0.0f against normals +0: each pad adds -0, which leaves every value, -0 included, as it is.
+// One wave owns 64 consecutive k of one (b, u) and ALL H steps: 4 kNT accumulator quads.  Per group of four r, lane l
+// draws ONE Philox quad -- r = r0 + (l >> 4), k-quad (l & 15) -- and its four normals are, as they stand, the B operands
+// of four MFMAs whose column j = l & 15 is sample 4 j + c of accumulator set c: no LDS, no transposition, and every
+// normal is drawn once.  The A operand of step tile n is M[16 n + (l & 15)][r0 + (l >> 4)], one 4-B load per lane from
+// the transposed table (four 64-B rows per wave; the table is 32 KiB at most and stays in cache).  At the end register i
+// of the four sets of tile n is steps 16 n + 4 (l >> 4) + i of samples 4 j .. 4 j + 3: one 16-B nontemporal store, 256
+// contiguous bytes per row.  No barrier; 4 kNT + ~40 VGPRs.
+// ------------------------------------------------------------------------------------------------
+constexpr int kBasisMfmaMaxNT = 8;  // H <= 128: beyond, noise_basis_kernel
+static_assert(kBasisTile == 16, "a tile of steps is the 16 rows of one MFMA");
+
+template <int kNT>
+__global__ __launch_bounds__(256) void noise_basis_mfma_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
+                                                               uint64_t seed, const unsigned long long* seed_ctr,
+                                                               NoiseModel m) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int bu = blockIdx.z * 65535 + blockIdx.y;  // b*nu + u
+  const int lane = threadIdx.x & (kWave - 1);
+  const int k_base = (blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave) * kWave;  // of this wave
+  if (bu >= nbu || k_base >= Kp) return;  // (whole waves: Kp is a multiple of 64)
+  const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+  const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+  const int u = bu % nu;
+  const int b = bu / nu;
+  const int R = m.n_basis;
+  const int j = lane & 15, rr = lane >> 4;
+  const int pitch = basis_pitch(H);
+  const float* mt = m.basis_T + j;  // A of (tile n, r): mt[r * pitch + 16 n]; rows R .. round_up(R, 4) hold -0.0f
+  knot_f4 acc[kNT][4];
+#pragma unroll
+  for (int n = 0; n < kNT; ++n)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[n][c] = knot_f4{-0.0f, -0.0f, -0.0f, -0.0f};
+  // (The MFMAs of one group and the draw of the next dealt out between them in one basic block measured the same: the
+  // f32 MFMA and the VALU do not run side by side on a SIMD)
+  for (int r0 = 0; r0 < R; r0 += 4) {
+    const int r = r0 + rr;
+    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (r < R) philox_normal4((uint32_t)(k_base / 4 + j), (uint32_t)r, (uint32_t)u, (uint32_t)b, k0, k1, z);
+    const float* row = mt + (long)r * pitch;
+#pragma unroll
+    for (int n = 0; n < kNT; ++n) {
+      const float a = row[16 * n];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[n][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, z[c], acc[n][c], 0, 0, 0);
+    }
+  }
+  const float su = m.sigma_u[u];
+  float* dst = noise + (long)bu * H * Kp + k_base + 4 * j;  // row t: dst + t * Kp
+#pragma unroll
+  for (int n = 0; n < kNT; ++n)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int t = 16 * n + 4 * rr + i;
+      if (t < H) {
+        const knot_f4 v = {su * acc[n][0][i], su * acc[n][1][i], su * acc[n][2][i], su * acc[n][3][i]};
+        __builtin_nontemporal_store(v, reinterpret_cast<knot_f4*>(dst + (long)t * Kp));
+      }
+    }
+}
+
+template <int kNT>
+static void launch_basis_mfma(int nt, float* noise, int nbu, int nu, int H, int Kp, uint64_t seed,
+                              const unsigned long long* seed_ctr, const NoiseModel& model, hipStream_t stream) {
+  if constexpr (kNT > 1) {
+    if (nt < kNT) return launch_basis_mfma<kNT - 1>(nt, noise, nbu, nu, H, Kp, seed, seed_ctr, model, stream);
+  }
+  const int threads = Kp >= 256 ? 256 : Kp;  // (Kp is a multiple of 64)
+  const dim3 grid((Kp + threads - 1) / threads, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
+  hipLaunchKernelGGL(noise_basis_mfma_kernel<kNT>, grid, dim3(threads), 0, stream, noise, nbu, nu, H, Kp, seed,
+                     seed_ctr, model);
+}
+
 // MPPI_NOISE_AR1=direct|lds (read per launch; an A/B and test knob): force one of the two kernels (lds: where its
 // LDS row fits, H <= 256); default: noise_ar1_lds_kernel when noise_ar1_kernel would have fewer waves than SIMDs
 static int ar1_knob() {
@@ -370,6 +534,22 @@ hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64
   if (!model.active) return launch_noise(noise, B, nu, H, Kp, seed, seed_ctr, sigma, stream);
   if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_model refuses such a handle)
   const int nbu = B * nu, nq = Kp / 4;
+  if (model.n_basis > 0) {  // a horizon basis (mppi_set_noise_basis refuses it beside every other law but sigma_u)
+    if (d_law || model.cov_L || model.n_knots > 0 || !model.basis_T || model.n_basis > H || model.n_basis > kMaxBasis)
+      return hipErrorInvalidValue;
+    // MPPI_NOISE_BASIS=valu (read per launch; an A/B and test knob) forces noise_basis_kernel where the MFMA form fits
+    const char* knob = std::getenv("MPPI_NOISE_BASIS");
+    const int nt = basis_pitch(H) / kBasisTile;
+    if (nt <= kBasisMfmaMaxNT && !(knob && std::strcmp(knob, "valu") == 0)) {
+      launch_basis_mfma<kBasisMfmaMaxNT>(nt, noise, nbu, nu, H, Kp, seed, seed_ctr, model, stream);
+      return hipGetLastError();
+    }
+    const int kb = model.n_basis <= kBasisWideR ? 256 : 128;
+    const dim3 grid((Kp + kb - 1) / kb, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
+    hipLaunchKernelGGL(noise_basis_kernel, grid, dim3(kb), (size_t)model.n_basis * kb * sizeof(float), stream, noise,
+                       nbu, nu, H, Kp, seed, seed_ctr, model);
+    return hipGetLastError();
+  }
   if (model.cov_L) {  // a cross-actuator covariance (mppi_set_noise_cov refuses it beside a knot law or an adapted one)
     if (d_law || model.n_knots > 0) return hipErrorInvalidValue;
     const int nd = nu < kCovWaves ? nu : kCovWaves, np = (nu + 1) / 2;  // drawers and mixers (noise_cov_kernel)

@@ -23,6 +23,7 @@
 #include "noise_adapt.h"  // NoiseAdapt
 #include "noise_cov.h"    // cov_factor
 #include "noise_cov_adapt.h"  // NoiseCovAdapt
+#include "noise_basis.h"  // basis_law_valid
 #include "noise_knots.h"  // knot_table
 #include "noise_model.h"  // ar1_innovation_scale
 
@@ -181,6 +182,11 @@ struct mppi_handle {
   void* d_knots = nullptr;
   std::vector<int32_t> knot_idx;
   std::vector<float> knot_w;
+  // the horizon basis (mppi_set_noise_basis; noise_basis.h, noise_basis_kernel).  noise_model.n_basis is the law; d_basis
+  // holds M transposed, [min(H, kMaxBasis)][basis_pitch(H)] fp32, allocated by the first enabling call and written by
+  // the setter only; basis_host is the host's copy of M [H][n_basis] as given (mppi_get_noise_basis)
+  float* d_basis = nullptr;
+  std::vector<float> basis_host;
   // the cross-actuator covariance (mppi_set_noise_cov; noise_cov.h, noise_cov_kernel).  noise_model.cov_L != nullptr
   // is the law; d_cov holds L [nu][kMaxNu] (rows padded) then Sinv [nu][nu], allocated by the first enabling call and written by the
   // setter and, while cov_adapt_on, by noise_cov_adapt_kernel; cov_host is the host's copy, Sigma, L, Sinv [nu][nu] each
@@ -473,7 +479,7 @@ void mppi_destroy(mppi_handle* h) {
   void* bufs[] = {h->d_x0, h->d_U, h->d_noise, h->d_costs, h->d_dU, h->d_weights, h->d_u0, h->d_ctx, h->d_status,
                   h->d_tickets, const_cast<char*>(h->net.fa.img), const_cast<char*>(h->net_env.fa.img), h->fa.d_img,
                   h->fa.d_ws, h->d_seed_ctr, h->d_env_noise, h->d_env_costs, h->d_env_status, h->d_noise2, h->d_gticket, h->d_part, h->d_kclock,
-                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_cross_mx, h->d_cross_part, h->d_cov_law, h->d_cov_hist, h->d_law, h->d_law_hist, h->d_knots, h->d_cov,
+                  h->d_stats, h->d_stats_m2, h->d_stats_m11, h->d_stats_w, h->d_stats_part, h->d_cross_mx, h->d_cross_part, h->d_cov_law, h->d_cov_hist, h->d_law, h->d_law_hist, h->d_knots, h->d_cov, h->d_basis,
                   h->d_lambda, h->d_wcost, h->d_term, h->d_lin, h->d_ctrl_part, h->d_ctrl_U, h->d_bcounts,
                   h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev,
                   h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
@@ -1869,6 +1875,12 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
   if (!active && h->noise_model.n_knots > 0)
     return fail(MPPI_E_STATE, "mppi_set_noise_model: (NULL, 0) is the default path, which has no knot law: "
                               "call mppi_set_noise_knots(h, 0, 0) first");
+  if (!active && h->noise_model.n_basis > 0)
+    return fail(MPPI_E_STATE, "mppi_set_noise_model: (NULL, 0) is the default path, which has no horizon basis: "
+                              "call mppi_set_noise_basis(h, 0, NULL) first");
+  if (rho != 0.0f && h->noise_model.n_basis > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_model: rho != 0 not together with mppi_set_noise_basis (the basis "
+                                    "is the horizon correlation)");
   if (h->noise_model.cov_L && !active)
     return fail(MPPI_E_STATE, "mppi_set_noise_model: (NULL, 0) is the default path, which has no covariance: "
                               "call mppi_set_noise_cov(h, NULL) first");
@@ -1884,6 +1896,7 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
   m.n_knots = h->noise_model.n_knots, m.order = h->noise_model.order;  // the knot law stays (mppi_set_noise_knots)
   m.kidx = h->noise_model.kidx, m.kw = h->noise_model.kw;
   m.cov_L = h->noise_model.cov_L;  // ... and so does the covariance (mppi_set_noise_cov): only rho changes under it
+  m.n_basis = h->noise_model.n_basis, m.basis_T = h->noise_model.basis_T;  // ... and the basis (mppi_set_noise_basis)
   m.active = active || h->adapt_on ? 1 : 0;  // (an adapting handle's model stays active: (NULL, 0) is its values)
   m.rho = rho;
   m.c = ar1_innovation_scale(rho);
@@ -1925,6 +1938,9 @@ int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigm
   if (on && h->noise_model.cov_L)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: not together with mppi_set_noise_cov (the rule adapts "
                                     "sigma_u, which is not the law under a full covariance)");
+  if (on && h->noise_model.n_basis > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: not together with mppi_set_noise_basis (the moment "
+                                    "estimates of sigma_u and rho assume AR(1))");
   if (!on && !h->adapt_on) {  // nothing to disable: only the limits are kept
     h->adapt = NoiseAdapt{0.0f, sigma_min, sigma_max, rho_max};
     return MPPI_OK;
@@ -2019,6 +2035,9 @@ int mppi_set_noise_knots(mppi_handle* h, int n_knots, int order) {
   if (on && m.cov_L)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: not together with mppi_set_noise_cov (the knot generator "
                                     "does not mix the actuators)");
+  if (on && m.n_basis > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: not together with mppi_set_noise_basis (both are horizon "
+                                    "laws)");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)c.H * 4;
   if (on && !h->d_knots) HIP_TRY(hipMalloc(&h->d_knots, n * (sizeof(int32_t) + sizeof(float))));
@@ -2065,6 +2084,81 @@ int mppi_get_noise_knots(mppi_handle* h, int* n_knots, int* order, int32_t* idx,
   return MPPI_OK;
 }
 
+int mppi_set_noise_basis(mppi_handle* h, int n_basis, const float* M) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_basis: null handle");
+  const mppi_config& c = h->cfg;
+  const bool on = n_basis != 0;
+  if (on && (!basis_law_valid(c.H, n_basis) || !M))
+    return fail(MPPI_E_ARG, "mppi_set_noise_basis: need n_basis in 1..H with M [H][n_basis], or n_basis == 0");
+  if (on && !basis_table_finite(M, c.H, n_basis))
+    return fail(MPPI_E_ARG, "mppi_set_noise_basis: every entry of M must be finite");
+  if (on && n_basis > kMaxBasis)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: n_basis <= 128 (it bounds the generators' registers and "
+                                    "LDS)");
+  NoiseModel m = h->noise_model;
+  if (!on && m.n_basis == 0) return MPPI_OK;  // nothing to disable
+  const size_t n = on ? (size_t)c.H * n_basis : 0;
+  // the table in effect, bitwise: prefetch and graphs stay
+  if (on && m.n_basis == n_basis && std::memcmp(M, h->basis_host.data(), n * sizeof(float)) == 0) return MPPI_OK;
+  if (on && c.nu > kMaxNu)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: a horizon basis is an active noise model (nu <= 32)");
+  if (on && m.n_knots > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: not together with mppi_set_noise_knots (both are horizon "
+                                    "laws)");
+  if (on && m.cov_L)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: not together with mppi_set_noise_cov / "
+                                    "mppi_set_noise_cov_adapt (the basis generator does not mix the actuators)");
+  if (on && h->adapt_on)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: not together with mppi_set_noise_adapt (the moment "
+                                    "estimates of sigma_u and rho assume AR(1))");
+  if (on && h->ctrl_gamma > 0.0f)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: not together with mppi_set_control_cost (the term needs the "
+                                    "inverse of M M^T, singular for n_basis < H)");
+  if (on && m.active && m.rho != 0.0f)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: not together with rho != 0 of mppi_set_noise_model (the "
+                                    "basis is the horizon correlation)");
+  HIP_TRY(hipSetDevice(h->device));
+  const int pitch = basis_pitch(c.H);
+  if (on && !h->d_basis)
+    HIP_TRY(hipMalloc(&h->d_basis, (size_t)basis_rows_padded(c.H < kMaxBasis ? c.H : kMaxBasis) * pitch * sizeof(float)));
+  // stale state, as in mppi_set_noise_model: the prefetched noise (the counter steps back: the key sequence is
+  // unchanged) and the captured graphs, whose generators are those of the other law
+  HIP_TRY(drop_prefetch(h));
+  MPPI_TRY(drop_graphs(h, true));
+  if (on) {
+    // M^T, the pad of every row zero; the rows up to a multiple of four -0.0f (they add -0 to a chain: nothing)
+    std::vector<float> host(M, M + n), mt((size_t)basis_rows_padded(n_basis) * pitch, 0.0f);
+    std::fill(mt.begin() + (size_t)n_basis * pitch, mt.end(), -0.0f);
+    for (int t = 0; t < c.H; ++t)
+      for (int r = 0; r < n_basis; ++r) mt[(size_t)r * pitch + t] = M[(size_t)t * n_basis + r];
+    // every launch that reads the table has finished before it changes (the generator stream included: drop_prefetch
+    // made the stream wait for it)
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->d_basis, mt.data(), mt.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->basis_host.swap(host);
+    if (!m.active) {  // the default law as an active model: value for value the same normals
+      m = NoiseModel{};
+      m.active = 1;
+      for (int u = 0; u < c.nu; ++u) m.sigma_u[u] = c.sigma;
+    }
+    m.n_basis = n_basis;
+    m.basis_T = h->d_basis;
+  } else {  // sigma_u stays as it stands: the rho = 0 generators again
+    m.n_basis = 0;
+    m.basis_T = nullptr;
+  }
+  h->noise_model = m;
+  return MPPI_OK;
+}
+
+int mppi_get_noise_basis(mppi_handle* h, int* n_basis, float* M) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_basis: null handle");
+  const NoiseModel& m = h->noise_model;
+  if (n_basis) *n_basis = m.n_basis;
+  if (m.n_basis > 0 && M) std::memcpy(M, h->basis_host.data(), h->basis_host.size() * sizeof(float));  // (off: untouched)
+  return MPPI_OK;
+}
+
 // the host's covariance (cov_host's Sigma, noise_model.sigma_u) -> d_cov_law; the stream is idle.  reset: the count of
 // rejected steps starts again
 static int upload_cov_law(mppi_handle* h, bool reset) {
@@ -2100,6 +2194,9 @@ int mppi_set_noise_cov_adapt(mppi_handle* h, float rate, float sigma_min, float 
   const bool on = rate > 0.0f;
   if (on && h->cfg.nu > kMaxNu)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov_adapt: the adapted covariance needs nu <= 32");
+  if (on && h->noise_model.n_basis > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov_adapt: not together with mppi_set_noise_basis (the basis "
+                                    "generator does not mix the actuators)");
   if (on && !h->noise_model.cov_L)
     return fail(MPPI_E_STATE, "mppi_set_noise_cov_adapt: no covariance to adapt: call mppi_set_noise_cov first");
   if (!on && !h->cov_adapt_on) {  // nothing to disable: only the limits are kept
@@ -2184,6 +2281,9 @@ int mppi_set_noise_cov(mppi_handle* h, const float* Sigma) {
     if (h->adapt_on)
       return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov: not together with mppi_set_noise_adapt (the rule adapts "
                                       "sigma_u, which is not the law under a full covariance)");
+    if (m.n_basis > 0)
+      return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov: not together with mppi_set_noise_basis (the basis generator "
+                                      "does not mix the actuators)");
     HIP_TRY(hipSetDevice(h->device));
     if (!h->d_cov) HIP_TRY(hipMalloc(&h->d_cov, ((size_t)c.nu * kMaxNu + nn) * sizeof(float)));
     if (!m.active) {  // the default law as an active model: rho = 0, the same normals
@@ -2317,6 +2417,9 @@ int mppi_set_control_cost(mppi_handle* h, float gamma) {
   if (gamma > 0.0f && h->noise_model.n_knots > 0)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_control_cost: not together with mppi_set_noise_knots (the term needs the "
                                     "inverse of the sampling covariance, which a knot law leaves singular)");
+  if (gamma > 0.0f && h->noise_model.n_basis > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_control_cost: not together with mppi_set_noise_basis (the term needs the "
+                                    "inverse of M M^T, singular for n_basis < H)");
   HIP_TRY(hipSetDevice(h->device));
   const mppi_config& c = h->cfg;
   if (gamma > 0.0f && !h->d_wcost) {  // all of the term's buffers, once, or none (every entry is written before it is read)

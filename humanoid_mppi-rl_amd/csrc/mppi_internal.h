@@ -287,10 +287,19 @@ struct NoiseModel {
   // the cross-actuator covariance (mppi_set_noise_cov; noise_cov.h): nullptr: off; else the factor L [nu][kMaxNu] (device
   // memory the setter owns) that mixes the unit-variance AR(1) rows; sigma_u is then sqrt(diag Sigma) and not read
   const float* cov_L = nullptr;
+  // the horizon basis (mppi_set_noise_basis; noise_basis.h): n_basis = 0: off; else eps = sigma_u M z over n_basis white
+  // normals per (b, u, k); basis_T (device memory the setter owns) is M transposed, [basis_rows_padded(n_basis)]
+  // [basis_pitch(H)]: the pad of every row zero (the coefficients of 16 consecutive steps and one r are one aligned
+  // load), the rows past n_basis -0.0f (the MFMA form mixes four r at a time; a product of -0 adds nothing to a chain)
+  int n_basis = 0;
+  const float* basis_T = nullptr;
 };
+constexpr int kBasisTile = 16;  // steps noise_basis_kernel mixes per pass over the normals: the pitch's granule
+constexpr int basis_pitch(int H) { return (H + kBasisTile - 1) / kBasisTile * kBasisTile; }
+constexpr int basis_rows_padded(int R) { return (R + 3) / 4 * 4; }  // rows of basis_T: the MFMA form mixes four r at a time
 // every explicit generation site: noise_kernel (inactive model, sigma) or, with the model active, noise_ar1_kernel /
-// noise_ar1_lds_kernel (grids too small to fill the chip), noise_knot_kernel (a knot law) or noise_cov_kernel (a
-// cross-actuator covariance); kernels_noise.hip.  d_law (or nullptr): the device law of
+// noise_ar1_lds_kernel (grids too small to fill the chip), noise_knot_kernel (a knot law), noise_basis_kernel (a horizon
+// basis) or noise_cov_kernel (a cross-actuator covariance); kernels_noise.hip.  d_law (or nullptr): the device law of
 // a handle that adapts it on the stream (mppi_set_noise_adapt) -- the same generators reading sigma_u, rho and c from
 // device memory instead of the by-value model (noise_ar1_dev_kernel / noise_ar1_lds_dev_kernel)
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,

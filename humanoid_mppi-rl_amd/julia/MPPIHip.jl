@@ -291,6 +291,42 @@ function noise_knots(c::Controller)
 end
 
 """
+    set_noise_basis!(c, M)
+
+Horizon-basis sampling noise (mppi_set_noise_basis): the device noise of one sample is `M` (H x R, indexed [t, r],
+1 <= R <= min(H, 128), finite) applied along the horizon to R white normals and scaled by sigma_u -- coloured noise,
+temporal kernels, spline or cosine bases.  `nothing` disables and keeps sigma_u.  Not together with rho != 0,
+`set_noise_knots!`, `set_noise_cov!`, `set_noise_adapt!` or `set_control_cost!`.
+"""
+function set_noise_basis!(c::Controller, M::Union{Nothing, AbstractMatrix})
+    if M === nothing
+        check(ccall((:mppi_set_noise_basis, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle, 0, C_NULL))
+        return c
+    end
+    size(M, 1) == c.cfg.H || throw(ArgumentError("M must be H x R"))
+    A = Matrix{Float32}(permutedims(M))   # the C ABI's [H][R] is row-major
+    GC.@preserve A check(ccall((:mppi_set_noise_basis, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle,
+                               size(M, 2), pointer(A)))
+    return c
+end
+
+"""
+    noise_basis(c) -> M::Matrix{Float32} or nothing
+
+The table of the handle's basis law as set (mppi_get_noise_basis), H x R indexed [t, r] as in C; `nothing` while the
+law is off.
+"""
+function noise_basis(c::Controller)
+    n = Ref{Cint}(0)
+    check(ccall((:mppi_get_noise_basis, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float32}), c.handle, n, C_NULL))
+    n[] == 0 && return nothing
+    A = zeros(Float32, Int(n[]), c.cfg.H)
+    GC.@preserve A check(ccall((:mppi_get_noise_basis, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float32}), c.handle, n,
+                               pointer(A)))
+    return permutedims(A)   # row-major C -> [t, r]
+end
+
+"""
     set_noise_cov!(c, Sigma)
 
 Cross-actuator sampling covariance (mppi_set_noise_cov): the device noise of one step is drawn with the full covariance

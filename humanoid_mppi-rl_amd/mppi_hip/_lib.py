@@ -37,7 +37,8 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_rate_term_eval", "mppi_set_elites", "mppi_get_elites", "mppi_get_elite_set", "mppi_elites_eval",
             "mppi_set_elite_keep", "mppi_get_elite_keep", "mppi_get_kept", "mppi_set_kept", "mppi_keep_store_eval",
             "mppi_keep_inject_eval", "mppi_get_cross_moments", "mppi_cross_moments_eval",
-            "mppi_set_noise_cov_adapt", "mppi_get_noise_cov_adapt", "mppi_get_noise_cov_law"]
+            "mppi_set_noise_cov_adapt", "mppi_get_noise_cov_adapt", "mppi_get_noise_cov_law", "mppi_set_noise_basis",
+            "mppi_get_noise_basis"]
 
 
 class MPPIError(RuntimeError):
@@ -124,6 +125,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_get_noise_adapt": (i32, [vp] + [ctypes.POINTER(ctypes.c_float)] * 4),
         "mppi_set_noise_knots": (i32, [vp, i32, i32]),
         "mppi_get_noise_knots": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp]),
+        "mppi_set_noise_basis": (i32, [vp, i32, vp]),
+        "mppi_get_noise_basis": (i32, [vp, ctypes.POINTER(i32), vp]),
         "mppi_set_noise_cov": (i32, [vp, vp]),
         "mppi_get_noise_cov": (i32, [vp, vp, vp, vp, ctypes.POINTER(i32)]),
         "mppi_noise_eval": (i32, [vp, i32, ctypes.c_uint64, vp]),

@@ -25,7 +25,7 @@ import numpy as np
 from . import _lib as L
 from .engine import Config, Engine
 from .nets import cross_attention_blob, feature_attention_blob, mlp_blob
-from .noise import ar1_filter, knot_filter
+from .noise import ar1_filter, basis_filter, colored_basis, knot_filter
 from .stats import adapt_noise_model
 
 # default cost of each preset (the reference script it mirrors)
@@ -58,6 +58,10 @@ class MPPIModel:
               law above drawn at n_knots knots along the horizon and interpolated, order 0 (hold), 1 (linear, the
               default) or 3 (Catmull-Rom); both noise modes sample the same law.  Not together with adapt_noise or
               control_cost.
+    noise_basis: None (default), an [H, R] array or ("colored", beta[, n_basis]): horizon-basis noise
+              (Engine.set_noise_basis) -- the table applied along the horizon to R white normals per sample, scaled by
+              noise_sigma; ("colored", beta) is noise.colored_basis(H, beta), iCEM's power-law noise.  Both noise modes
+              sample the same law.  Not together with noise_knots, noise_rho != 0, adapt_noise or control_cost.
     adapt_noise: above 0, mppi_step / mppi_controller request the solve's statistics (Engine.solve(stats=True)) and
               after each step move the law towards the weighted moments of the noise that won
               (stats.adapt_noise_model with this rate and adapt_limits = (sigma_min, sigma_max, rho_max)), through
@@ -94,7 +98,8 @@ class MPPIModel:
                  body_ids: dict | None = None, u0_before: bool = False, noise_sigma=None, noise_rho: float = 0.0,
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
                  lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, rate_cost=None,
-                 rate_anchor: bool = True, n_elite: int = 0, n_keep: int = 0, noise_knots=None, **overrides):
+                 rate_anchor: bool = True, n_elite: int = 0, n_keep: int = 0, noise_knots=None, noise_basis=None,
+                 **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -167,6 +172,12 @@ class MPPIModel:
             if self.adapt_noise > 0.0 or self.control_cost > 0.0:
                 raise ValueError("MPPIModel: noise_knots does not go together with adapt_noise or control_cost")
             self.engine.set_noise_knots(int(n_knots), int(order))
+        self._noise_basis = None
+        if noise_basis is not None:
+            if noise_knots is not None or self._noise_rho != 0.0 or self.adapt_noise > 0.0 or self.control_cost > 0.0:
+                raise ValueError("MPPIModel: noise_basis does not go together with noise_knots, noise_rho != 0, "
+                                 "adapt_noise or control_cost")
+            self.noise_basis = noise_basis
         if self.device_adapt:
             self.engine.set_noise_adapt(self.adapt_noise, *self.adapt_limits)
         if self.ess_target > 0.0:
@@ -264,6 +275,25 @@ class MPPIModel:
         self.engine.set_noise_knots(int(n_knots), int(order))
 
     @property
+    def noise_basis(self):
+        """M [H, R] (float32) of the engine's basis law as it was set here, or None while it is off."""
+        return getattr(self, "_noise_basis", None)
+
+    @noise_basis.setter
+    def noise_basis(self, v):
+        if v is None:
+            self.engine.set_noise_basis(None)
+            self._noise_basis = None
+            return
+        if isinstance(v, tuple) and len(v) in (2, 3) and isinstance(v[0], str) and v[0] == "colored":
+            v = colored_basis(self.config.H, *v[1:])
+        M = np.ascontiguousarray(np.asarray(v, np.float32))
+        if M.ndim != 2 or M.shape[0] != self.config.H or not 1 <= M.shape[1] <= self.config.H:
+            raise ValueError(f"MPPIModel: noise_basis must be [H = {self.config.H}, R] with 1 <= R <= H")
+        self.engine.set_noise_basis(M)
+        self._noise_basis = M
+
+    @property
     def K(self):
         return self.config.K
 
@@ -275,6 +305,9 @@ class MPPIModel:
         c = self.config
         if self.noise == "numpy":
             z = np.random.randn(c.nu, c.H, c.K)
+            if self.noise_basis is not None:
+                return basis_filter(z, self.noise_basis,
+                                    c.sigma if self.noise_sigma is None else self.noise_sigma).astype(np.float64)
             if self.noise_knots is not None:
                 return knot_filter(z, *self.noise_knots, rho=self.noise_rho,
                                    sigma_u=c.sigma if self.noise_sigma is None else self.noise_sigma).astype(np.float64)

@@ -166,6 +166,32 @@ class Engine:
             return 0, 0, None, None
         return int(n.value), int(order.value), idx, w
 
+    def set_noise_basis(self, M):
+        """Horizon-basis sampling noise (mppi_set_noise_basis; noise.basis_filter states the law, noise.colored_basis
+        builds iCEM's power-law table): the device noise of one (b, u, k) is M [H, R] (float32, 1 <= R <= min(H, 128))
+        applied along the horizon to R white normals, scaled by sigma_u.  None disables and keeps sigma_u.  Makes the
+        noise model active; destroys captured graphs, as set_noise_model does.  Not together with rho != 0,
+        set_noise_knots, set_noise_cov, set_noise_adapt or set_control_cost."""
+        if M is None:
+            L.check(self.lib.mppi_set_noise_basis(self._h, 0, None))
+            return self
+        A = _f32(M)
+        H = self.config.H
+        if A.ndim != 2 or A.shape[0] != H or A.shape[1] < 1:
+            raise ValueError(f"set_noise_basis: M must be [{H}, R] with R >= 1, got {list(A.shape)}")
+        L.check(self.lib.mppi_set_noise_basis(self._h, int(A.shape[1]), _ptr(A)))
+        return self
+
+    def noise_basis(self) -> np.ndarray | None:
+        """M [H, R] float32 of the handle's basis law as set, bitwise (mppi_get_noise_basis); None while off."""
+        n = ctypes.c_int()
+        L.check(self.lib.mppi_get_noise_basis(self._h, ctypes.byref(n), None))
+        if n.value == 0:
+            return None
+        A = np.zeros((self.config.H, n.value), np.float32)
+        L.check(self.lib.mppi_get_noise_basis(self._h, ctypes.byref(n), _ptr(A)))
+        return A
+
     def set_noise_cov(self, Sigma):
         """Cross-actuator sampling covariance (mppi_set_noise_cov; noise.cov_factor / noise.cov_filter state the law):
         the device noise of one step is drawn with the full covariance Sigma [nu, nu] (float32: symmetric bit for bit,

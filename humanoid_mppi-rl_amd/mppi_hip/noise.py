@@ -8,6 +8,9 @@ this restatement is float64 (the reference for tests, and the filter of MPPIMode
 The knot law (mppi_set_noise_knots; csrc/noise_knots.h) draws the row at P knots and interpolates it to the H steps:
 knot_table and knot_filter restate it in float32, operation by operation, bitwise what the device draws.
 
+The horizon basis (mppi_set_noise_basis; csrc/noise_basis.h) applies a dense M [H, R] along the horizon to R white
+normals: basis_filter restates it bitwise, colored_basis builds the table of iCEM's power-law noise.
+
 The cross-actuator covariance (mppi_set_noise_cov; csrc/noise_cov.h) mixes the unit-variance rows of the actuators with
 the Cholesky factor of a full Sigma: cov_factor, cov_mix and cov_filter restate it the same way, bitwise.
 """
@@ -135,6 +138,73 @@ def knot_filter(z, P: int, order: int, rho: float = 0.0, sigma_u=None) -> np.nda
     for i in (1, 2, 3):
         e = _fma32(w[:, i][:, None], kn[..., idx[:, i], :], e)
     return (s[:, None, None] * e).astype(np.float32)
+
+
+# ---- the horizon basis (include/mppi.h mppi_set_noise_basis; csrc/noise_basis.h), restated bit for bit
+
+def basis_filter(z, M, sigma_u=None) -> np.ndarray:
+    """The basis law over given standard normals z [..., nu, H, K] (float32 result of the same shape): only
+    z[..., :R, :] is read, as the R white normals of M [H, R].  float32 with every fmaf of csrc/noise_basis.h emulated
+    (correctly rounded): bitwise what the device draws (Engine.noise_eval) from the same normals.
+
+        e[t] = M[t][0] z[0];   e[t] = fmaf(M[t][r], z[r], e[t]), r = 1 .. R-1 ascending;   eps = sigma_u[u] e[t]
+
+    sigma_u: scalar or [nu] (None = 1)."""
+    z = np.asarray(z, np.float32)
+    M = np.asarray(M, np.float32)
+    if z.ndim < 3:
+        raise ValueError("basis_filter: z must be [..., nu, H, K]")
+    nu, H = z.shape[-3], z.shape[-2]
+    if M.ndim != 2 or M.shape[0] != H or not 1 <= M.shape[1] <= H:
+        raise ValueError(f"basis_filter: M must be [H = {H}, R] with 1 <= R <= H, got {list(M.shape)}")
+    s = np.ones(nu, np.float32) if sigma_u is None else np.asarray(sigma_u, np.float32).ravel()
+    if s.size == 1:
+        s = np.full(nu, s[0], np.float32)
+    if s.shape != (nu,):
+        raise ValueError(f"basis_filter: sigma_u must have {nu} entries, got {s.size}")
+    e = M[:, 0][:, None] * z[..., 0:1, :]
+    for r in range(1, M.shape[1]):
+        e = _fma32(M[:, r][:, None], z[..., r:r + 1, :], e)
+    return (s[:, None, None] * e).astype(np.float32)
+
+
+def colored_basis(H: int, beta: float, n_basis: int | None = None, dtype=np.float32) -> np.ndarray:
+    """The table M [H, R] of coloured (power-law) noise along the horizon, S(f) ~ f^-beta (iCEM): a real Fourier basis
+    whose column pair of frequency j carries the amplitude s_j = j^(-beta / 2).  Computed in float64 and rounded to
+    float32 once (dtype=np.float64 returns it unrounded).
+
+    Columns in the order DC, cos 1, sin 1, cos 2, sin 2, ..., and for even H a last Nyquist column:
+        M[t][0] = g sqrt(2) s_1        M[t][2j-1] = 2 g s_j cos(2 pi j t / H)        M[t][2j] = 2 g s_j sin(2 pi j t / H)
+        Nyquist: g sqrt(2) s_{H/2} (-1)^t
+    with g such that every row of the kept columns has unit 2-norm: sigma_u is the scale at every step.  M M^T is
+    circulant with eigenvalues lambda_j / lambda_1 = j^-beta (lambda_0 = lambda_1); beta = 0 gives M M^T = I.
+    n_basis keeps the first columns (a low-pass law); it must be odd or H, so that the pairs stay whole and the variance
+    stays constant in t."""
+    H = int(H)
+    beta = float(beta)
+    if H < 1 or not np.isfinite(beta):
+        raise ValueError("colored_basis: need H >= 1 and a finite beta")
+    R = H if n_basis is None else int(n_basis)
+    if not 1 <= R <= H or (R != H and R % 2 == 0):
+        raise ValueError("colored_basis: n_basis must be in 1..H and odd or equal to H")
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("colored_basis: dtype must be float32 or float64")
+    if H == 1:
+        return np.ones((1, 1), dtype)
+    t = np.arange(H, dtype=np.int64)
+    M = np.zeros((H, H), np.float64)
+    s = lambda j: float(j) ** (-0.5 * beta)
+    M[:, 0] = np.sqrt(2.0) * s(1)
+    for j in range(1, (H - 1) // 2 + 1):
+        a = 2.0 * np.pi * ((j * t) % H).astype(np.float64) / H  # (the angle reduced in integers)
+        M[:, 2 * j - 1] = 2.0 * s(j) * np.cos(a)
+        M[:, 2 * j] = 2.0 * s(j) * np.sin(a)
+    if H % 2 == 0:
+        M[:, H - 1] = np.sqrt(2.0) * s(H // 2) * np.where(t % 2 == 0, 1.0, -1.0)
+    M = M[:, :R]
+    g = 1.0 / np.sqrt(np.sum(M[0] * M[0]))  # (constant in t: whole pairs)
+    return (g * M).astype(dtype)
 
 
 # ---- the cross-actuator covariance (include/mppi.h mppi_set_noise_cov; csrc/noise_cov.h), restated bit for bit

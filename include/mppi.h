@@ -115,7 +115,13 @@ extern "C" {
  *      Additive, version unchanged: mppi_set_noise_cov_adapt / mppi_get_noise_cov_adapt / mppi_get_noise_cov_law (the
  *      full sampling covariance adapted on the device from the cross moments); kernel name "cov_adapt".  BEHAVIOUR
  *      while it is on only: mppi_set_noise_cov(h, NULL) returns MPPI_E_STATE, mppi_set_noise_cov(h, Sigma) resets the
- *      device law even for the value last set, mppi_get_noise_cov / mppi_get_noise_model wait for the stream. */
+ *      device law even for the value last set, mppi_get_noise_cov / mppi_get_noise_model wait for the stream.
+ *      Additive, version unchanged: mppi_set_noise_basis / mppi_get_noise_basis (a dense horizon basis M [H][R] over R
+ *      white normals per sample: coloured noise, temporal kernels, spline and cosine bases, mixed on the device).  A
+ *      handle that never enables it launches exactly the kernels it launched before, with the same grids.  BEHAVIOUR
+ *      while a basis is on only: mppi_set_noise_model(NULL, 0) returns MPPI_E_STATE; mppi_set_noise_model(., rho != 0),
+ *      mppi_set_noise_knots(n_knots > 0), mppi_set_noise_cov(Sigma), mppi_set_noise_cov_adapt(rate > 0),
+ *      mppi_set_noise_adapt(rate > 0) and mppi_set_control_cost(gamma > 0) return MPPI_E_UNSUPPORTED. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -399,6 +405,40 @@ int mppi_set_noise_knots(mppi_handle* h, int n_knots, int order);
 int mppi_get_noise_knots(mppi_handle* h, int* n_knots, int* order, int32_t* idx /* [H][4] or NULL */,
                          float* w /* [H][4] or NULL */);
 int mppi_noise_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out /* [B][nu][H][K] host */);
+
+/* Horizon-basis sampling noise: the DEVICE noise of one (b, u, k) is a dense matrix M [H][R] (fp32, row-major, R =
+ * n_basis) applied along the horizon to R independent standard normals -- iCEM's coloured noise (a power-law spectrum:
+ * mppi_hip.noise.colored_basis), a squared-exponential temporal kernel, a B-spline or a truncated cosine basis --
+ * generated on the device in every stream form.  The third horizon law beside AR(1) and the knots; the rule is
+ * csrc/noise_basis.h, its numpy restatement mppi_hip.noise.basis_filter (bitwise).
+ *   Normals: z[r], r < R, are the standard normals of the default law at Philox counter (k/4, r, u, b) -- t replaced by
+ *   the basis index, under the key the solve draws anyway.  They are white: no AR(1) over them.
+ *   Noise, fp32 in this order:  e[t] = M[t][0] z[0];  e[t] = fmaf(M[t][r], z[r], e[t]), r = 1 .. R-1 ascending;
+ *   eps[b][u][t][k] = sigma_u[u] e[t].  The pad lanes K..Kp are written like every other lane.
+ * The covariance along the horizon is sigma_u^2 M M^T; M = I (R = H) reproduces the handle's rho = 0 model value for
+ * value.  The dense noise [B][nu][H][Kp] is still written: everything behind the generator (control bounds, the rate
+ * term, elites, kept elites, the ESS target, MPPI_FLAG_STATS / MPPI_FLAG_CROSS, the env step, trajectory logging, the
+ * seed counter) works unchanged, mppi_noise_eval returns the noise under the basis law, the analytic cartpole leaves
+ * its fused generator as for any active model, and plain, host-pointer, ASYNC, chained, captured-graph and
+ * trajectory-logging streams give bit for bit what a loop of plain counter solves gives.
+ * mppi_set_noise_basis: 1 <= n_basis <= H with every entry of M finite enables; n_basis == 0 disables (M ignored);
+ * anything else, a NULL M with n_basis > 0 included, is MPPI_E_ARG and changes nothing.  n_basis > 128 is
+ * MPPI_E_UNSUPPORTED (128 is the largest horizon of the presets; it bounds the generators' registers and LDS).
+ * Enabling makes the noise model active as mppi_set_noise_knots does (an inactive one becomes sigma_u = cfg.sigma, rho = 0) and so needs nu <= 32
+ * (MPPI_E_UNSUPPORTED otherwise); the first enabling call allocates the table's device memory (nothing is allocated
+ * inside a solve).  Disabling leaves sigma_u as it stands; mppi_set_noise_model(NULL, 0) is refused with MPPI_E_STATE
+ * while a basis is on (disable it first); mppi_set_noise_model(sigma_u, 0) keeps it.  Any change drops a prefetched
+ * noise and destroys captured graphs exactly as mppi_set_noise_model does; the key sequence is unchanged.  Setting the
+ * table already in effect (bitwise) keeps both.
+ * Not together with rho != 0 (the basis is the horizon correlation), mppi_set_noise_knots (both are horizon laws),
+ * mppi_set_noise_cov and with it mppi_set_noise_cov_adapt (the Kronecker law is not built), mppi_set_noise_adapt (its
+ * moment estimates assume AR(1)) nor mppi_set_control_cost(gamma > 0) (it needs (M M^T)^-1, singular for n_basis < H;
+ * n_basis == H is not special-cased): either order of each pair returns MPPI_E_UNSUPPORTED, changes nothing and names
+ * both setters in mppi_last_error.
+ * mppi_get_noise_basis: *n_basis (0 while off) and the table M [H][n_basis] as set, bitwise (written only while a law
+ * is on); each pointer may be NULL. */
+int mppi_set_noise_basis(mppi_handle* h, int n_basis, const float* M /* [H][n_basis] host, or n_basis == 0: off */);
+int mppi_get_noise_basis(mppi_handle* h, int* n_basis, float* M /* [H][n_basis] or NULL */);
 
 /* Cross-actuator sampling covariance: the DEVICE noise of one (b, t, k) drawn with a full covariance Sigma [nu][nu]
  * across the actuators (the Sigma of information-theoretic MPPI, pytorch_mppi's noise_sigma) instead of one independent
