@@ -5,6 +5,8 @@
 // covariance across the actuators (mppi_set_noise_cov; noise_cov.h, noise_cov_kernel).
 // A third horizon law stands beside AR(1) and the knots: a dense basis (mppi_set_noise_basis; noise_basis.h,
 // noise_basis_mfma_kernel on the matrix cores up to H = 128, noise_basis_kernel beyond).
+// The AR(1) generators also run under a table of per-step scales (mppi_set_noise_steps; StepLaw,
+// noise_ar1_steps_kernel / noise_ar1_lds_steps_kernel).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -50,6 +52,28 @@ __device__ __forceinline__ void law_read(const DeviceLaw& m, int u, float& su, f
   rho = m.p[kLawRho];
   c = m.p[kLawC];
 }
+// A third form: the table of per-step scales of mppi_set_noise_steps, S [B][nu][H] in device memory (written by the
+// setter and, on a handle that refits it, by step_adapt_kernel: a launch of its own ahead of the generator on the same
+// stream, never during it), rho and c by value.  The scale of step t is S[(b*nu + u)*H + t]: b, u and t are uniform per
+// block, so it arrives as one scalar load through the constant address space.  For the two laws above law_scale is the
+// per-actuator su itself: their instantiations are instruction for instruction what they were.
+struct StepLaw {
+  const float* S;
+  float rho, c;
+};
+typedef const __attribute__((address_space(4))) float* step_scales;
+__device__ __forceinline__ void law_read(const StepLaw& m, int, float& su, float& rho, float& c) {
+  su = 0.0f;  // (not read: law_scale)
+  rho = m.rho;
+  c = m.c;
+}
+template <class Law>
+__device__ __forceinline__ float law_scale(const Law&, float su, int, int, int) {
+  return su;
+}
+__device__ __forceinline__ float law_scale(const StepLaw& m, float, int bu, int H, int t) {
+  return ((step_scales)m.S)[(long)bu * H + t];
+}
 
 template <class Law>
 __device__ __forceinline__ void noise_ar1_body(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
@@ -78,7 +102,8 @@ __device__ __forceinline__ void noise_ar1_body(float* __restrict__ noise, int nb
       if (t < H) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) e[i] = t == 0 ? z[j][i] : ar1_step(rho, c, e[i], z[j][i]);
-        const f4 v = {su * e[0], su * e[1], su * e[2], su * e[3]};
+        const float st = law_scale(m, su, bu, H, t);
+        const f4 v = {st * e[0], st * e[1], st * e[2], st * e[3]};
         __builtin_nontemporal_store(v, dst + (long)t * nq);
       }
     }
@@ -93,6 +118,11 @@ __global__ __launch_bounds__(256) void noise_ar1_kernel(float* __restrict__ nois
 __global__ __launch_bounds__(256) void noise_ar1_dev_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
                                                             uint64_t seed, const unsigned long long* seed_ctr,
                                                             DeviceLaw m) {
+  noise_ar1_body(noise, nbu, nu, H, Kp, seed, seed_ctr, m);
+}
+__global__ __launch_bounds__(256) void noise_ar1_steps_kernel(float* __restrict__ noise, int nbu, int nu, int H, int Kp,
+                                                              uint64_t seed, const unsigned long long* seed_ctr,
+                                                              StepLaw m) {
   noise_ar1_body(noise, nbu, nu, H, Kp, seed, seed_ctr, m);
 }
 
@@ -140,7 +170,7 @@ __device__ __forceinline__ void noise_ar1_lds_body(float* inno, float* __restric
   for (int t = 0; t < H; ++t) {
     const float v = inno[t * kAr1LdsK + threadIdx.x];
     e = t == 0 ? v : ar1_advance(rho, e, v);
-    __builtin_nontemporal_store(su * e, dst + (long)t * Kp);
+    __builtin_nontemporal_store(law_scale(m, su, bu, H, t) * e, dst + (long)t * Kp);
   }
 }
 
@@ -153,6 +183,12 @@ __global__ __launch_bounds__(256) void noise_ar1_lds_kernel(float* __restrict__ 
 __global__ __launch_bounds__(256) void noise_ar1_lds_dev_kernel(float* __restrict__ noise, int nbu, int nu, int H,
                                                                 int Kp, uint64_t seed,
                                                                 const unsigned long long* seed_ctr, DeviceLaw m) {
+  extern __shared__ __attribute__((aligned(16))) float inno[];  // [H][kAr1LdsK]
+  noise_ar1_lds_body(inno, noise, nbu, nu, H, Kp, seed, seed_ctr, m);
+}
+__global__ __launch_bounds__(256) void noise_ar1_lds_steps_kernel(float* __restrict__ noise, int nbu, int nu, int H,
+                                                                  int Kp, uint64_t seed,
+                                                                  const unsigned long long* seed_ctr, StepLaw m) {
   extern __shared__ __attribute__((aligned(16))) float inno[];  // [H][kAr1LdsK]
   noise_ar1_lds_body(inno, noise, nbu, nu, H, Kp, seed, seed_ctr, m);
 }
@@ -530,10 +566,12 @@ static int ar1_knob() {
 
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
                               const unsigned long long* seed_ctr, float sigma, const NoiseModel& model,
-                              hipStream_t stream, const float* d_law) {
+                              hipStream_t stream, const float* d_law, const float* d_steps) {
   if (!model.active) return launch_noise(noise, B, nu, H, Kp, seed, seed_ctr, sigma, stream);
   if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_model refuses such a handle)
   const int nbu = B * nu, nq = Kp / 4;
+  // a table of per-step scales (mppi_set_noise_steps refuses it beside every law below but sigma_u and rho)
+  if (d_steps && (d_law || model.n_basis > 0 || model.cov_L || model.n_knots > 0)) return hipErrorInvalidValue;
   if (model.n_basis > 0) {  // a horizon basis (mppi_set_noise_basis refuses it beside every other law but sigma_u)
     if (d_law || model.cov_L || model.n_knots > 0 || !model.basis_T || model.n_basis > H || model.n_basis > kMaxBasis)
       return hipErrorInvalidValue;
@@ -574,7 +612,10 @@ hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64
   const bool lds = H <= kAr1LdsMaxH && (knob == 2 || (knob == 0 && waves < 4L * current_device_cus()));
   if (lds) {
     const dim3 grid(Kp / kAr1LdsK, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
-    if (d_law)
+    if (d_steps)
+      hipLaunchKernelGGL(noise_ar1_lds_steps_kernel, grid, dim3(256), (size_t)H * kAr1LdsK * sizeof(float), stream,
+                         noise, nbu, nu, H, Kp, seed, seed_ctr, StepLaw{d_steps, model.rho, model.c});
+    else if (d_law)
       hipLaunchKernelGGL(noise_ar1_lds_dev_kernel, grid, dim3(256), (size_t)H * kAr1LdsK * sizeof(float), stream,
                          noise, nbu, nu, H, Kp, seed, seed_ctr, DeviceLaw{d_law});
     else
@@ -584,7 +625,10 @@ hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64
   }
   const int threads = nq >= 256 ? 256 : (nq + kWave - 1) / kWave * kWave;
   const dim3 grid((nq + threads - 1) / threads, nbu < 65535 ? nbu : 65535, (nbu + 65534) / 65535);
-  if (d_law)
+  if (d_steps)
+    hipLaunchKernelGGL(noise_ar1_steps_kernel, grid, dim3(threads), 0, stream, noise, nbu, nu, H, Kp, seed, seed_ctr,
+                       StepLaw{d_steps, model.rho, model.c});
+  else if (d_law)
     hipLaunchKernelGGL(noise_ar1_dev_kernel, grid, dim3(threads), 0, stream, noise, nbu, nu, H, Kp, seed, seed_ctr,
                        DeviceLaw{d_law});
   else

@@ -26,6 +26,7 @@
 #include "noise_basis.h"  // basis_law_valid
 #include "noise_knots.h"  // knot_table
 #include "noise_model.h"  // ar1_innovation_scale
+#include "step_law.h"  // StepAdapt
 
 namespace mppi {
 std::vector<unsigned char> build_fc_net(int kind, const void* blob, size_t nbytes, int precision, int nx, int nu,
@@ -65,10 +66,13 @@ enum KernelId {
   kKeep = 10,
   kCross = 11,
   kCovAdapt = 12,
-  kNumKernels = 13
+  kStepMom = 13,
+  kStepAdapt = 14,
+  kNumKernels = 15
 };
 const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost",
-                                         "bounds", "rate_cost", "elites", "keep", "cross", "cov_adapt"};
+                                         "bounds", "rate_cost", "elites", "keep", "cross", "cov_adapt", "step_mom",
+                                         "step_adapt"};
 
 struct PendingEvt {
   int id;
@@ -89,6 +93,8 @@ struct SolveOpts {
   bool rate = false;    // mppi_set_rate_cost
   bool elite = false;   // mppi_set_elites
   bool keep = false;    // mppi_set_elite_keep
+  bool step_mom = false;    // MPPI_FLAG_STEP_MOMENTS
+  bool step_adapt = false;  // mppi_set_noise_steps_adapt
 };
 
 }  // namespace
@@ -282,6 +288,24 @@ struct mppi_handle {
   float* d_keep_ecost = nullptr;     // [max_batch][Kp] (scratch: the selection's masked costs, never read)
   float* d_keep_U = nullptr;         // [max_batch][nu][H] the eval entries' U (the resident d_U stays as it is)
   int keep_B = 0;                    // slots 0..keep_B hold a set: stored by a solve or written by mppi_set_kept (0: none)
+  // the per-step sampling scale (mppi_set_noise_steps; kernels_noise.hip StepLaw).  While steps_on, d_steps is the scale
+  // of the law: S [max_batch][nu][H], one table per batch slot, allocated by the first enabling call, written by the
+  // setter on the stream and, while steps_adapt_on, by step_adapt_kernel; the AR(1) generators read it per step, and
+  // noise_model.sigma_u is the fill a step entering the horizon starts with.  steps_host: the table as last set, all
+  // max_batch slots (what "the table in effect" is compared with while the refit is off).
+  bool steps_on = false;
+  float* d_steps = nullptr;
+  std::vector<float> steps_host;
+  // the per-step moments (MPPI_FLAG_STEP_MOMENTS; step_moments.h, kernels_step_moments.hip), allocated by
+  // ensure_step_mom before the first flagged solve or capture, slot-major like the statistics: step_slots slots for
+  // solves and one more, the last, for mppi_step_moments_eval; m1 of every slot first, then m2
+  float* d_step_mom = nullptr;       // [2][step_slots + 1][max_batch][nu][H]
+  int step_slots = 0;
+  int stepm_B = 0, stepm_n = 0;      // batch and slot count of the last solve / graph launch with the flag (0: none ran)
+  // the refit (mppi_set_noise_steps_adapt; step_law.h, step_adapt_kernel).  While steps_adapt_on every solve carries
+  // MPPI_FLAG_STEP_MOMENTS and runs the kernel behind its per-step moments: it moves d_steps
+  bool steps_adapt_on = false;
+  StepAdapt steps_adapt{0.0f, 1e-3f, 10.0f, 1};
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -484,7 +508,7 @@ void mppi_destroy(mppi_handle* h) {
                   h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev,
                   h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
                   h->d_keep_idx, h->d_keep_count, h->d_keep_steps, h->d_keep_sel, h->d_keep_selcount, h->d_keep_tau,
-                  h->d_keep_ecost, h->d_keep_U};
+                  h->d_keep_ecost, h->d_keep_U, h->d_steps, h->d_step_mom};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -905,6 +929,44 @@ static int ensure_cov_hist(mppi_handle* h, int slots) {
   return MPPI_OK;
 }
 
+// The per-step moments' buffers for `slots` solve slots (+ 1 for mppi_step_moments_eval), beside the statistics' (whose
+// weights the pass reads: the caller runs ensure_stats first).  Growing them waits for the stream and forgets the
+// moments held so far.  Never called inside a capture.
+static size_t step_mom_slot_floats(const mppi_handle* h) { return (size_t)h->cfg.max_batch * h->cfg.nu * h->cfg.H; }
+static int ensure_step_mom(mppi_handle* h, int slots) {
+  if (slots <= h->step_slots) return MPPI_OK;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->d_step_mom) (void)hipFree(h->d_step_mom);
+  h->d_step_mom = nullptr;
+  h->step_slots = 0;
+  h->stepm_B = h->stepm_n = 0;
+  const size_t n = 2 * (size_t)(slots + 1) * step_mom_slot_floats(h) * 4;
+  HIP_TRY(hipMalloc(&h->d_step_mom, n));
+  HIP_TRY(hipMemsetAsync(h->d_step_mom, 0, n, h->stream));  // in stream order, ahead of the kernels that write slots
+  h->step_slots = slots;
+  return MPPI_OK;
+}
+static float* step_m1(const mppi_handle* h, int slot) { return h->d_step_mom + (size_t)slot * step_mom_slot_floats(h); }
+static float* step_m2(const mppi_handle* h, int slot) { return step_m1(h, h->step_slots + 1 + slot); }
+
+// The per-step moments of B solves from noise [B][nu][H][Kp] into output slot `slot`, behind enqueue_stats of the same
+// solves (d_stats_w holds their weights).
+static hipError_t enqueue_step_mom(mppi_handle* h, int B, const float* noise, int slot) {
+  const mppi_config& c = h->cfg;
+  const StepMomArgs sa{B, c.nu, c.H, h->Kp, h->d_stats_w, noise, step_m1(h, slot), step_m2(h, slot)};
+  return launch_step_moments(sa, h->stream);
+}
+
+// Behind the per-step moments of slot `slot`: every solve's rows of the table refit from its own moments and, with
+// shift, moved along the horizon with the nominal (the fill: the model's sigma_u).
+static hipError_t enqueue_step_adapt(mppi_handle* h, int B, int slot, bool shift) {
+  const mppi_config& c = h->cfg;
+  StepFill fill;
+  std::memcpy(fill.sigma_u, h->noise_model.sigma_u, sizeof(fill.sigma_u));
+  return launch_step_adapt(h->d_steps, step_m1(h, slot), step_m2(h, slot), h->d_stats + (size_t)slot * c.max_batch, B,
+                           c.nu, c.H, shift ? 1 : 0, h->steps_adapt, fill, h->stream);
+}
+
 // the device covariance of an adapting handle (d_cov_law: the rejects counter, Sigma, sigma_u; d_cov: L, Sinv)
 static CovLaw cov_law(const mppi_handle* h) {
   const size_t nu = (size_t)h->cfg.nu;
@@ -943,6 +1005,8 @@ static float* lambda_slot(const mppi_handle* h, int slot) {
 
 // the generators' law argument: the device law of an adapting handle, else nullptr (the by-value model)
 static const float* gen_law(const mppi_handle* h) { return h->adapt_on ? h->d_law : nullptr; }
+// ... and their table argument: the per-step scales of mppi_set_noise_steps, else nullptr
+static const float* gen_steps(const mppi_handle* h) { return h->steps_on ? h->d_steps : nullptr; }
 
 // Behind the statistics of slot `slot`: record the law the solve drew from, move the device law one step.
 static hipError_t enqueue_adapt(mppi_handle* h, int B, int slot) {
@@ -1170,6 +1234,8 @@ static SolveOpts solve_opts(const mppi_handle* h, int flags) {
   o.rate = h->rate_on;
   o.elite = h->elite_n > 0;
   o.keep = h->keep_n > 0;
+  o.step_mom = (flags & MPPI_FLAG_STEP_MOMENTS) != 0;
+  o.step_adapt = h->steps_adapt_on;
   return o;
 }
 
@@ -1196,6 +1262,10 @@ static void note_ran(mppi_handle* h, const SolveOpts& o, int B, int n) {
   if (o.rate) h->rate_B = B;
   if (o.elite) h->elite_B = B;
   if (o.keep && B > h->keep_B) h->keep_B = B;  // (slots beyond B keep the set they hold)
+  if (o.step_mom) {
+    h->stepm_B = B;
+    h->stepm_n = n;
+  }
 }
 
 // Enqueue one solve on the handle's stream: inputs, noise, rollout, reduce (+ update, shift), env step, outputs.
@@ -1225,7 +1295,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   a.shift_fill = c.shift_fill;
   a.terminal_weight = c.terminal_weight;
   a.update_mode = c.update_mode;
-  a.flags = flags & ~(MPPI_FLAG_STATS | MPPI_FLAG_CROSS);  // (host-side only: the kernels see the arguments of a solve without it)
+  a.flags = flags & ~(MPPI_FLAG_STATS | MPPI_FLAG_CROSS | MPPI_FLAG_STEP_MOMENTS);  // (host-side only: the kernels see the arguments of a solve without it)
   a.cost_kind = h->cost_kind;
   std::memcpy(a.ctx_default, h->cost_params, sizeof(a.ctx_default));
   a.noise = ns ? ns->cur : h->d_noise;
@@ -1293,7 +1363,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     if (!tmp.empty()) HIP_TRY(hipStreamSynchronize(s));
   } else if (!ns) {
     HIP_TRY(timed(h, kNoise, [&] {
-      return launch_noise_model(a.noise, B, nu, H, Kp, seed, a.seed_ctr, c.sigma, h->noise_model, s, gen_law(h));
+      return launch_noise_model(a.noise, B, nu, H, Kp, seed, a.seed_ctr, c.sigma, h->noise_model, s, gen_law(h),
+                                gen_steps(h));
     }));
   }
 
@@ -1397,10 +1468,19 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // behind the cross moments and, like the law's kernel above, ahead of the launch that draws the next solve's noise
   // from L; this solve's control-cost term (far above) has read the Sinv its own noise was drawn under
   if (o.cov_adapt) HIP_TRY(timed(h, kCovAdapt, [&] { return enqueue_cov_adapt(h, B, stats_slot); }));
+  // the per-step moments (MPPI_FLAG_STEP_MOMENTS; every such solve carries MPPI_FLAG_STATS): one more pass over a.noise
+  // behind the statistics, whose weights it reads, and like them ahead of everything that may write a.noise
+  if (o.step_mom) HIP_TRY(timed(h, kStepMom, [&] { return enqueue_step_mom(h, B, a.noise, stats_slot); }));
+  // the refit of the per-step scales (mppi_set_noise_steps_adapt; every such solve carries the flag): directly behind
+  // the moments and, like the laws' kernels above, ahead of the launch that draws the next solve's noise from the table
+  if (o.step_adapt)
+    HIP_TRY(timed(h, kStepAdapt, [&] {
+      return enqueue_step_adapt(h, B, stats_slot, (flags & MPPI_FLAG_SHIFT) != 0);
+    }));
   if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
     HIP_TRY(timed(h, kNoise, [&] {
       return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s,
-                                gen_law(h));
+                                gen_law(h), gen_steps(h));
     }));
     HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, s));
   }
@@ -1488,7 +1568,7 @@ static int prime_prefetch(mppi_handle* h, int B, uint64_t seed) {
   if (h->prefetch_valid) return MPPI_OK;
   const mppi_config& c = h->cfg;
   HIP_TRY(launch_noise_model(h->graph_parity ? h->d_noise2 : h->d_noise, B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr,
-                             c.sigma, h->noise_model, h->stream, gen_law(h)));
+                             c.sigma, h->noise_model, h->stream, gen_law(h), gen_steps(h)));
   HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->stream));
   h->prefetch_valid = true;
   h->prefetch_B = B;
@@ -1529,7 +1609,7 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   MPPI_TRY(ensure_stream_buffers(h));
   // (an adapting handle ignores the overlap arm, as a capture does: it would draw the next noise ahead of this
   // solve's update of the law)
-  const bool overlap = gen_overlap() && !h->capturing && !h->adapt_on && !h->cov_adapt_on;
+  const bool overlap = gen_overlap() && !h->capturing && !h->adapt_on && !h->cov_adapt_on && !h->steps_adapt_on;
   if (!overlap) HIP_TRY(wait_gen(h));  // leaving overlap mode: the solve stream behind the last generator launch
   MPPI_TRY(prime_prefetch(h, B, seed));
   float* buf[2] = {h->d_noise, h->d_noise2};
@@ -1551,7 +1631,7 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   HIP_TRY(hipEventRecord(h->ev_red, h->stream));  // = the previous reduce (everything enqueued so far)
   HIP_TRY(hipStreamWaitEvent(h->gstream, h->ev_red, 0));
   HIP_TRY(launch_noise_model(buf[h->graph_parity ^ 1], B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr, c.sigma,
-                             h->noise_model, h->gstream));
+                             h->noise_model, h->gstream, nullptr, gen_steps(h)));
   HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->gstream));
   HIP_TRY(hipEventRecord(h->ev_gen, h->gstream));
   h->gen_pending = true;
@@ -1734,9 +1814,11 @@ int mppi_solve_ex(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int f
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;
   if (h->adapt_on) flags |= MPPI_FLAG_STATS;  // the adaptation reads the solve's moments
   if (h->cov_adapt_on) flags |= MPPI_FLAG_CROSS;  // the covariance's adaptation reads the solve's cross moments
-  if (flags & MPPI_FLAG_CROSS) flags |= MPPI_FLAG_STATS;  // the cross pass reads the statistics' weights
+  if (h->steps_adapt_on) flags |= MPPI_FLAG_STEP_MOMENTS;  // the table's refit reads the solve's per-step moments
+  if (flags & (MPPI_FLAG_CROSS | MPPI_FLAG_STEP_MOMENTS)) flags |= MPPI_FLAG_STATS;  // both read the statistics' weights
   if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, 1)) != MPPI_OK) return rc;
   if ((flags & MPPI_FLAG_CROSS) && (rc = ensure_cross(h, 1)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_STEP_MOMENTS) && (rc = ensure_step_mom(h, 1)) != MPPI_OK) return rc;
   if (h->cov_adapt_on && (rc = ensure_cov_hist(h, 1)) != MPPI_OK) return rc;
   if (h->ess_on && (rc = ensure_lambda(h, 1)) != MPPI_OK) return rc;
   if (flags & MPPI_FLAG_CHAIN) return chain_solve(h, B, io, seed, flags);
@@ -1765,7 +1847,8 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   if (rc != MPPI_OK) return rc;
   if (h->adapt_on) flags |= MPPI_FLAG_STATS;  // the adaptation reads solve i's moments out of slot i
   if (h->cov_adapt_on) flags |= MPPI_FLAG_CROSS;  // ... and the covariance's its cross moments
-  if (flags & MPPI_FLAG_CROSS) flags |= MPPI_FLAG_STATS;  // the cross pass reads the statistics' weights
+  if (h->steps_adapt_on) flags |= MPPI_FLAG_STEP_MOMENTS;  // ... and the table's refit its per-step moments
+  if (flags & (MPPI_FLAG_CROSS | MPPI_FLAG_STEP_MOMENTS)) flags |= MPPI_FLAG_STATS;  // both read the statistics' weights
   HIP_TRY(hipSetDevice(h->device));
   if ((rc = x3_probe(h, B, io, flags)) != MPPI_OK) return rc;  // before the capture: it synchronises the stream
   MPPI_TRY(drop_graphs(h, false));
@@ -1776,6 +1859,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   // the statistics' slots exist before the capture begins: solve i's launches carry slot i's pointers
   if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, n_solves)) != MPPI_OK) return rc;
   if ((flags & MPPI_FLAG_CROSS) && (rc = ensure_cross(h, n_solves)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_STEP_MOMENTS) && (rc = ensure_step_mom(h, n_solves)) != MPPI_OK) return rc;
   if (h->cov_adapt_on && (rc = ensure_cov_hist(h, n_solves)) != MPPI_OK) return rc;
   if (h->ess_on && (rc = ensure_lambda(h, n_solves)) != MPPI_OK) return rc;  // ... and the lambdas' slots
   float* buf[2] = {h->d_noise, h->d_noise2};
@@ -1881,6 +1965,9 @@ int mppi_set_noise_model(mppi_handle* h, const float* sigma_u, float rho) {
   if (rho != 0.0f && h->noise_model.n_basis > 0)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_model: rho != 0 not together with mppi_set_noise_basis (the basis "
                                     "is the horizon correlation)");
+  if (!active && h->steps_on)
+    return fail(MPPI_E_STATE, "mppi_set_noise_model: (NULL, 0) is the default path, which has no per-step scales: "
+                              "call mppi_set_noise_steps(h, 0, NULL) first");
   if (h->noise_model.cov_L && !active)
     return fail(MPPI_E_STATE, "mppi_set_noise_model: (NULL, 0) is the default path, which has no covariance: "
                               "call mppi_set_noise_cov(h, NULL) first");
@@ -1941,6 +2028,9 @@ int mppi_set_noise_adapt(mppi_handle* h, float rate, float sigma_min, float sigm
   if (on && h->noise_model.n_basis > 0)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: not together with mppi_set_noise_basis (the moment "
                                     "estimates of sigma_u and rho assume AR(1))");
+  if (on && h->steps_on)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_adapt: not together with mppi_set_noise_steps (the rule adapts one "
+                                    "sigma_u per actuator, which is not the scale under a per-step table)");
   if (!on && !h->adapt_on) {  // nothing to disable: only the limits are kept
     h->adapt = NoiseAdapt{0.0f, sigma_min, sigma_max, rho_max};
     return MPPI_OK;
@@ -2038,6 +2128,9 @@ int mppi_set_noise_knots(mppi_handle* h, int n_knots, int order) {
   if (on && m.n_basis > 0)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: not together with mppi_set_noise_basis (both are horizon "
                                     "laws)");
+  if (on && h->steps_on)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_knots: not together with mppi_set_noise_steps (the knot generator "
+                                    "reads no per-step scale)");
   HIP_TRY(hipSetDevice(h->device));
   const size_t n = (size_t)c.H * 4;
   if (on && !h->d_knots) HIP_TRY(hipMalloc(&h->d_knots, n * (sizeof(int32_t) + sizeof(float))));
@@ -2114,6 +2207,9 @@ int mppi_set_noise_basis(mppi_handle* h, int n_basis, const float* M) {
   if (on && h->ctrl_gamma > 0.0f)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: not together with mppi_set_control_cost (the term needs the "
                                     "inverse of M M^T, singular for n_basis < H)");
+  if (on && h->steps_on)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: not together with mppi_set_noise_steps (the basis generators "
+                                    "read no per-step scale)");
   if (on && m.active && m.rho != 0.0f)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_basis: not together with rho != 0 of mppi_set_noise_model (the "
                                     "basis is the horizon correlation)");
@@ -2284,6 +2380,9 @@ int mppi_set_noise_cov(mppi_handle* h, const float* Sigma) {
     if (m.n_basis > 0)
       return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov: not together with mppi_set_noise_basis (the basis generator "
                                       "does not mix the actuators)");
+    if (h->steps_on)
+      return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_cov: not together with mppi_set_noise_steps (the covariance "
+                                      "generator reads no per-step scale)");
     HIP_TRY(hipSetDevice(h->device));
     if (!h->d_cov) HIP_TRY(hipMalloc(&h->d_cov, ((size_t)c.nu * kMaxNu + nn) * sizeof(float)));
     if (!m.active) {  // the default law as an active model: rho = 0, the same normals
@@ -2335,6 +2434,118 @@ int mppi_get_noise_cov(mppi_handle* h, float* Sigma, float* L, float* Sinv, int*
   return MPPI_OK;
 }
 
+int mppi_set_noise_steps(mppi_handle* h, int B, const float* sigma) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_steps: null handle");
+  const mppi_config& c = h->cfg;
+  if (!sigma) {  // off: sigma_u and rho stay as they stand, the AR(1) generators again
+    if (!h->steps_on) return MPPI_OK;  // nothing to disable
+    if (h->steps_adapt_on)
+      return fail(MPPI_E_STATE, "mppi_set_noise_steps: the table is being refit: disable it first "
+                                "(mppi_set_noise_steps_adapt with rate 0)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(drop_prefetch(h));
+    MPPI_TRY(drop_graphs(h, true));
+    h->steps_on = false;
+    return MPPI_OK;
+  }
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_set_noise_steps: B out of range [1, max_batch]");
+  const size_t row = (size_t)c.nu * c.H;
+  for (size_t i = 0; i < (size_t)B * row; ++i)
+    if (!(std::isfinite(sigma[i]) && sigma[i] >= 0.0f))
+      return fail(MPPI_E_ARG, "mppi_set_noise_steps: sigma[" + std::to_string(i) + "] must be finite and >= 0");
+  if (c.nu > kMaxNu)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_steps: a table of per-step scales is an active noise model (nu <= 32)");
+  NoiseModel m = h->noise_model;
+  if (m.n_knots > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_steps: not together with mppi_set_noise_knots (the knot generator "
+                                    "reads no per-step scale)");
+  if (m.n_basis > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_steps: not together with mppi_set_noise_basis (the basis generators "
+                                    "read no per-step scale)");
+  if (m.cov_L)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_steps: not together with mppi_set_noise_cov / "
+                                    "mppi_set_noise_cov_adapt (the covariance generator reads no per-step scale)");
+  if (h->adapt_on)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_steps: not together with mppi_set_noise_adapt (the rule adapts one "
+                                    "sigma_u per actuator, which is not the scale under a per-step table)");
+  if (h->ctrl_gamma > 0.0f)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_noise_steps: not together with mppi_set_control_cost (under AR(1) the term "
+                                    "needs D^-1 P D^-1 per cell of the table, which is not built)");
+  // every slot of the handle: slot b takes row b mod B (B = 1 broadcasts one table)
+  std::vector<float> host((size_t)c.max_batch * row);
+  for (int b = 0; b < c.max_batch; ++b) std::memcpy(host.data() + (size_t)b * row, sigma + (size_t)(b % B) * row, row * 4);
+  // the table in effect, bitwise: prefetch and graphs stay (a refitting handle's table has moved: it is set again below)
+  if (h->steps_on && !h->steps_adapt_on && std::memcmp(host.data(), h->steps_host.data(), host.size() * 4) == 0)
+    return MPPI_OK;
+  HIP_TRY(hipSetDevice(h->device));
+  if (!h->d_steps) HIP_TRY(hipMalloc(&h->d_steps, at_least16(host.size() * 4)));
+  // stale state, as in mppi_set_noise_model: the prefetched noise (the counter steps back: the key sequence is
+  // unchanged) and the captured graphs, whose generators are those of the other law
+  HIP_TRY(drop_prefetch(h));
+  MPPI_TRY(drop_graphs(h, true));
+  // on the handle's stream, behind every launch that reads the table (the generator stream included: drop_prefetch made
+  // the stream wait for it); the source stays alive in the handle
+  h->steps_host.swap(host);
+  HIP_TRY(hipMemcpyAsync(h->d_steps, h->steps_host.data(), h->steps_host.size() * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));  // (the next call may replace steps_host)
+  if (!m.active) {  // the default law as an active model: value for value the same normals
+    m = NoiseModel{};
+    m.active = 1;
+    for (int u = 0; u < c.nu; ++u) m.sigma_u[u] = c.sigma;
+  }
+  h->noise_model = m;
+  h->steps_on = true;
+  return MPPI_OK;
+}
+
+int mppi_get_noise_steps(mppi_handle* h, int B, float* sigma, int* active) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_steps: null handle");
+  if (B < 1 || B > h->cfg.max_batch) return fail(MPPI_E_ARG, "mppi_get_noise_steps: B out of range [1, max_batch]");
+  if (active) *active = h->steps_on ? 1 : 0;
+  if (h->steps_on && sigma) {  // the live table: every enqueued solve's refit included (off: the array is left untouched)
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(sigma, h->d_steps, (size_t)B * h->cfg.nu * h->cfg.H * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  return MPPI_OK;
+}
+
+int mppi_set_noise_steps_adapt(mppi_handle* h, float rate, float sigma_min, float sigma_max, int centred) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_noise_steps_adapt: null handle");
+  if (!(rate >= 0.0f && rate <= 1.0f)) return fail(MPPI_E_ARG, "mppi_set_noise_steps_adapt: rate must be in [0, 1]");
+  if (!(sigma_min > 0.0f && sigma_min <= sigma_max && std::isfinite(sigma_max)))
+    return fail(MPPI_E_ARG, "mppi_set_noise_steps_adapt: need 0 < sigma_min <= sigma_max < inf");
+  if (centred != 0 && centred != 1) return fail(MPPI_E_ARG, "mppi_set_noise_steps_adapt: centred must be 0 or 1");
+  const bool on = rate > 0.0f;
+  if (on && !h->steps_on)
+    return fail(MPPI_E_STATE, "mppi_set_noise_steps_adapt: no table to refit: call mppi_set_noise_steps first");
+  if (!on && !h->steps_adapt_on) {  // nothing to disable: only the settings are kept
+    h->steps_adapt = StepAdapt{0.0f, sigma_min, sigma_max, centred};
+    return MPPI_OK;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state, as in mppi_set_noise_adapt: the prefetched noise (the counter steps back: the key sequence is
+  // unchanged) and the captured graphs, which hold the settings in their kernel arguments
+  HIP_TRY(drop_prefetch(h));
+  MPPI_TRY(drop_graphs(h, true));
+  if (!on) {  // the table stays as it stands on the device; the host's copy of "the table in effect" follows it
+    HIP_TRY(hipMemcpyAsync(h->steps_host.data(), h->d_steps, h->steps_host.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  h->steps_adapt_on = on;
+  h->steps_adapt = StepAdapt{rate, sigma_min, sigma_max, centred};
+  return MPPI_OK;
+}
+
+int mppi_get_noise_steps_adapt(mppi_handle* h, float* rate, float* sigma_min, float* sigma_max, int* centred) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_noise_steps_adapt: null handle");
+  if (rate) *rate = h->steps_adapt_on ? h->steps_adapt.rate : 0.0f;
+  if (sigma_min) *sigma_min = h->steps_adapt.sigma_min;
+  if (sigma_max) *sigma_max = h->steps_adapt.sigma_max;
+  if (centred) *centred = h->steps_adapt.centred;
+  return MPPI_OK;
+}
+
 int mppi_noise_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out) {
   if (!h || !noise_out) return fail(MPPI_E_ARG, "mppi_noise_eval: null argument");
   const mppi_config& c = h->cfg;
@@ -2345,7 +2556,8 @@ int mppi_noise_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out) {
   const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
   // the generator of a solve's a1 under the law in effect, key = seed (no counter); no projection, no injection
   HIP_TRY(timed(h, kNoise, [&] {
-    return launch_noise_model(h->d_noise, B, c.nu, c.H, h->Kp, seed, nullptr, c.sigma, h->noise_model, s, gen_law(h));
+    return launch_noise_model(h->d_noise, B, c.nu, c.H, h->Kp, seed, nullptr, c.sigma, h->noise_model, s, gen_law(h),
+                              gen_steps(h));
   }));
   HIP_TRY(hipMemcpy2DAsync(noise_out, K * 4, h->d_noise, Kp * 4, K * 4, rows, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -2420,6 +2632,9 @@ int mppi_set_control_cost(mppi_handle* h, float gamma) {
   if (gamma > 0.0f && h->noise_model.n_basis > 0)
     return fail(MPPI_E_UNSUPPORTED, "mppi_set_control_cost: not together with mppi_set_noise_basis (the term needs the "
                                     "inverse of M M^T, singular for n_basis < H)");
+  if (gamma > 0.0f && h->steps_on)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_set_control_cost: not together with mppi_set_noise_steps (under AR(1) the "
+                                    "term needs D^-1 P D^-1 per cell of the table, which is not built)");
   HIP_TRY(hipSetDevice(h->device));
   const mppi_config& c = h->cfg;
   if (gamma > 0.0f && !h->d_wcost) {  // all of the term's buffers, once, or none (every entry is written before it is read)
@@ -3018,6 +3233,45 @@ int mppi_cross_moments_eval(mppi_handle* h, int B, const float* costs, const flo
   HIP_TRY(hipMemcpy(mx, h->d_cross_mx + (size_t)h->cross_slots * c.max_batch * nn, (size_t)B * nn * 4,
                     hipMemcpyDeviceToHost));
   return MPPI_OK;
+}
+
+// slot `slot` of the per-step moments -> host (the stream is idle)
+static int copy_step_mom(mppi_handle* h, int B, int slot, float* m1, float* m2) {
+  const size_t n = (size_t)B * h->cfg.nu * h->cfg.H * 4;
+  if (m1) HIP_TRY(hipMemcpy(m1, step_m1(h, slot), n, hipMemcpyDeviceToHost));
+  if (m2) HIP_TRY(hipMemcpy(m2, step_m2(h, slot), n, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_get_step_moments(mppi_handle* h, int B, int step, float* m1, float* m2) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_step_moments: null handle");
+  if (h->stepm_n == 0)
+    return fail(MPPI_E_STATE, "mppi_get_step_moments: no solve with MPPI_FLAG_STEP_MOMENTS has run on the handle");
+  if (B < 1 || B > h->stepm_B)
+    return fail(MPPI_E_ARG, "mppi_get_step_moments: B beyond the batch of the last flagged solve");
+  if (step < 0 || step >= h->stepm_n)
+    return fail(MPPI_E_ARG, "mppi_get_step_moments: step beyond the solves of the last flagged solve or graph");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_step_mom(h, B, step, m1, m2);
+}
+
+int mppi_step_moments_eval(mppi_handle* h, int B, const float* costs, const float* noise, float* m1, float* m2) {
+  if (!h || !costs || !noise) return fail(MPPI_E_ARG, "mppi_step_moments_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_step_moments_eval: B out of range [1, max_batch]");
+  HIP_TRY(hipSetDevice(h->device));
+  MPPI_TRY(ensure_stats(h, 1));
+  MPPI_TRY(ensure_step_mom(h, 1));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  MPPI_TRY(stage_costs(h, costs, B));
+  MPPI_TRY(stage_noise(h, noise, (size_t)B * c.nu * c.H));
+  // the evaluations' own slots: the statistics and per-step moments of the last solve stay readable; never refits
+  HIP_TRY(timed(h, kStats, [&] { return enqueue_stats(h, B, h->d_costs, h->d_noise, h->stats_slots); }));
+  HIP_TRY(timed(h, kStepMom, [&] { return enqueue_step_mom(h, B, h->d_noise, h->step_slots); }));
+  HIP_TRY(hipStreamSynchronize(s));
+  return copy_step_mom(h, B, h->step_slots, m1, m2);
 }
 
 int mppi_solve(mppi_handle* h, int B, const float* x0, float* U, const float* noise, uint64_t seed, float* costs_out,

@@ -11,6 +11,7 @@
 struct NoiseAdapt;  // noise_adapt.h: the settings of mppi_set_noise_adapt
 struct EssTarget;   // ess_target.h: the settings of mppi_set_ess_target
 struct NoiseCovAdapt;  // noise_cov_adapt.h: the settings of mppi_set_noise_cov_adapt
+struct StepAdapt;      // step_law.h: the settings of mppi_set_noise_steps_adapt
 
 namespace mppi {
 
@@ -301,10 +302,13 @@ constexpr int basis_rows_padded(int R) { return (R + 3) / 4 * 4; }  // rows of b
 // noise_ar1_lds_kernel (grids too small to fill the chip), noise_knot_kernel (a knot law), noise_basis_kernel (a horizon
 // basis) or noise_cov_kernel (a cross-actuator covariance); kernels_noise.hip.  d_law (or nullptr): the device law of
 // a handle that adapts it on the stream (mppi_set_noise_adapt) -- the same generators reading sigma_u, rho and c from
-// device memory instead of the by-value model (noise_ar1_dev_kernel / noise_ar1_lds_dev_kernel)
+// device memory instead of the by-value model (noise_ar1_dev_kernel / noise_ar1_lds_dev_kernel).  d_steps (or nullptr):
+// the table of per-step scales S [B][nu][H] of mppi_set_noise_steps (device memory the setter owns, moved on the stream
+// by step_adapt_kernel) -- the same two generators reading their scale per step from it, rho and c from the model
+// (noise_ar1_steps_kernel / noise_ar1_lds_steps_kernel); never beside d_law, a knot law, a basis or a covariance
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
                               const unsigned long long* seed_ctr, float sigma, const NoiseModel& model,
-                              hipStream_t stream, const float* d_law = nullptr);
+                              hipStream_t stream, const float* d_law = nullptr, const float* d_steps = nullptr);
 // The device law [kLawFloats] = sigma_u[kMaxNu], rho, c: set from a by-value model on the stream, and moved one step
 // by the rule of noise_adapt.h from one statistics slot (stats [B], m2 / m11 [B][nu]) after the law the solve drew
 // from was recorded into hist[0..nu] (sigma_u, rho).  One wave each; capturable.
@@ -394,6 +398,24 @@ struct CrossArgs {
 };
 size_t cross_part_floats(int B, int nu, int H, int Kp);
 hipError_t launch_cross(const CrossArgs& a, hipStream_t stream);  // moment part, fixed-order finish
+// Weighted per-step moments (kernels_step_moments.hip; MPPI_FLAG_STEP_MOMENTS, mppi_step_moments_eval; the definition:
+// step_moments.h), by value like StatsArgs and behind its launches, whose weights they read.
+struct StepMomArgs {
+  int B, nu, H, Kp;
+  const float* w;      // [B][Kp] the normalised softmin weights stats_cost_kernel wrote (pads 0)
+  const float* noise;  // [B][nu][H][Kp]
+  float* m1;           // [B][nu][H] out
+  float* m2;           // [B][nu][H] out
+};
+hipError_t launch_step_moments(const StepMomArgs& a, hipStream_t stream);
+// The refit of the per-step scales (mppi_set_noise_steps_adapt; the rule: step_law.h): S [B][nu][H] in place from one
+// slot of statistics (stats [B]) and per-step moments (m1, m2 [B][nu][H]); shift: the row moves with the nominal and
+// its last cell becomes fill.sigma_u[u].  One wave per row; capturable; nu <= kMaxNu.
+struct StepFill {
+  float sigma_u[kMaxNu];
+};
+hipError_t launch_step_adapt(float* S, const float* m1, const float* m2, const mppi_solve_stats* stats, int B, int nu,
+                             int H, int shift, const StepAdapt& a, const StepFill& fill, hipStream_t stream);
 // kernels_lambda.hip: per solve b, lambda_out[b] = the lambda in [lambda_min, lambda_max] at which costs [B][Kp] give
 // the target effective sample size (the rule: ess_target.h); one block per solve, read-only on the costs, capturable
 hipError_t launch_lambda_search(const float* costs, int B, int K, int Kp, const EssTarget& s, float cfg_lambda,

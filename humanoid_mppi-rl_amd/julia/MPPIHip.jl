@@ -34,6 +34,7 @@ const COST = Dict(:cartpole => Cint(1), :cartpole_est => Cint(2), :humanoid_v3 =
 const FLAG_SHIFT, FLAG_COLMAJOR, FLAG_U0_BEFORE = Cint(0x1), Cint(0x2), Cint(0x10)
 const FLAG_STATS = Cint(0x200)   # also compute the solve's diagnostics (solve_stats)
 const FLAG_CROSS = Cint(0x400)   # ... and the weighted cross moments of its noise (cross_moments); implies FLAG_STATS
+const FLAG_STEP_MOMENTS = Cint(0x800)   # ... and the weighted per-step moments (step_moments); implies FLAG_STATS
 const CTX_MAX = 8
 
 # must match `mppi_io` in include/mppi.h (7 pointers)
@@ -324,6 +325,70 @@ function noise_basis(c::Controller)
     GC.@preserve A check(ccall((:mppi_get_noise_basis, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Float32}), c.handle, n,
                                pointer(A)))
     return permutedims(A)   # row-major C -> [t, r]
+end
+
+"""
+    set_noise_steps!(c, S)
+
+A sampling scale per actuator and horizon step (mppi_set_noise_steps): `eps[u, t, k] = S[u, t] * e[t]` with `e` the
+handle's unit-variance AR(1) row -- the distribution of CEM / iCEM.  `S` is nu x H, finite and >= 0; every batch slot of
+the handle takes it.  `nothing` disables and keeps sigma_u and rho.  While on, sigma_u is the scale a step entering the
+horizon starts with.  Not together with `set_noise_knots!`, `set_noise_basis!`, `set_noise_cov!`, `set_noise_adapt!`
+or `set_control_cost!`.
+"""
+function set_noise_steps!(c::Controller, S::Union{Nothing, AbstractMatrix})
+    if S === nothing
+        check(ccall((:mppi_set_noise_steps, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle, 0, C_NULL))
+        return c
+    end
+    size(S) == (c.cfg.nu, c.cfg.H) || throw(ArgumentError("S must be nu x H"))
+    A = Matrix{Float32}(permutedims(S))   # the C ABI's [nu][H] is row-major
+    GC.@preserve A check(ccall((:mppi_set_noise_steps, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle, 1,
+                               pointer(A)))
+    return c
+end
+
+"""
+    noise_steps(c) -> S::Matrix{Float32} or nothing
+
+The live table of the handle's per-step scales (mppi_get_noise_steps; waits for the stream), nu x H indexed [u, t];
+`nothing` while the law is off.
+"""
+function noise_steps(c::Controller)
+    active = Ref{Cint}(0)
+    A = zeros(Float32, c.cfg.H, c.cfg.nu)
+    GC.@preserve A check(ccall((:mppi_get_noise_steps, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Ref{Cint}),
+                               c.handle, 1, pointer(A), active))
+    return active[] == 0 ? nothing : permutedims(A)   # row-major C -> [u, t]
+end
+
+"""
+    set_noise_steps_adapt!(c, rate; sigma_min = 1f-3, sigma_max = 10f0, centred = true)
+
+Refit the table on the device behind every solve from the solve's own per-step moments and shift it with the nominal
+(mppi_set_noise_steps_adapt): CEM's variance update with momentum.  `rate` in (0, 1] enables (needs `set_noise_steps!`
+first), 0 disables and keeps the table as it stands.
+"""
+function set_noise_steps_adapt!(c::Controller, rate::Real; sigma_min::Real = 1f-3, sigma_max::Real = 10f0,
+                                centred::Bool = true)
+    check(ccall((:mppi_set_noise_steps_adapt, LIB), Cint, (Ptr{Cvoid}, Cfloat, Cfloat, Cfloat, Cint), c.handle,
+                Float32(rate), Float32(sigma_min), Float32(sigma_max), centred ? 1 : 0))
+    return c
+end
+
+"""
+    step_moments(c, step = 0) -> (m1, m2)
+
+The weighted per-step moments of the last solve made with FLAG_STEP_MOMENTS or with the refit on
+(mppi_get_step_moments): `sum_k w_k eps` and `sum_k w_k eps^2`, each nu x H indexed [u, t].
+"""
+function step_moments(c::Controller, step::Integer = 0)
+    m1 = zeros(Float32, c.cfg.H, c.cfg.nu)
+    m2 = zeros(Float32, c.cfg.H, c.cfg.nu)
+    GC.@preserve m1 m2 check(ccall((:mppi_get_step_moments, LIB), Cint,
+                                   (Ptr{Cvoid}, Cint, Cint, Ptr{Float32}, Ptr{Float32}), c.handle, 1, step,
+                                   pointer(m1), pointer(m2)))
+    return (permutedims(m1), permutedims(m2))
 end
 
 """

@@ -19,6 +19,7 @@ PREC_FP32, PREC_BF16, PREC_BF16X3 = 0, 1, 2  # BF16X3: fp32-accurate split bf16 
 FLAG_SHIFT, FLAG_COLMAJOR, FLAG_DEVICE, FLAG_ASYNC, FLAG_U0_BEFORE, FLAG_RESIDENT_U = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 FLAG_ENV_STEP, FLAG_SEED_COUNTER, FLAG_CHAIN, FLAG_STATS = 0x40, 0x80, 0x100, 0x200
 FLAG_CROSS = 0x400  # implies FLAG_STATS
+FLAG_STEP_MOMENTS = 0x800  # implies FLAG_STATS
 CTX_MAX = 8
 
 EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", "mppi_set_cost", "mppi_solve",
@@ -38,7 +39,8 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_set_elite_keep", "mppi_get_elite_keep", "mppi_get_kept", "mppi_set_kept", "mppi_keep_store_eval",
             "mppi_keep_inject_eval", "mppi_get_cross_moments", "mppi_cross_moments_eval",
             "mppi_set_noise_cov_adapt", "mppi_get_noise_cov_adapt", "mppi_get_noise_cov_law", "mppi_set_noise_basis",
-            "mppi_get_noise_basis"]
+            "mppi_get_noise_basis", "mppi_set_noise_steps", "mppi_get_noise_steps", "mppi_set_noise_steps_adapt",
+            "mppi_get_noise_steps_adapt", "mppi_get_step_moments", "mppi_step_moments_eval"]
 
 
 class MPPIError(RuntimeError):
@@ -167,6 +169,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_set_noise_cov_adapt": (i32, [vp, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
         "mppi_get_noise_cov_adapt": (i32, [vp, vp, vp, vp, vp]),
         "mppi_get_noise_cov_law": (i32, [vp, i32, vp]),
+        "mppi_set_noise_steps": (i32, [vp, i32, vp]),
+        "mppi_get_noise_steps": (i32, [vp, i32, vp, ctypes.POINTER(i32)]),
+        "mppi_set_noise_steps_adapt": (i32, [vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, i32]),
+        "mppi_get_noise_steps_adapt": (i32, [vp] + [ctypes.POINTER(ctypes.c_float)] * 3 + [ctypes.POINTER(i32)]),
+        "mppi_get_step_moments": (i32, [vp, i32, i32, vp, vp]),
+        "mppi_step_moments_eval": (i32, [vp, i32, vp, vp, vp, vp]),
         "mppi_kernel_clock_read": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_double)]),
     }

@@ -25,7 +25,7 @@ import numpy as np
 from . import _lib as L
 from .engine import Config, Engine
 from .nets import cross_attention_blob, feature_attention_blob, mlp_blob
-from .noise import ar1_filter, basis_filter, colored_basis, knot_filter
+from .noise import ar1_filter, basis_filter, colored_basis, knot_filter, steps_filter
 from .stats import adapt_noise_model
 
 # default cost of each preset (the reference script it mirrors)
@@ -62,6 +62,13 @@ class MPPIModel:
               (Engine.set_noise_basis) -- the table applied along the horizon to R white normals per sample, scaled by
               noise_sigma; ("colored", beta) is noise.colored_basis(H, beta), iCEM's power-law noise.  Both noise modes
               sample the same law.  Not together with noise_knots, noise_rho != 0, adapt_noise or control_cost.
+    noise_steps: None (default) or a table of sampling scales [nu, H] (Engine.set_noise_steps): one standard deviation
+              per actuator AND horizon step, CEM's distribution, over the AR(1) row of noise_rho; noise_sigma is then
+              the scale a step entering the horizon starts with.  Both noise modes sample the same law (the numpy mode
+              reads the engine's live table).  Not together with noise_knots, noise_basis, adapt_noise or control_cost.
+    adapt_steps: above 0 (needs noise_steps), the engine refits the table behind every solve from the solve's own
+              per-step moments, about the weighted mean, and shifts it with the nominal (Engine.set_noise_steps_adapt
+              with this rate and adapt_limits[:2] = (sigma_min, sigma_max)): with n_elite, CEM's variance update.
     adapt_noise: above 0, mppi_step / mppi_controller request the solve's statistics (Engine.solve(stats=True)) and
               after each step move the law towards the weighted moments of the noise that won
               (stats.adapt_noise_model with this rate and adapt_limits = (sigma_min, sigma_max, rho_max)), through
@@ -99,7 +106,7 @@ class MPPIModel:
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
                  lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, rate_cost=None,
                  rate_anchor: bool = True, n_elite: int = 0, n_keep: int = 0, noise_knots=None, noise_basis=None,
-                 **overrides):
+                 noise_steps=None, adapt_steps: float = 0.0, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -178,6 +185,19 @@ class MPPIModel:
                 raise ValueError("MPPIModel: noise_basis does not go together with noise_knots, noise_rho != 0, "
                                  "adapt_noise or control_cost")
             self.noise_basis = noise_basis
+        self.adapt_steps = float(adapt_steps)
+        if not 0.0 <= self.adapt_steps <= 1.0:
+            raise ValueError("MPPIModel: adapt_steps must be in [0, 1]")
+        self._steps_on = noise_steps is not None
+        if noise_steps is not None:
+            if noise_knots is not None or noise_basis is not None or self.adapt_noise > 0.0 or self.control_cost > 0.0:
+                raise ValueError("MPPIModel: noise_steps does not go together with noise_knots, noise_basis, "
+                                 "adapt_noise or control_cost")
+            self.engine.set_noise_steps(np.asarray(noise_steps, np.float32).reshape(self.config.nu, self.config.H))
+            if self.adapt_steps > 0.0:
+                self.engine.set_noise_steps_adapt(self.adapt_steps, self.adapt_limits[0], self.adapt_limits[1])
+        elif self.adapt_steps > 0.0:
+            raise ValueError("MPPIModel: adapt_steps needs noise_steps")
         if self.device_adapt:
             self.engine.set_noise_adapt(self.adapt_noise, *self.adapt_limits)
         if self.ess_target > 0.0:
@@ -294,6 +314,14 @@ class MPPIModel:
         self._noise_basis = M
 
     @property
+    def noise_steps(self):
+        """The engine's live table of per-step scales [nu, H] (Engine.noise_steps), or None while it is off."""
+        if not getattr(self, "_steps_on", False):
+            return None
+        S = self.engine.noise_steps(1)
+        return None if S is None else S[0]
+
+    @property
     def K(self):
         return self.config.K
 
@@ -305,6 +333,8 @@ class MPPIModel:
         c = self.config
         if self.noise == "numpy":
             z = np.random.randn(c.nu, c.H, c.K)
+            if self.noise_steps is not None:
+                return steps_filter(z, self.noise_steps, self.noise_rho)
             if self.noise_basis is not None:
                 return basis_filter(z, self.noise_basis,
                                     c.sigma if self.noise_sigma is None else self.noise_sigma).astype(np.float64)

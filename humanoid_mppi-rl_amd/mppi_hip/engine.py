@@ -244,6 +244,57 @@ class Engine:
         L.check(self.lib.mppi_get_noise_cov_law(self._h, step, _ptr(S)))
         return S
 
+    def set_noise_steps(self, sigma):
+        """A sampling scale per solve, actuator and horizon step (mppi_set_noise_steps; noise.steps_filter states the
+        law): eps[b, u, t, k] = sigma[b, u, t] * e[t] with e the handle's unit-variance AR(1) row -- the distribution
+        of CEM / iCEM.  sigma [B, nu, H] float32 (1 <= B <= max_batch; slot b takes row b mod B), or [nu, H], which
+        broadcasts one table to every solve; entries finite and >= 0.  None disables and keeps sigma_u and rho.  While
+        on, sigma_u of set_noise_model is the fill a step entering the horizon starts with.  Makes the noise model
+        active; a change destroys captured graphs, as set_noise_model does.  Not together with set_noise_knots,
+        set_noise_basis, set_noise_cov, set_noise_adapt or set_control_cost.  Needs nu <= 32."""
+        if sigma is None:
+            L.check(self.lib.mppi_set_noise_steps(self._h, 0, None))
+            return self
+        c = self.config
+        S = _f32(sigma)
+        if S.ndim == 2:
+            S = S[None]
+        if S.ndim != 3 or S.shape[1:] != (c.nu, c.H):
+            raise ValueError(f"set_noise_steps: sigma must be [B, {c.nu}, {c.H}] or [{c.nu}, {c.H}], "
+                             f"got {list(S.shape)}")
+        S = np.ascontiguousarray(S)
+        L.check(self.lib.mppi_set_noise_steps(self._h, int(S.shape[0]), _ptr(S)))
+        return self
+
+    def noise_steps(self, B: int = 1) -> np.ndarray | None:
+        """The live table [B, nu, H] float32 of the handle's per-step scales (mppi_get_noise_steps; waits for the
+        stream: with set_noise_steps_adapt on, after every enqueued solve's refit); None while off."""
+        c = self.config
+        S = np.zeros((int(B), c.nu, c.H), np.float32)
+        active = ctypes.c_int()
+        L.check(self.lib.mppi_get_noise_steps(self._h, int(B), _ptr(S), ctypes.byref(active)))
+        return S if active.value else None
+
+    def set_noise_steps_adapt(self, rate: float, sigma_min: float = 1e-3, sigma_max: float = 10.0,
+                              centred: bool = True):
+        """Refit the per-step scales on the device behind every solve, each solve's table from its own per-step
+        moments, and shift it along the horizon with the nominal (mppi_set_noise_steps_adapt; the rule is
+        stats.adapt_noise_steps_f32): CEM's variance update with momentum.  rate in (0, 1] enables (needs
+        set_noise_steps first), 0 disables and keeps the table as it stands.  centred: the variance about the weighted
+        mean (CEM; with set_elites, of the elites about their mean), else the moment about the nominal.  Chained
+        solves and graph streams refit step by step with no host round trip.  Destroys captured graphs, as
+        set_noise_adapt does."""
+        L.check(self.lib.mppi_set_noise_steps_adapt(self._h, float(rate), float(sigma_min), float(sigma_max),
+                                                    int(bool(centred))))
+        return self
+
+    def noise_steps_adapt(self) -> tuple[float, float, float, bool]:
+        """(rate, sigma_min, sigma_max, centred) of mppi_get_noise_steps_adapt; rate 0.0 while the refit is off."""
+        v = [ctypes.c_float() for _ in range(3)]
+        cen = ctypes.c_int()
+        L.check(self.lib.mppi_get_noise_steps_adapt(self._h, *(ctypes.byref(x) for x in v), ctypes.byref(cen)))
+        return float(v[0].value), float(v[1].value), float(v[2].value), bool(cen.value)
+
     def noise_eval(self, B: int, seed: int) -> np.ndarray:
         """The noise [B, nu, H, K] (float32) the handle's generator draws for the by-value key `seed` under the law in
         effect (mppi_noise_eval): a solve's noise for that key, ahead of bounds and kept elites.  Drops a prefetched
@@ -582,11 +633,14 @@ class Engine:
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,
-              raise_nonfinite: bool = False, stats: bool = False, cross: bool = False) -> SolveResult:
+              raise_nonfinite: bool = False, stats: bool = False, cross: bool = False,
+              step_moments: bool = False) -> SolveResult:
         """One batched solve. x0 [B,nx] (or [nx]); U [B,nu,H] (or [nu,H]); noise None (device Philox) or
         [B,nu,H,K] (or [nu,H,K]). Returns the updated (and optionally shifted) U plus diagnostics.
         stats: also compute the solve's statistics on the device (MPPI_FLAG_STATS) into SolveResult.stats.
-        cross: the statistics plus the weighted cross moments (MPPI_FLAG_CROSS): SolveResult.stats["eps_mx"] [B,nu,nu]."""
+        cross: the statistics plus the weighted cross moments (MPPI_FLAG_CROSS): SolveResult.stats["eps_mx"] [B,nu,nu].
+        step_moments: the statistics plus the weighted per-step moments (MPPI_FLAG_STEP_MOMENTS):
+        SolveResult.stats["step_m1"], ["step_m2"] [B,nu,H]."""
         c = self.config
         single = np.ndim(x0) == 1
         x0 = _f32(x0).reshape(-1, c.nx)
@@ -602,14 +656,18 @@ class Engine:
         u0 = np.empty((B, c.nu), np.float32)
         io = L.mppi_io(_ptr(x0), _ptr(Uo), _ptr(nz), _ptr(costs), _ptr(weights), _ptr(u0), _ptr(cx))
         flags = (L.FLAG_SHIFT if shift else 0) | (L.FLAG_U0_BEFORE if u0_before else 0) | (
-            L.FLAG_COLMAJOR if colmajor else 0) | (L.FLAG_STATS if stats else 0) | (L.FLAG_CROSS if cross else 0)
+            L.FLAG_COLMAJOR if colmajor else 0) | (L.FLAG_STATS if stats else 0) | (L.FLAG_CROSS if cross else 0) | (
+            L.FLAG_STEP_MOMENTS if step_moments else 0)
         rc = self.lib.mppi_solve_ex(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags)
         if rc != L.MPPI_E_NONFINITE or raise_nonfinite:
             L.check(rc)
         sq = (lambda a: a[0]) if single else (lambda a: a)
-        st = {k: sq(v) for k, v in self.stats(B).items()} if stats or cross else None
+        st = {k: sq(v) for k, v in self.stats(B).items()} if stats or cross or step_moments else None
         if cross:
             st["eps_mx"] = sq(self.cross_moments(B))
+        if step_moments:
+            m1, m2 = self.step_moments(B)
+            st["step_m1"], st["step_m2"] = sq(m1), sq(m2)
         return SolveResult(U=sq(Uo), costs=None if costs is None else sq(costs),
                            weights=None if weights is None else sq(weights), u0=sq(u0), status=rc, stats=st)
 
@@ -618,9 +676,11 @@ class Engine:
                      costs_ptr: int | None = None, u0_ptr: int | None = None, ctx_ptr: int | None = None,
                      weights_ptr: int | None = None, shift: bool = False, resident_U: bool = False,
                      asynchronous: bool = True, env_step: bool = False, seed_counter: bool = False,
-                     chain: bool = False, stats: bool = False, cross: bool = False) -> int:
+                     chain: bool = False, stats: bool = False, cross: bool = False,
+                     step_moments: bool = False) -> int:
         """stats: also compute the solve's statistics (MPPI_FLAG_STATS; read with Engine.stats);
         cross: the statistics plus the weighted cross moments (MPPI_FLAG_CROSS; read with Engine.cross_moments);
+        step_moments: the statistics plus the per-step moments (MPPI_FLAG_STEP_MOMENTS; read with Engine.step_moments);
         env_step: advance x0 in place by one dynamics step with u0 (MPPI_FLAG_ENV_STEP);
         seed_counter: noise key = seed + the handle's device counter (MPPI_FLAG_SEED_COUNTER);
         chain: a chained solve (MPPI_FLAG_CHAIN: the previous chained solve's reduce generated this one's noise;
@@ -628,7 +688,8 @@ class Engine:
         io = L.mppi_io(x0_ptr, U_ptr, noise_ptr, costs_ptr, weights_ptr, u0_ptr, ctx_ptr)
         flags = self._dev_flags(shift, resident_U, env_step) | (L.FLAG_ASYNC if asynchronous else 0) | (
             L.FLAG_SEED_COUNTER if seed_counter else 0) | (L.FLAG_CHAIN if chain else 0) | (
-            L.FLAG_STATS if stats else 0) | (L.FLAG_CROSS if cross else 0)
+            L.FLAG_STATS if stats else 0) | (L.FLAG_CROSS if cross else 0) | (
+            L.FLAG_STEP_MOMENTS if step_moments else 0)
         return L.check(self.lib.mppi_solve_ex(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags))
 
     @staticmethod
@@ -639,22 +700,24 @@ class Engine:
     # -- receding-horizon stream as one hipGraph (mppi_graph_capture / mppi_graph_launch)
     def graph_capture(self, B: int, n_solves: int, x0_ptr: int, U_ptr: int | None = None, u0_ptr: int | None = None,
                       ctx_ptr: int | None = None, costs_ptr: int | None = None, seed: int = 0, shift: bool = True,
-                      resident_U: bool = False, env_step: bool = True, stats: bool = False, cross: bool = False):
+                      resident_U: bool = False, env_step: bool = True, stats: bool = False, cross: bool = False,
+                      step_moments: bool = False):
         return self.graph_capture_traj(B, n_solves, x0_ptr, U_ptr, u0_ptr, ctx_ptr, costs_ptr, seed, shift,
-                                       resident_U, env_step, stats=stats, cross=cross)
+                                       resident_U, env_step, stats=stats, cross=cross, step_moments=step_moments)
 
     def graph_capture_traj(self, B: int, n_solves: int, x0_ptr: int, U_ptr: int | None = None,
                            u0_ptr: int | None = None, ctx_ptr: int | None = None, costs_ptr: int | None = None,
                            seed: int = 0, shift: bool = True, resident_U: bool = False, env_step: bool = True,
                            traj_x_ptr: int | None = None, traj_u_ptr: int | None = None, stats: bool = False,
-                           cross: bool = False):
+                           cross: bool = False, step_moments: bool = False):
         """Capture n_solves chained solves; with traj_*_ptr (device [n][B][nx] / [n][B][nu]) the env steps log
         the (state, control) trajectory.  stats: solve i also writes its statistics, Engine.stats(B, step=i); cross:
-        and its weighted cross moments, Engine.cross_moments(B, step=i)."""
+        and its weighted cross moments, Engine.cross_moments(B, step=i); step_moments: and its per-step moments,
+        Engine.step_moments(B, step=i)."""
         io = L.mppi_io(x0_ptr, U_ptr, None, costs_ptr, None, u0_ptr, ctx_ptr)
         self._graph_io = io  # the graph holds these device pointers
         flags = self._dev_flags(shift, resident_U, env_step) | (L.FLAG_STATS if stats else 0) | (
-            L.FLAG_CROSS if cross else 0)
+            L.FLAG_CROSS if cross else 0) | (L.FLAG_STEP_MOMENTS if step_moments else 0)
         L.check(self.lib.mppi_graph_capture_traj(self._h, B, ctypes.byref(io), ctypes.c_uint64(seed), flags,
                                                  n_solves, traj_x_ptr, traj_u_ptr))
         return self
@@ -723,6 +786,30 @@ class Engine:
         mx = np.zeros((B, c.nu, c.nu), np.float32)
         L.check(self.lib.mppi_cross_moments_eval(self._h, B, _ptr(costs), _ptr(nz), _ptr(mx)))
         return mx
+
+    # -- weighted per-step moments (MPPI_FLAG_STEP_MOMENTS; mppi_hip.stats.step_moments_ref states the definition)
+    def step_moments(self, B: int = 1, step: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """(m1, m2), each [B, nu, H] float32, of the last solve made with step_moments=True or with
+        set_noise_steps_adapt on (mppi_get_step_moments; waits for the stream): sum_k w_k eps and sum_k w_k eps^2 per
+        actuator and horizon step.  step as for Engine.stats."""
+        c = self.config
+        m1 = np.zeros((B, c.nu, c.H), np.float32)
+        m2 = np.zeros((B, c.nu, c.H), np.float32)
+        L.check(self.lib.mppi_get_step_moments(self._h, B, step, _ptr(m1), _ptr(m2)))
+        return m1, m2
+
+    def step_moments_eval(self, costs, noise) -> tuple[np.ndarray, np.ndarray]:
+        """The same kernels on host arrays (mppi_step_moments_eval): costs [B, K] (or [K]), noise [B, nu, H, K] ->
+        (m1, m2) [B, nu, H].  Uses the handle's lambda_ and norm_eps; no dynamics or cost need be loaded; touches no
+        solve state and never refits."""
+        c = self.config
+        costs = _f32(costs).reshape(-1, c.K)
+        B = costs.shape[0]
+        nz = _f32(noise).reshape(B, c.nu, c.H, c.K)
+        m1 = np.zeros((B, c.nu, c.H), np.float32)
+        m2 = np.zeros((B, c.nu, c.H), np.float32)
+        L.check(self.lib.mppi_step_moments_eval(self._h, B, _ptr(costs), _ptr(nz), _ptr(m1), _ptr(m2)))
+        return m1, m2
 
     def device_stats(self) -> dict:
         """Device pointers of the statistics' buffers (mppi_device_stats), slot-major with max_batch as the batch

@@ -13,6 +13,9 @@ normals: basis_filter restates it bitwise, colored_basis builds the table of iCE
 
 The cross-actuator covariance (mppi_set_noise_cov; csrc/noise_cov.h) mixes the unit-variance rows of the actuators with
 the Cholesky factor of a full Sigma: cov_factor, cov_mix and cov_filter restate it the same way, bitwise.
+
+The per-step scale (mppi_set_noise_steps) replaces sigma_u[u] by a table S[b][u][t]: steps_filter restates it, bitwise
+the device's on float32 normals and ar1_filter's own arithmetic otherwise.
 """
 from __future__ import annotations
 
@@ -205,6 +208,44 @@ def colored_basis(H: int, beta: float, n_basis: int | None = None, dtype=np.floa
     M = M[:, :R]
     g = 1.0 / np.sqrt(np.sum(M[0] * M[0]))  # (constant in t: whole pairs)
     return (g * M).astype(dtype)
+
+
+# ---- the per-step scale (include/mppi.h mppi_set_noise_steps), restated bit for bit
+
+def steps_filter(z, table, rho: float = 0.0) -> np.ndarray:
+    """The per-step law over standard normals z [..., nu, H, K]: eps[..., u, t, k] = table[..., u, t] * e[..., u, t, k]
+    with e the unit-variance AR(1) row of z.  table: [nu, H] (every leading index of z takes it) or [..., nu, H]
+    matching z's leading axes -- one table per solve.
+
+    The arithmetic follows z's dtype.  float32 z: the device's own operations -- ar1_filter_f32's recursion, then one
+    float32 product per element -- bitwise what the device draws (Engine.noise_eval) from the same normals; unit rows
+    taken from the device (noise_eval under sigma_u = 1) go through with rho = 0, which leaves them as they are.
+    Any other dtype: float64 in ar1_filter's own operations, so a table that is sigma_u broadcast along the horizon
+    gives ar1_filter(z, rho, sigma_u) bit for bit."""
+    z = np.asarray(z)
+    if z.ndim < 3:
+        raise ValueError("steps_filter: z must be [..., nu, H, K]")
+    rho = float(rho)
+    if not 0.0 <= rho < 1.0:
+        raise ValueError("steps_filter: rho must be in [0, 1)")
+    f32 = z.dtype == np.float32
+    S = np.asarray(table, np.float32 if f32 else np.float64)
+    nu, H = z.shape[-3], z.shape[-2]
+    if S.ndim < 2 or S.shape[-2:] != (nu, H) or (S.ndim > 2 and S.shape[:-2] != z.shape[:-3]):
+        raise ValueError(f"steps_filter: table must be [{nu}, {H}] or {list(z.shape[:-3])} + [{nu}, {H}], "
+                         f"got {list(S.shape)}")
+    if not (np.all(np.isfinite(S)) and np.all(S >= 0.0)):
+        raise ValueError("steps_filter: table entries must be finite and >= 0")
+    if f32:
+        e = ar1_filter_f32(z, rho) if rho != 0.0 else z
+        return (S[..., None] * e).astype(np.float32)
+    z = np.asarray(z, np.float64)
+    e = z.copy()
+    if rho != 0.0:
+        c = np.sqrt(1.0 - rho * rho)
+        for t in range(1, H):
+            e[..., t, :] = rho * e[..., t - 1, :] + c * z[..., t, :]
+    return S[..., None] * e
 
 
 # ---- the cross-actuator covariance (include/mppi.h mppi_set_noise_cov; csrc/noise_cov.h), restated bit for bit

@@ -69,6 +69,15 @@ equals the device bit for bit.
 The adapted covariance (mppi_set_noise_cov_adapt; csrc/noise_cov_adapt.h is the fp32 rule): Sigma moves towards the
 batch mean of eps_mx, its standard deviations are clipped with the correlations kept, and L and Sigma^-1 are factored
 again.  adapt_noise_cov is the float64 restatement, adapt_noise_cov_f32 the step as the device takes it, bit for bit.
+
+Weighted per-step moments (MPPI_FLAG_STEP_MOMENTS; csrc/step_moments.h is the fp32 definition):
+
+    m1[u, t] = sum_k w_k eps[u,t,k]          m2[u, t] = sum_k w_k eps[u,t,k]^2
+
+step_moments_ref is the float64 restatement, step_moments_f32 the device's own summation, bit for bit.  The refit of
+the per-step sampling scales (mppi_set_noise_steps_adapt; csrc/step_law.h is the fp32 rule) moves every solve's table
+towards its own moments, about the weighted mean or about zero, and shifts it with the nominal: adapt_noise_steps is
+the float64 restatement, adapt_noise_steps_f32 the step as the device takes it, bit for bit.
 """
 from __future__ import annotations
 
@@ -809,3 +818,144 @@ def adapt_noise_cov_f32(Sigma, eps_mx, rate, sigma_min=1e-3, sigma_max=10.0, n_f
     if np.all(np.isfinite(S2)):
         assert np.array_equal(L.view(np.uint32), cov_factor(S2).view(np.uint32))  # one factor, two statements
     return S2, L, Sinv, sig, 1
+
+
+# ---- weighted per-step moments (MPPI_FLAG_STEP_MOMENTS; csrc/step_moments.h) and the refit of the per-step scales
+# ---- (mppi_set_noise_steps_adapt; csrc/step_law.h)
+
+def step_moments_ref(costs, noise, lam: float = 1.0, norm_eps: float = 0.0, w=None):
+    """costs [B, K], noise [B, nu, H, K] -> (m1, m2), each [B, nu, H] in float64:
+    m1 = sum_k w_k eps, m2 = sum_k w_k eps^2 with the softmin weights of solve_stats_ref -- or with the given weights
+    w [B, K] (costs is then not read: pass None)."""
+    w = softmin_weights_ref(costs, lam, norm_eps) if w is None else np.asarray(w, np.float64)
+    w = w.reshape(-1, w.shape[-1])
+    e = np.asarray(noise, np.float64)
+    e = e.reshape(w.shape[0], -1, e.shape[-2], w.shape[1])
+    return np.einsum("bk,buhk->buh", w, e), np.einsum("bk,buhk->buh", w, e * e)
+
+
+def step_moments_f32(w, noise):
+    """w [B, K] float32 (the normalised weights, as the device holds them), noise [B, nu, H, K] float32 -> (m1, m2),
+    each [B, nu, H] float32, by the cell scheme of csrc/step_moments.h, operation by operation: per wave-chunk of 256 k
+    and lane the chains a1 = fmaf(w_i, e_i, a1) and p = w_i * e_i; a2 = fmaf(p, e_i, a2) over the lane's quad in the
+    order x, y, z, w, the wave's butterfly, then the chunks added in ascending order from 0.  Bitwise equal to the
+    device and to the header through g++."""
+    w = np.ascontiguousarray(w, np.float32)
+    e = np.ascontiguousarray(noise, np.float32)
+    B, K = w.shape
+    e = e.reshape(B, -1, e.shape[-2], K)
+    nu, H = e.shape[1], e.shape[2]
+    Kp = (K + 63) // 64 * 64
+    nq = Kp // 4
+    nwc = (nq + 63) // 64
+    # lanes beyond the row's last quad: weight 0 on the row's last quad (the device's clamp)
+    q = np.minimum(np.arange(nwc * 64), nq - 1)
+    act = np.arange(nwc * 64) < nq
+    wp = np.zeros((B, Kp), np.float32)
+    wp[:, :K] = w
+    ep = np.zeros((B, nu, H, Kp), np.float32)
+    ep[..., :K] = e
+    wl = np.where(act[None, :, None], wp.reshape(B, nq, 4)[:, q], np.float32(0.0))[:, None, None]  # [B, 1, 1, lanes, 4]
+    el = ep.reshape(B, nu, H, nq, 4)[:, :, :, q]                                                   # [B, nu, H, lanes, 4]
+    wl = np.broadcast_to(wl, el.shape)
+    a1 = np.zeros(el.shape[:-1], np.float32)
+    a2 = np.zeros(el.shape[:-1], np.float32)
+    with np.errstate(all="ignore"):
+        for i in range(4):
+            a1 = _fma32_vec(wl[..., i], el[..., i], a1)
+            p = wl[..., i] * el[..., i]
+            a2 = _fma32_vec(p, el[..., i], a2)
+        c1 = _wave_sum32(a1.reshape(B, nu, H, nwc, 64))
+        c2 = _wave_sum32(a2.reshape(B, nu, H, nwc, 64))
+        m1 = np.zeros((B, nu, H), np.float32)
+        m2 = np.zeros((B, nu, H), np.float32)
+        for wc in range(nwc):
+            m1 = m1 + c1[..., wc]
+            m2 = m2 + c2[..., wc]
+    return m1, m2
+
+
+def _check_steps_adapt(rate, sigma_min, sigma_max):
+    if not 0.0 <= float(rate) <= 1.0:
+        raise ValueError("adapt_noise_steps: rate must be in [0, 1]")
+    if not (0.0 < sigma_min <= sigma_max and np.isfinite(sigma_max)):
+        raise ValueError("adapt_noise_steps: need 0 < sigma_min <= sigma_max < inf")
+
+
+def _shift_steps(S, fill):
+    """The table moved one step along the horizon: S[..., t] <- S[..., t + 1], the last cell the per-actuator fill."""
+    out = np.empty_like(S)
+    out[..., :-1] = S[..., 1:]
+    out[..., -1] = np.broadcast_to(np.asarray(fill, S.dtype), S.shape[:-1])
+    return out
+
+
+def adapt_noise_steps(table, m1, m2, rate: float, sigma_min: float = 1e-3, sigma_max: float = 10.0,
+                      centred: bool = True, shift: bool = False, fill=None, n_finite=None) -> np.ndarray:
+    """One refit of the per-step scales in float64 (the rule of mppi_set_noise_steps_adapt): table, m1, m2 [B, nu, H]
+    (or [nu, H]) -> the new table.  Pure.  Per solve, no batch mean:
+
+        v  = m2 - m1^2 if centred else m2, clipped below at 0
+        S' = clip(sqrt((1 - rate) S^2 + rate v), sigma_min, sigma_max)
+        shift: S[t] <- S'[t + 1], S[H - 1] <- fill [nu] (a scalar: every actuator's; required with shift)
+
+    n_finite [B] (default: all finite): a solve with 0 is only shifted.  ValueError on bad settings or shapes."""
+    _check_steps_adapt(rate, sigma_min, sigma_max)
+    S = np.asarray(table, np.float64)
+    a, b = np.asarray(m1, np.float64), np.asarray(m2, np.float64)
+    if S.ndim not in (2, 3) or a.shape != S.shape or b.shape != S.shape:
+        raise ValueError("adapt_noise_steps: table, m1 and m2 must all be [B, nu, H] or [nu, H]")
+    single = S.ndim == 2
+    if single:
+        S, a, b = S[None], a[None], b[None]
+    if shift and fill is None:
+        raise ValueError("adapt_noise_steps: shift needs the fill (sigma_u)")
+    v = np.maximum(b - a * a if centred else b, 0.0)
+    new = np.clip(np.sqrt((1.0 - rate) * S * S + rate * v), sigma_min, sigma_max)
+    if n_finite is not None:
+        dead = np.asarray(n_finite).reshape(-1)[:S.shape[0]] == 0
+        new[dead] = S[dead]
+    if shift:
+        f = np.asarray(fill, np.float64)
+        new = _shift_steps(new, np.full(S.shape[1], float(f)) if f.ndim == 0 else f.reshape(1, -1))
+    return new[0] if single else new
+
+
+def adapt_noise_steps_f32(table, m1, m2, rate, sigma_min=1e-3, sigma_max=10.0, centred=True, shift=False, fill=None,
+                          n_finite=None) -> np.ndarray:
+    """The device's refit (csrc/step_law.h, mppi_set_noise_steps_adapt) restated in numpy float32, operation by
+    operation: table, m1, m2 [B, nu, H] float32, n_finite [B] or None, fill [nu] (or a scalar; read with shift only) ->
+    the table after one step, bitwise what step_adapt_kernel leaves.
+
+        n_finite[b] == 0: no cell of solve b is refit
+        v   = fmaf(-m1, m1, m2) if centred else m2;   a non-finite v leaves the cell;   v = v if v > 0 else 0
+        var = fmaf(rate, v, (1 - rate) * (S * S));    S' = min(max(sqrt(var), sigma_min), sigma_max)
+              (a non-finite var or root leaves the cell)
+        shift: S[t] <- S'[t + 1], S[H - 1] <- fill[u]
+
+    adapt_noise_steps is the same rule in float64 (it raises on invalid input, this one follows the kernel)."""
+    f = np.float32
+    S = np.array(table, np.float32, copy=True)
+    a, b = np.asarray(m1, np.float32), np.asarray(m2, np.float32)
+    single = S.ndim == 2
+    if single:
+        S, a, b = S[None], a[None], b[None]
+    rate, lo, hi = f(rate), f(sigma_min), f(sigma_max)
+    with np.errstate(all="ignore"):
+        v = _fma32_vec(-a, a, b) if centred else b.copy()
+        ok = np.isfinite(v)
+        v = np.where(v > 0.0, v, f(0.0)).astype(np.float32)
+        keep = f(f(1.0) - rate)
+        old = (keep * (S * S).astype(np.float32)).astype(np.float32)
+        var = _fma32_vec(np.full(S.shape, rate, np.float32), v, old)
+        r = np.sqrt(var, dtype=np.float32)
+        ok &= np.isfinite(var) & np.isfinite(r)
+        r = np.where(r < lo, lo, r)
+        r = np.where(r > hi, hi, r).astype(np.float32)
+    if n_finite is not None:
+        ok &= (np.asarray(n_finite).reshape(-1)[:S.shape[0]] != 0)[:, None, None]
+    new = np.where(ok, r, S).astype(np.float32)
+    if shift:
+        fl = np.asarray(fill, np.float32)
+        new = _shift_steps(new, np.full(S.shape[1], fl, np.float32) if fl.ndim == 0 else fl.reshape(1, -1))
+    return new[0] if single else new

@@ -121,7 +121,16 @@ extern "C" {
  *      handle that never enables it launches exactly the kernels it launched before, with the same grids.  BEHAVIOUR
  *      while a basis is on only: mppi_set_noise_model(NULL, 0) returns MPPI_E_STATE; mppi_set_noise_model(., rho != 0),
  *      mppi_set_noise_knots(n_knots > 0), mppi_set_noise_cov(Sigma), mppi_set_noise_cov_adapt(rate > 0),
- *      mppi_set_noise_adapt(rate > 0) and mppi_set_control_cost(gamma > 0) return MPPI_E_UNSUPPORTED. */
+ *      mppi_set_noise_adapt(rate > 0) and mppi_set_control_cost(gamma > 0) return MPPI_E_UNSUPPORTED.
+ *      Additive, version unchanged: mppi_set_noise_steps / mppi_get_noise_steps (a table of sampling scales per solve,
+ *      actuator and horizon step: CEM's distribution), MPPI_FLAG_STEP_MOMENTS, mppi_get_step_moments /
+ *      mppi_step_moments_eval (the weighted per-step moments of a solve's noise) and mppi_set_noise_steps_adapt /
+ *      mppi_get_noise_steps_adapt (the table refit per solve on the device, shifted with the nominal); kernel names
+ *      "step_mom" and "step_adapt".  A handle that never enables the table launches exactly the kernels it launched
+ *      before, with the same grids and arguments; a solve without the flag likewise.  BEHAVIOUR while the table is on
+ *      only: mppi_set_noise_model(NULL, 0) returns MPPI_E_STATE; mppi_set_noise_knots(n_knots > 0),
+ *      mppi_set_noise_basis(n_basis > 0), mppi_set_noise_cov(Sigma), mppi_set_noise_adapt(rate > 0) and
+ *      mppi_set_control_cost(gamma > 0) return MPPI_E_UNSUPPORTED. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -213,6 +222,10 @@ extern "C" {
                                        solve's noise (below), computed behind the statistics on the handle's stream;
                                        read with mppi_get_cross_moments.  Every solve form takes it; needs nu <= 32
                                        (MPPI_E_UNSUPPORTED otherwise).  Nothing else a solve returns changes by a bit */
+#define MPPI_FLAG_STEP_MOMENTS 0x800 /* MPPI_FLAG_STATS (implied) plus the weighted PER-STEP moments m1, m2 [nu][H] of
+                                       the solve's noise (below), one more pass over the noise behind the statistics;
+                                       read with mppi_get_step_moments.  Every solve form takes it.  Nothing else a
+                                       solve returns changes by a bit */
 
 #define MPPI_CTX_MAX 8 /* floats of per-solve cost context */
 
@@ -439,6 +452,59 @@ int mppi_noise_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out /* [B
  * is on); each pointer may be NULL. */
 int mppi_set_noise_basis(mppi_handle* h, int n_basis, const float* M /* [H][n_basis] host, or n_basis == 0: off */);
 int mppi_get_noise_basis(mppi_handle* h, int* n_basis, float* M /* [H][n_basis] or NULL */);
+
+/* A per-step sampling scale (mppi_set_noise_steps): the distribution of CEM-MPC, PETS, PlaNet and iCEM, which keep one
+ * standard deviation per action dimension AND per horizon step -- and, here, per solve of the batch.  A table
+ * S[b][u][t] in device memory replaces the per-actuator scale:
+ *     eps[b][u][t][k] = S[b][u][t] * e[t],   e the handle's unit-variance AR(1) row (mppi_set_noise_model: rho)
+ * over the same normals, Philox counters and keys; rho = 0 gives S times the normals themselves.  sigma_u is not
+ * multiplied in again while the table is on: it becomes the FILL, the scale a step that enters the horizon starts with
+ * (below).  A table whose every entry equals sigma_u[u] gives the AR(1) model's noise value for value.  The generators
+ * are the AR(1) model's two, reading their scale per step with one scalar load (noise_ar1_steps_kernel /
+ * noise_ar1_lds_steps_kernel; env MPPI_NOISE_AR1=direct|lds forces one as before); mppi_noise_eval returns the noise
+ * under the table.  mppi_hip.noise.steps_filter restates the law.
+ * mppi_set_noise_steps: sigma [B][nu][H] host fp32 with 1 <= B <= max_batch, every entry finite and >= 0, enables the
+ * law; every one of the max_batch slots is written, slot b taking row b mod B (B = 1 broadcasts one table).  sigma ==
+ * NULL disables it and leaves sigma_u and rho as they stand (MPPI_E_STATE while the refit below is on: disable that
+ * first).  Anything else is MPPI_E_ARG and changes nothing.  Needs nu <= 32 (MPPI_E_UNSUPPORTED).  Makes the noise
+ * model active, as mppi_set_noise_knots does.  The first enabling call allocates the table (max_batch * nu * H floats),
+ * nothing is allocated inside a solve; the table is uploaded on the handle's stream.  A change drops a prefetched
+ * noise and destroys captured graphs exactly as mppi_set_noise_model does, the key sequence is unchanged; setting the
+ * table already in effect (bitwise, with the refit off) changes nothing and keeps them.
+ * While the table is on: mppi_set_noise_model(NULL, 0) returns MPPI_E_STATE; mppi_set_noise_model(sigma_u, rho) keeps
+ * the table and sets the fill and rho.  Not together with mppi_set_noise_knots, mppi_set_noise_basis,
+ * mppi_set_noise_cov (and with it mppi_set_noise_cov_adapt), mppi_set_noise_adapt (one law per handle, where this is
+ * one per solve) nor mppi_set_control_cost(gamma > 0) (under AR(1) the term needs D^-1 P D^-1 per cell, which is not
+ * built): either order of every pair returns MPPI_E_UNSUPPORTED, changes nothing and names both setters in
+ * mppi_last_error.
+ * mppi_get_noise_steps: *active (0 / 1) and, while on, the LIVE table of slots 0..B (waits for the stream: every
+ * enqueued solve's refit included); sigma is written only while on; either pointer may be NULL.
+ *
+ * The refit (mppi_set_noise_steps_adapt): while on, every solve of every stream form behaves as if
+ * MPPI_FLAG_STEP_MOMENTS were set and runs one more small kernel directly behind its per-step moments (below), ahead
+ * of the launch that draws the next solve's noise.  Per solve b -- no batch mean: every solve owns its table -- and
+ * per cell (the fp32 rule is csrc/step_law.h, its numpy restatement mppi_hip.stats.adapt_noise_steps_f32):
+ *   n_finite[b] == 0: no cell of solve b is refit (the shift still applies)
+ *   v  = centred ? fmaf(-m1, m1, m2) : m2;   a non-finite v leaves the cell as it was;   v = max(v, 0)
+ *   S' = clamp(sqrtf(fmaf(rate, v, (1 - rate) * S^2)), sigma_min, sigma_max)
+ * and, if the solve carries MPPI_FLAG_SHIFT, the refitted row moves with the nominal: S[b][u][t] <- S'[b][u][t+1],
+ * S[b][u][H-1] <- sigma_u[u], the fill (H == 1: the one cell becomes the fill).  centred = 1 is CEM's variance of the
+ * elites about their mean (with mppi_set_elites the weights are zero off the elite set); centred = 0 takes the moment
+ * about the nominal, as mppi_set_noise_adapt does.  Slots >= B are untouched.
+ * Plain solves with host or device pointers, MPPI_FLAG_ASYNC, chained solves, captured graphs and trajectory logging
+ * all give bit for bit what a loop of plain solves gives; MPPI_GEN_OVERLAP=1 is ignored while it is on.  A stream
+ * resumes bit for bit on a fresh handle from the table (mppi_get_noise_steps), U, the seed counter, and u_prev / the
+ * kept set where used.
+ * mppi_set_noise_steps_adapt: rate in (0, 1] enables, rate == 0 disables and keeps the table as it stands;
+ * 0 < sigma_min <= sigma_max < inf; centred 0 or 1; anything else is MPPI_E_ARG and changes nothing.  Enabling needs
+ * the table on (MPPI_E_STATE otherwise).  Enabling, disabling and changing the settings drop a prefetched noise and
+ * destroy captured graphs, as mppi_set_noise_adapt does; the key sequence is unchanged.  While it is on,
+ * mppi_set_noise_steps(h, B, sigma) sets the table again even for the value last set.
+ * mppi_get_noise_steps_adapt: rate (0 while off), the limits and centred.  Kernel name "step_adapt". */
+int mppi_set_noise_steps(mppi_handle* h, int B, const float* sigma /* [B][nu][H] host, or NULL: off */);
+int mppi_get_noise_steps(mppi_handle* h, int B, float* sigma /* [B][nu][H] or NULL */, int* active);
+int mppi_set_noise_steps_adapt(mppi_handle* h, float rate, float sigma_min, float sigma_max, int centred);
+int mppi_get_noise_steps_adapt(mppi_handle* h, float* rate, float* sigma_min, float* sigma_max, int* centred);
 
 /* Cross-actuator sampling covariance: the DEVICE noise of one (b, t, k) drawn with a full covariance Sigma [nu][nu]
  * across the actuators (the Sigma of information-theoretic MPPI, pytorch_mppi's noise_sigma) instead of one independent
@@ -862,6 +928,26 @@ int mppi_stats_eval(mppi_handle* h, int B, const float* costs, const float* nois
 int mppi_get_cross_moments(mppi_handle* h, int B, int step, float* mx /* [B][nu][nu] */);
 int mppi_cross_moments_eval(mppi_handle* h, int B, const float* costs, const float* noise, float* mx /* [B][nu][nu] */);
 
+/* Weighted per-step moments (MPPI_FLAG_STEP_MOMENTS): the first and second moment of the noise the solve used, per
+ * actuator AND per horizon step, weighted with the statistics' w,
+ *     m1[b][u][t] = sum_k w_k eps[b][u][t][k]          m2[b][u][t] = sum_k w_k eps[b][u][t][k]^2
+ * -- under mppi_set_elites the weights are zero off the elite set, so m1 is the elite mean and m2 - m1^2 the elite
+ * variance: what CEM's refit of a per-step scale (mppi_set_noise_steps_adapt) is driven by.  One more streaming pass
+ * over the solve's noise behind the statistics and, like them, ahead of everything that may write that noise; it
+ * works with any noise (injected, projected by the bounds, with kept elites injected: the moments describe what the
+ * rollout saw).  The sums are fp32 in a cell order fixed by (H, Kp) alone (csrc/step_moments.h states it: per lane an
+ * fma chain over its four k, one butterfly across the 64 lanes of a 256-k chunk, the chunks in ascending order;
+ * mppi_hip.stats.step_moments_f32 is the numpy restatement, bitwise equal).  No nu limit.  Storage is per statistics
+ * slot, [B][nu][H] twice, grown with the slots and never inside a solve.
+ * mppi_get_step_moments: m1, m2 [B][nu][H] (either may be NULL); waits for the stream; step as for mppi_get_stats.
+ * MPPI_E_STATE if no solve with the flag has run on the handle.
+ * mppi_step_moments_eval: the same kernels on host arrays, costs [B][K] and noise [B][nu][H][K], behind the
+ * statistics' cost pass with cfg.lambda.  Needs only mppi_create; touches no solve state and never refits.  Like
+ * mppi_stats_eval it goes through the staging buffers (a prefetched noise is dropped, key sequence unchanged) and
+ * leaves the last solve's statistics and moments readable.  Kernel name "step_mom". */
+int mppi_get_step_moments(mppi_handle* h, int B, int step, float* m1, float* m2 /* each [B][nu][H] or NULL */);
+int mppi_step_moments_eval(mppi_handle* h, int B, const float* costs, const float* noise, float* m1, float* m2);
+
 /* MPPI_PREC_BF16X3 with a CrossAttention net: *products = the products layer 1 runs with (2 or 3; 0 = not a split CA
  * handle, or no solve yet), *probe_rel_err = the probe's max relative cost difference between the two forms (-1: no
  * probe ran: forced by env, or H > 64).  Either pointer may be NULL. */
@@ -894,7 +980,8 @@ int mppi_sync(mppi_handle* h);
  * "rate_cost" (the term launches of mppi_set_rate_cost and the store of u_prev, counted as one per solve), "elites"
  * (the selection of mppi_set_elites), "keep" (the inject, selection and gather launches of mppi_set_elite_keep, counted
  * as one per solve), "cross" (the two launches of MPPI_FLAG_CROSS), "cov_adapt" (the update kernel of
- * mppi_set_noise_cov_adapt). */
+ * mppi_set_noise_cov_adapt), "step_mom" (the pass of MPPI_FLAG_STEP_MOMENTS), "step_adapt" (the refit kernel of
+ * mppi_set_noise_steps_adapt). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
