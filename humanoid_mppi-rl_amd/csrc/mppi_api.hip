@@ -68,11 +68,12 @@ enum KernelId {
   kCovAdapt = 12,
   kStepMom = 13,
   kStepAdapt = 14,
-  kNumKernels = 15
+  kIter = 15,
+  kNumKernels = 16
 };
 const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost",
                                          "bounds", "rate_cost", "elites", "keep", "cross", "cov_adapt", "step_mom",
-                                         "step_adapt"};
+                                         "step_adapt", "iter"};
 
 struct PendingEvt {
   int id;
@@ -95,6 +96,7 @@ struct SolveOpts {
   bool keep = false;    // mppi_set_elite_keep
   bool step_mom = false;    // MPPI_FLAG_STEP_MOMENTS
   bool step_adapt = false;  // mppi_set_noise_steps_adapt
+  bool iter = false;        // mppi_set_iterations: the best sample of the step is tracked
 };
 
 }  // namespace
@@ -306,6 +308,21 @@ struct mppi_handle {
   // MPPI_FLAG_STEP_MOMENTS and runs the kernel behind its per-step moments: it moves d_steps
   bool steps_adapt_on = false;
   StepAdapt steps_adapt{0.0f, 1e-3f, 10.0f, 1};
+  // inner iterations per control step (mppi_set_iterations; iter_best.h, kernels_iter.hip).  A control step is iter_n
+  // calls of enqueue_solve on the same x0 and ctx: all but the last without MPPI_FLAG_SHIFT and MPPI_FLAG_ENV_STEP, each
+  // with its own noise key and per-step slot.  While iter_on() every iteration runs iter_best_kernel behind the cost
+  // terms and the selections; the step's last iteration also runs iter_mean_kernel ahead of its rollout (iter_mean) and
+  // iter_apply_kernel behind its update (iter_best).  The stored best persists per batch slot b; the buffers are
+  // allocated by mppi_set_iterations or mppi_iter_best_eval, two slots each: slot 0 the handle's, slot 1 the eval's.
+  int iter_n = 1;
+  int iter_best = 0, iter_mean = 0;  // return_best, add_mean
+  float* d_best_v = nullptr;         // [2][max_batch][nu][H]
+  float* d_best_cost = nullptr;      // [2][max_batch]
+  int32_t* d_best_k = nullptr;       // [2][max_batch]
+  int32_t* d_best_iter = nullptr;    // [2][max_batch]
+  float* d_best_U = nullptr;         // [max_batch][nu][H] mppi_iter_best_eval's U (the resident d_U stays as it is)
+  int best_B = 0;                    // batch of the last tracking solve / graph launch (0: none ran)
+  bool iter_on() const { return iter_n > 1 || iter_best || iter_mean; }
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -508,7 +525,8 @@ void mppi_destroy(mppi_handle* h) {
                   h->d_bpart, h->d_bounds_U, h->d_rate_wcost, h->d_rate_term, h->d_rate_part, h->d_rate_U, h->d_uprev,
                   h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
                   h->d_keep_idx, h->d_keep_count, h->d_keep_steps, h->d_keep_sel, h->d_keep_selcount, h->d_keep_tau,
-                  h->d_keep_ecost, h->d_keep_U, h->d_steps, h->d_step_mom};
+                  h->d_keep_ecost, h->d_keep_U, h->d_steps, h->d_step_mom, h->d_best_v, h->d_best_cost, h->d_best_k,
+                  h->d_best_iter, h->d_best_U};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -1193,6 +1211,13 @@ static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if ((h->dyn_kind == MPPI_DYN_MLP || h->dyn_kind == MPPI_DYN_CROSS_ATTN) && h->net.arch != kArchGeneric &&
       (c.nx > kMaxNx || c.nu > kMaxNu))
     return fail(MPPI_E_UNSUPPORTED, "learned dynamics: nx <= 64, nu <= 32");
+  if (io->noise && h->iter_n > 1)
+    return fail(MPPI_E_ARG, "mppi_solve: injected noise with mppi_set_iterations n_iter > 1 (one array cannot serve "
+                            "every iteration)");
+  if ((flags & MPPI_FLAG_U0_BEFORE) && h->iter_n > 1)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_solve: MPPI_FLAG_U0_BEFORE with mppi_set_iterations n_iter > 1");
+  if ((flags & MPPI_FLAG_U0_BEFORE) && h->iter_best)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_solve: MPPI_FLAG_U0_BEFORE with mppi_set_iterations return_best");
   return MPPI_OK;
 }
 
@@ -1236,12 +1261,13 @@ static SolveOpts solve_opts(const mppi_handle* h, int flags) {
   o.keep = h->keep_n > 0;
   o.step_mom = (flags & MPPI_FLAG_STEP_MOMENTS) != 0;
   o.step_adapt = h->steps_adapt_on;
+  o.iter = h->iter_on();
   return o;
 }
 
-// n solves of batch B with these options were enqueued (a plain or chained solve: n = 1, slot 0; a graph launch: its
-// solves, solve i in slot i): what the getters may read from now on.  The options without per-step slots keep the
-// chain's last solve.
+// n solves of batch B with these options were enqueued (a plain or chained solve: its n_iter iterations, slots 0..; a
+// graph launch: its solves' iterations, iteration it of solve i in slot i n_iter + it): what the getters may read from
+// now on.  The options without per-step slots keep the chain's last solve.
 static void note_ran(mppi_handle* h, const SolveOpts& o, int B, int n) {
   if (o.stats) {
     h->stats_B = B;
@@ -1266,12 +1292,25 @@ static void note_ran(mppi_handle* h, const SolveOpts& o, int B, int n) {
     h->stepm_B = B;
     h->stepm_n = n;
   }
+  if (o.iter) h->best_B = B;
+}
+
+// One iteration of a control step (mppi_set_iterations): its index and the step's count.  The first iteration stages the
+// step's inputs and the last copies its outputs; with host pointers the iterations between run on the staged copies
+// (d_x0, d_ctx, d_U), which hold bit for bit what a host round trip would bring back.
+struct IterStep {
+  int it, n;
+};
+// the flags iteration `it` of n carries: all but the last neither shift nor step the environment
+static int iter_flags(int flags, int it, int n) {
+  return it + 1 < n ? flags & ~(MPPI_FLAG_SHIFT | MPPI_FLAG_ENV_STEP) : flags;
 }
 
 // Enqueue one solve on the handle's stream: inputs, noise, rollout, reduce (+ update, shift), env step, outputs.
 // Synchronises only for host-side column-major staging. Capturable into a hipGraph in device mode.
 static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int flags, float* rec_x = nullptr,
-                         float* rec_u = nullptr, const NoiseStep* ns = nullptr, int stats_slot = 0) {
+                         float* rec_u = nullptr, const NoiseStep* ns = nullptr, int stats_slot = 0,
+                         const IterStep* is = nullptr) {
   const mppi_config& c = h->cfg;
   const bool dev = (flags & MPPI_FLAG_DEVICE) != 0;
   const bool resident = (flags & MPPI_FLAG_RESIDENT_U) != 0;
@@ -1279,6 +1318,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   hipStream_t s = h->stream;
   const int nx = c.nx, nu = c.nu, H = c.H, K = c.K, Kp = h->Kp;
   const size_t rowsU = (size_t)B * nu * H;
+  const int it = is ? is->it : 0;
+  const bool first = it == 0, last = !is || is->it + 1 == is->n;  // of the control step's iterations
 
   SolveArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1314,7 +1355,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // o.ctrl: the softmin weighs d_wcost = costs + term; o.rate: d_rate_wcost = (costs [+ control term]) + rate term;
   // o.elite: d_elite_wcost, the chain's end on the elite set (below)
   const SolveOpts o = solve_opts(h, flags);
-  const bool cart_unfused = (lam || o.ctrl || o.rate || o.elite || o.keep) && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  const bool cart_unfused = (lam || o.ctrl || o.rate || o.elite || o.keep || o.iter) && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  int iter_count = 1;  // "iter" is counted once per iteration, by the first of its launches
   // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths); the cartpole's unfused
   // rollout carries no stamp
   a.kclock = (h->kclock && a.seed_ctr && !cart_unfused) ? h->d_kclock : nullptr;
@@ -1329,12 +1371,13 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     a.U = resident ? h->d_U : io->U;
     a.Umirror = (resident && io->U) ? io->U : nullptr;  // written by the update kernels themselves
   } else {
-    HIP_TRY(hipMemcpyAsync(h->d_x0, io->x0, (size_t)B * nx * 4, hipMemcpyHostToDevice, s));
+    if (first) HIP_TRY(hipMemcpyAsync(h->d_x0, io->x0, (size_t)B * nx * 4, hipMemcpyHostToDevice, s));
     a.x0 = h->d_x0;
-    if (io->ctx) HIP_TRY(hipMemcpyAsync(h->d_ctx, io->ctx, (size_t)B * MPPI_CTX_MAX * 4, hipMemcpyHostToDevice, s));
+    if (io->ctx && first)
+      HIP_TRY(hipMemcpyAsync(h->d_ctx, io->ctx, (size_t)B * MPPI_CTX_MAX * 4, hipMemcpyHostToDevice, s));
     a.ctx = io->ctx ? h->d_ctx : nullptr;
     a.U = h->d_U;
-    if (!resident) {
+    if (!resident && first) {
       const float* src = io->U;
       if (colmajor) {  // Julia U (nu,H) column-major -> [nu][H]
         h->staging.resize(rowsU);
@@ -1377,6 +1420,16 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // for every solve of a handle with the feature on and changes nothing while the set is empty
   if (o.keep) HIP_TRY(timed(h, kKeep, [&] { return launch_keep_inject(keep_args(h, B, a.U, a.noise, 0), s); }));
 
+  // add_mean (mppi_set_iterations), the step's last iteration: the column behind the carried set zeroed, so the nominal
+  // itself is one of the candidates -- behind the injection (which never writes that column) and ahead of the bounds
+  // projection and the rollout.  The kept set's count is read on the device, as the injection reads it
+  if (o.iter && h->iter_mean && last) {
+    HIP_TRY(timed(h, kIter, [&] {
+      return launch_iter_mean(a.noise, o.keep ? h->d_keep_count : nullptr, h->keep_n, B, nu, H, K, Kp, s);
+    }, iter_count));
+    iter_count = 0;
+  }
+
   // per-actuator bounds: the solve's noise -- drawn above, prefetched by the previous solve's generator, or the copy of
   // an injected io.noise (never the caller's array) -- projected in place against the nominal U, ahead of the rollout
   // and of every other reader of this solve's noise
@@ -1415,6 +1468,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       HIP_TRY(timed(h, kRate, [&] { return enqueue_rate(h, B, a.U, a.noise, h->d_uprev, wcost, 0); }));
       wcost = h->d_rate_wcost;
     }
+    const float* const sel_cost = wcost;  // the unmasked end of the chain: what the selections and the tracking read
     if (o.elite) {
       // elite truncation, behind the terms (it selects on what the softmin would otherwise weigh) and ahead of the lambda
       // search: the search, the reduce and the statistics see the cost on the elite set and +inf elsewhere
@@ -1433,12 +1487,26 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       }, 0));
       if (o.elite) wcost = h->d_elite_wcost;
     }
+    if (o.iter) {
+      // the best sample of the step so far (mppi_set_iterations), on the unmasked chain like the keep store and at the
+      // same place: a.U is still the nominal the rollout perturbed, a.noise what the rollout saw
+      IterBestArgs ia{B, nu, H, K, Kp, first ? 1 : 0, it, c.ctrl_clamp, sel_cost, a.noise, a.U,
+                      h->d_best_v, h->d_best_cost, h->d_best_k, h->d_best_iter};
+      HIP_TRY(timed(h, kIter, [&] { return launch_iter_best(ia, s); }, iter_count));
+      iter_count = 0;
+    }
     if (lam)
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
     SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
     r.costs = wcost;
     HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s); }));
   }
+  // return_best (mppi_set_iterations), the step's last iteration: u0 becomes the first control of the step's best sample
+  // -- behind the update and shift (U, the nominal that warm-starts the next step, is untouched), ahead of the clip (so
+  // lo <= u0 <= hi still holds exactly), of the u_prev store, the trajectory record and the env step.  A step without
+  // a finite sample keeps the update's u0
+  if (o.iter && h->iter_best && last)
+    HIP_TRY(timed(h, kIter, [&] { return launch_iter_apply(h->d_best_v, h->d_best_k, a.u0, B, nu, H, s); }, iter_count));
   // per-actuator bounds: behind the update and shift (the cartpole's fused epilogue included), ahead of the env step,
   // the trajectory record and the output copies, U, its mirror and u0 are clipped: this removes the last rounding of
   // U + sum w (v - U), brings a shift-filled last column into a box that excludes zero, and makes lo <= U, u0 <= hi
@@ -1509,7 +1577,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     HIP_TRY(launch_rollout(h, e, s));
   }
 
-  // ---- outputs
+  // ---- outputs (the step's last iteration's)
+  if (!last) return MPPI_OK;
   const hipMemcpyKind d2x = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (io->costs)
     HIP_TRY(hipMemcpy2DAsync(io->costs, (size_t)K * 4, h->d_costs, (size_t)Kp * 4, (size_t)K * 4, B, d2x, s));
@@ -1602,11 +1671,8 @@ static int ensure_gen_stream(mppi_handle* h) {
 // gen_overlap the generator stream's noise launch beside the rollout, then the read-only reduce).  A graph launch pays
 // a fixed gap at its boundary (~8.5 us on the box, rocprof trace) that back-to-back stream launches do not, so
 // one-solve-per-step loops chain on the stream and multi-solve streams replay graphs.
-static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int flags) {
-  if (!(flags & MPPI_FLAG_DEVICE)) return fail(MPPI_E_ARG, "mppi_solve: MPPI_FLAG_CHAIN needs MPPI_FLAG_DEVICE");
-  if (io->noise) return fail(MPPI_E_ARG, "mppi_solve: MPPI_FLAG_CHAIN draws device noise (no injected noise)");
-  flags |= MPPI_FLAG_SEED_COUNTER;
-  MPPI_TRY(ensure_stream_buffers(h));
+// chain_iter: one iteration of the step (flags: the iteration's own), its statistics in slot is.it.
+static int chain_iter(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int flags, const IterStep& is) {
   // (an adapting handle ignores the overlap arm, as a capture does: it would draw the next noise ahead of this
   // solve's update of the law)
   const bool overlap = gen_overlap() && !h->capturing && !h->adapt_on && !h->cov_adapt_on && !h->steps_adapt_on;
@@ -1615,12 +1681,10 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   float* buf[2] = {h->d_noise, h->d_noise2};
   if (!overlap) {
     const NoiseStep ns{buf[h->graph_parity], buf[h->graph_parity ^ 1]};
-    const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns);
+    const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns, is.it, &is);
     if (rc != MPPI_OK) return rc;
-    note_ran(h, solve_opts(h, flags), B, 1);
     h->graph_parity ^= 1;  // this solve's reduce prefetched the next one's noise (still key-valid for B, seed)
-    if (flags & MPPI_FLAG_ASYNC) return MPPI_OK;
-    return finish_solve(h, B, io);
+    return MPPI_OK;
   }
   MPPI_TRY(ensure_gen_stream(h));
   const mppi_config& c = h->cfg;
@@ -1636,10 +1700,22 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
   HIP_TRY(hipEventRecord(h->ev_gen, h->gstream));
   h->gen_pending = true;
   const NoiseStep ns{buf[h->graph_parity], nullptr};  // read-only reduce, no counter bump (the generator owns it)
-  const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns);
+  const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns, is.it, &is);
   if (rc != MPPI_OK) return rc;
-  note_ran(h, solve_opts(h, flags), B, 1);
   h->graph_parity ^= 1;  // the generator prefetched the next one's noise (key-valid for B, seed)
+  return MPPI_OK;
+}
+
+static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int flags) {
+  if (!(flags & MPPI_FLAG_DEVICE)) return fail(MPPI_E_ARG, "mppi_solve: MPPI_FLAG_CHAIN needs MPPI_FLAG_DEVICE");
+  if (io->noise) return fail(MPPI_E_ARG, "mppi_solve: MPPI_FLAG_CHAIN draws device noise (no injected noise)");
+  flags |= MPPI_FLAG_SEED_COUNTER;
+  MPPI_TRY(ensure_stream_buffers(h));
+  // the control step's iterations, each a chained solve of its own: every one draws the counter's next key and
+  // prefetches the next one's noise, exactly as consecutive chained solves do
+  const int n = h->iter_n;
+  for (int it = 0; it < n; ++it) MPPI_TRY(chain_iter(h, B, io, seed, iter_flags(flags, it, n), IterStep{it, n}));
+  note_ran(h, solve_opts(h, flags), B, n);
   if (flags & MPPI_FLAG_ASYNC) return MPPI_OK;
   return finish_solve(h, B, io);
 }
@@ -1816,16 +1892,21 @@ int mppi_solve_ex(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int f
   if (h->cov_adapt_on) flags |= MPPI_FLAG_CROSS;  // the covariance's adaptation reads the solve's cross moments
   if (h->steps_adapt_on) flags |= MPPI_FLAG_STEP_MOMENTS;  // the table's refit reads the solve's per-step moments
   if (flags & (MPPI_FLAG_CROSS | MPPI_FLAG_STEP_MOMENTS)) flags |= MPPI_FLAG_STATS;  // both read the statistics' weights
-  if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, 1)) != MPPI_OK) return rc;
-  if ((flags & MPPI_FLAG_CROSS) && (rc = ensure_cross(h, 1)) != MPPI_OK) return rc;
-  if ((flags & MPPI_FLAG_STEP_MOMENTS) && (rc = ensure_step_mom(h, 1)) != MPPI_OK) return rc;
-  if (h->cov_adapt_on && (rc = ensure_cov_hist(h, 1)) != MPPI_OK) return rc;
-  if (h->ess_on && (rc = ensure_lambda(h, 1)) != MPPI_OK) return rc;
+  const int n = h->iter_n;  // the step's iterations: one per-step slot each
+  if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, n)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_CROSS) && (rc = ensure_cross(h, n)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_STEP_MOMENTS) && (rc = ensure_step_mom(h, n)) != MPPI_OK) return rc;
+  if (h->cov_adapt_on && (rc = ensure_cov_hist(h, n)) != MPPI_OK) return rc;
+  if (h->ess_on && (rc = ensure_lambda(h, n)) != MPPI_OK) return rc;
   if (flags & MPPI_FLAG_CHAIN) return chain_solve(h, B, io, seed, flags);
   HIP_TRY(drop_prefetch(h));  // a plain solve generates its own noise into d_noise
-  rc = enqueue_solve(h, B, io, seed, flags);
-  if (rc != MPPI_OK) return rc;
-  note_ran(h, solve_opts(h, flags), B, 1);
+  for (int it = 0; it < n; ++it) {  // (the counter advances per iteration by itself; a by-value seed: key seed + it)
+    const IterStep is{it, n};
+    rc = enqueue_solve(h, B, io, (flags & MPPI_FLAG_SEED_COUNTER) ? seed : seed + (uint64_t)it, iter_flags(flags, it, n),
+                       nullptr, nullptr, nullptr, it, &is);
+    if (rc != MPPI_OK) return rc;
+  }
+  note_ran(h, solve_opts(h, flags), B, n);
   if ((flags & MPPI_FLAG_DEVICE) && (flags & MPPI_FLAG_ASYNC)) return MPPI_OK;
   return finish_solve(h, B, io);
 }
@@ -1857,11 +1938,14 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   const mppi_config& c = h->cfg;
   if (const int e = ensure_stream_buffers(h); e != MPPI_OK) return e;
   // the statistics' slots exist before the capture begins: solve i's launches carry slot i's pointers
-  if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, n_solves)) != MPPI_OK) return rc;
-  if ((flags & MPPI_FLAG_CROSS) && (rc = ensure_cross(h, n_solves)) != MPPI_OK) return rc;
-  if ((flags & MPPI_FLAG_STEP_MOMENTS) && (rc = ensure_step_mom(h, n_solves)) != MPPI_OK) return rc;
-  if (h->cov_adapt_on && (rc = ensure_cov_hist(h, n_solves)) != MPPI_OK) return rc;
-  if (h->ess_on && (rc = ensure_lambda(h, n_solves)) != MPPI_OK) return rc;  // ... and the lambdas' slots
+  const int n_iter = h->iter_n;
+  if ((long)n_solves * n_iter > (1L << 24)) return fail(MPPI_E_ARG, "mppi_graph_capture: n_solves * n_iter too large");
+  const int n_total = n_solves * n_iter;  // one per-step slot per iteration
+  if ((flags & MPPI_FLAG_STATS) && (rc = ensure_stats(h, n_total)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_CROSS) && (rc = ensure_cross(h, n_total)) != MPPI_OK) return rc;
+  if ((flags & MPPI_FLAG_STEP_MOMENTS) && (rc = ensure_step_mom(h, n_total)) != MPPI_OK) return rc;
+  if (h->cov_adapt_on && (rc = ensure_cov_hist(h, n_total)) != MPPI_OK) return rc;
+  if (h->ess_on && (rc = ensure_lambda(h, n_total)) != MPPI_OK) return rc;  // ... and the lambdas' slots
   float* buf[2] = {h->d_noise, h->d_noise2};
   const bool prof = h->prof;
   h->prof = false;  // no event nodes inside the graph
@@ -1870,10 +1954,13 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   // of a valid prefetch)
   for (int p = 0; p < 2 && rc == MPPI_OK; ++p) {
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
-    for (int i = 0; i < n_solves && rc == MPPI_OK; ++i) {
-      const NoiseStep ns{buf[(p + i) % 2], buf[(p + i + 1) % 2]};
-      rc = enqueue_solve(h, B, io, seed, flags, traj_x ? traj_x + (size_t)i * B * c.nx : nullptr,
-                         traj_u ? traj_u + (size_t)i * B * c.nu : nullptr, &ns, i);
+    for (int j = 0; j < n_total && rc == MPPI_OK; ++j) {  // iteration it of control step i: slot and noise pair j
+      const int i = j / n_iter;
+      const IterStep is{j - i * n_iter, n_iter};
+      const NoiseStep ns{buf[(p + j) % 2], buf[(p + j + 1) % 2]};
+      rc = enqueue_solve(h, B, io, seed, iter_flags(flags, is.it, n_iter),
+                         traj_x ? traj_x + (size_t)i * B * c.nx : nullptr,
+                         traj_u ? traj_u + (size_t)i * B * c.nu : nullptr, &ns, j, &is);
     }
     hipGraph_t g = nullptr;
     const hipError_t ec = hipStreamEndCapture(h->stream, &g);
@@ -1898,7 +1985,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->graph_kclock = h->kclock;
   h->graph_opts = solve_opts(h, flags);
   h->graph_B = B;
-  h->graph_n = n_solves;
+  h->graph_n = n_total;  // (what a launch counts: slots, stamped rollouts, the noise pair's parity)
   h->graph_seed = seed;
   return MPPI_OK;
 }
@@ -3148,6 +3235,94 @@ int mppi_keep_inject_eval(mppi_handle* h, int B, const float* U, const float* no
   HIP_TRY(hipMemcpy2DAsync(noise_out, K * 4, h->d_noise, Kp * 4, K * 4, rows, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return MPPI_OK;
+}
+
+// The tracking's buffers (mppi_set_iterations, mppi_iter_best_eval): allocated once, never inside a solve.
+static int ensure_iter(mppi_handle* h) {
+  if (h->d_best_v) return MPPI_OK;
+  const mppi_config& c = h->cfg;
+  const size_t mb = (size_t)c.max_batch, nb = 2 * mb;
+  return alloc_group("mppi_set_iterations", {{(void**)&h->d_best_v, nb * c.nu * c.H * 4},
+                                             {(void**)&h->d_best_cost, at_least16(nb * 4)},
+                                             {(void**)&h->d_best_k, at_least16(nb * 4)},
+                                             {(void**)&h->d_best_iter, at_least16(nb * 4)},
+                                             {(void**)&h->d_best_U, mb * c.nu * c.H * 4}});
+}
+
+int mppi_set_iterations(mppi_handle* h, int n_iter, int return_best, int add_mean) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_iterations: null handle");
+  if (n_iter < 1 || n_iter > 16) return fail(MPPI_E_ARG, "mppi_set_iterations: n_iter must be in [1, 16]");
+  if ((return_best != 0 && return_best != 1) || (add_mean != 0 && add_mean != 1))
+    return fail(MPPI_E_ARG, "mppi_set_iterations: return_best and add_mean must be 0 or 1");
+  if (n_iter == h->iter_n && return_best == h->iter_best && add_mean == h->iter_mean) return MPPI_OK;  // graphs stay
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state: the captured graphs hold the iteration structure in their launches; everything in flight finishes
+  // first.  A prefetched noise is kept: the key sequence does not depend on the setting
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (n_iter > 1 || return_best || add_mean) MPPI_TRY(ensure_iter(h));
+  MPPI_TRY(drop_graphs(h, false));
+  h->iter_n = n_iter;
+  h->iter_best = return_best;
+  h->iter_mean = add_mean;
+  return MPPI_OK;
+}
+
+int mppi_get_iterations(mppi_handle* h, int* n_iter, int* return_best, int* add_mean) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_iterations: null handle");
+  if (n_iter) *n_iter = h->iter_n;
+  if (return_best) *return_best = h->iter_best;
+  if (add_mean) *add_mean = h->iter_mean;
+  return MPPI_OK;
+}
+
+// slot `slot` of the stored best -> host (the stream is idle); each pointer may be nullptr
+static int copy_best(mppi_handle* h, int B, int slot, float* v, float* cost, int32_t* k, int32_t* iter) {
+  const mppi_config& c = h->cfg;
+  const size_t ob = (size_t)slot * c.max_batch;
+  if (v) HIP_TRY(hipMemcpy(v, h->d_best_v + ob * c.nu * c.H, (size_t)B * c.nu * c.H * 4, hipMemcpyDeviceToHost));
+  if (cost) HIP_TRY(hipMemcpy(cost, h->d_best_cost + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (k) HIP_TRY(hipMemcpy(k, h->d_best_k + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  if (iter) HIP_TRY(hipMemcpy(iter, h->d_best_iter + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+int mppi_get_best(mppi_handle* h, int B, float* v, float* cost, int32_t* k, int32_t* iter) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_best: null handle");
+  if (h->best_B == 0)
+    return fail(MPPI_E_STATE, "mppi_get_best: no solve has tracked a best sample on the handle (mppi_set_iterations)");
+  if (B < 1 || B > h->best_B) return fail(MPPI_E_ARG, "mppi_get_best: B beyond the batch of the last tracking solve");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_best(h, B, 0, v, cost, k, iter);
+}
+
+int mppi_iter_best_eval(mppi_handle* h, int B, const float* U, const float* noise, const float* costs, int reset, int it,
+                        float* v, float* cost, int32_t* k, int32_t* iter) {
+  if (!h || !U || !noise || !costs) return fail(MPPI_E_ARG, "mppi_iter_best_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_iter_best_eval: B out of range [1, max_batch]");
+  if (!reset && (!v || !cost || !k || !iter))
+    return fail(MPPI_E_ARG, "mppi_iter_best_eval: reset == 0 carries the stored best in (v, cost, k, iter)");
+  HIP_TRY(hipSetDevice(h->device));
+  MPPI_TRY(ensure_iter(h));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t mb = (size_t)c.max_batch, rows = (size_t)B * c.nu * c.H;
+  float* bv = h->d_best_v + mb * c.nu * c.H;  // the evaluation's own slot: the handle's stored best is untouched
+  HIP_TRY(hipMemcpyAsync(h->d_best_U, U, rows * 4, hipMemcpyHostToDevice, s));
+  MPPI_TRY(stage_noise(h, noise, rows));
+  MPPI_TRY(stage_costs(h, costs, B));
+  if (!reset) {
+    HIP_TRY(hipMemcpyAsync(bv, v, rows * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_best_cost + mb, cost, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_best_k + mb, k, (size_t)B * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_best_iter + mb, iter, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  }
+  const IterBestArgs ia{B, c.nu, c.H, c.K, h->Kp, reset ? 1 : 0, it, c.ctrl_clamp, h->d_costs, h->d_noise,
+                        h->d_best_U, bv, h->d_best_cost + mb, h->d_best_k + mb, h->d_best_iter + mb};
+  HIP_TRY(timed(h, kIter, [&] { return launch_iter_best(ia, s); }));
+  HIP_TRY(hipStreamSynchronize(s));
+  return copy_best(h, B, 1, v, cost, k, iter);
 }
 
 // slot `slot` of the diagnostics' buffers -> host (the stream is idle)

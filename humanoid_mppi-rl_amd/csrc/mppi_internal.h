@@ -447,6 +447,27 @@ struct KeepArgs {
 inline int keep_pitch(int n_keep) { return (n_keep + 3) / 4 * 4; }
 hipError_t launch_keep_gather(const KeepArgs& a, int shift, hipStream_t stream);  // v, kcost, idx, count, steps
 hipError_t launch_keep_inject(const KeepArgs& a, hipStream_t stream);  // eps = v - U on columns < count, rows < steps
+// kernels_iter.hip: inner iterations per control step (mppi_set_iterations; the tracking's rule: iter_best.h), by value
+// like SolveArgs, so the launches can sit in a captured graph.  The stored best of solve b: bv [nu][H], bcost, bk, biter.
+struct IterBestArgs {
+  int B, nu, H, K, Kp;
+  int reset;             // 1: the step's first iteration (the stored best is not read)
+  int it;                // the iteration's index within its step
+  float clamp;           // cfg.ctrl_clamp (<= 0: none)
+  const float* costs;    // [B][Kp] the selection's input: the unmasked end of the wcost chain
+  const float* noise;    // [B][nu][H][Kp] as the rollout saw it
+  const float* U;        // [B][nu][H] the nominal the rollout perturbed
+  float* bv;             // [B][nu][H] in/out
+  float* bcost;          // [B] in/out
+  int32_t* bk;           // [B] out
+  int32_t* biter;        // [B] out
+};
+hipError_t launch_iter_best(const IterBestArgs& a, hipStream_t stream);
+// u0 [B][nu] <- bv[b][u][0] where bk[b] >= 0
+hipError_t launch_iter_apply(const float* bv, const int32_t* bk, float* u0, int B, int nu, int H, hipStream_t stream);
+// noise[b][u][t][j0] <- +0.0, j0 = count[b] in [0, n_keep] (count == nullptr: 0); j0 >= K: nothing
+hipError_t launch_iter_mean(float* noise, const int32_t* count, int n_keep, int B, int nu, int H, int K, int Kp,
+                            hipStream_t stream);
 // kernels_ctrl_cost.hip: the control-cost term (mppi_set_control_cost; the rule for lin: control_cost.h), by value
 // like SolveArgs: read-only on the solve's U, noise and costs, so the launches can sit in a captured graph.
 struct CtrlLaw {

@@ -894,6 +894,49 @@ function kept(c::Controller)
 end
 
 """
+    set_iterations!(c, n_iter; return_best = false, add_mean = false)
+
+Refine the distribution `n_iter` (1:16) times per control step on the device (mppi_set_iterations; CEM / iCEM proper): a
+step is bit for bit `n_iter` consecutive solves on the same state, all but the last without shift, each with a fresh
+noise key.  `return_best`: the step executes the first control of the best sample seen during the step; `add_mean`: the
+last iteration enters the nominal itself as a candidate.  Injected noise with `n_iter > 1` and `u0_before` with
+`n_iter > 1` or `return_best` are refused.  Any change destroys captured graphs.
+"""
+function set_iterations!(c::Controller, n_iter::Integer; return_best::Bool = false, add_mean::Bool = false)
+    check(ccall((:mppi_set_iterations, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Cint), c.handle, n_iter,
+                Cint(return_best), Cint(add_mean)))
+    return c
+end
+
+"""
+    iterations(c) -> (n_iter::Int, return_best::Bool, add_mean::Bool)
+
+The setting of `set_iterations!` (mppi_get_iterations); `(1, false, false)` by default.
+"""
+function iterations(c::Controller)
+    n, rb, am = Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0)
+    check(ccall((:mppi_get_iterations, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Cint}), c.handle, n, rb, am))
+    return (Int(n[]), rb[] != 0, am[] != 0)
+end
+
+"""
+    best(c) -> (v::Matrix{Float32}, cost::Float32, k::Int, iter::Int)
+
+The best sampled control sequence of the last control step made with `set_iterations!` on (mppi_get_best; waits for
+the stream): the planned trajectory `v` (nu, H), its cost, its 1-based sample index and the 1-based iteration that drew
+it (both 0 when no sample of the step was finite).
+"""
+function best(c::Controller)
+    nu, H = c.cfg.nu, c.cfg.H
+    v = zeros(Float32, H, nu)  # the engine's [nu][H], row-major
+    cost, k, it = Ref{Float32}(Inf32), Ref{Int32}(-1), Ref{Int32}(-1)
+    GC.@preserve v check(ccall((:mppi_get_best, LIB), Cint,
+                               (Ptr{Cvoid}, Cint, Ptr{Float32}, Ref{Float32}, Ref{Int32}, Ref{Int32}), c.handle, 1,
+                               pointer(v), cost, k, it))
+    return (permutedims(v, (2, 1)), cost[], Int(k[]) + 1, Int(it[]) + 1)
+end
+
+"""
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 
 The diagnostics of the last solve made with `stats = true` (mppi_get_stats): the softmin statistics of its costs and

@@ -40,7 +40,8 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_keep_inject_eval", "mppi_get_cross_moments", "mppi_cross_moments_eval",
             "mppi_set_noise_cov_adapt", "mppi_get_noise_cov_adapt", "mppi_get_noise_cov_law", "mppi_set_noise_basis",
             "mppi_get_noise_basis", "mppi_set_noise_steps", "mppi_get_noise_steps", "mppi_set_noise_steps_adapt",
-            "mppi_get_noise_steps_adapt", "mppi_get_step_moments", "mppi_step_moments_eval"]
+            "mppi_get_noise_steps_adapt", "mppi_get_step_moments", "mppi_step_moments_eval", "mppi_set_iterations",
+            "mppi_get_iterations", "mppi_get_best", "mppi_iter_best_eval"]
 
 
 class MPPIError(RuntimeError):
@@ -175,6 +176,10 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_get_noise_steps_adapt": (i32, [vp] + [ctypes.POINTER(ctypes.c_float)] * 3 + [ctypes.POINTER(i32)]),
         "mppi_get_step_moments": (i32, [vp, i32, i32, vp, vp]),
         "mppi_step_moments_eval": (i32, [vp, i32, vp, vp, vp, vp]),
+        "mppi_set_iterations": (i32, [vp, i32, i32, i32]),
+        "mppi_get_iterations": (i32, [vp] + [ctypes.POINTER(i32)] * 3),
+        "mppi_get_best": (i32, [vp, i32, vp, vp, vp, vp]),
+        "mppi_iter_best_eval": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "mppi_kernel_clock_read": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_double)]),
     }

@@ -98,6 +98,11 @@ class MPPIModel:
     n_keep:   carry the n_keep best sampled control sequences of each solve into the next one (Engine.set_elite_keep;
               iCEM's keep / shift elites), an int in 1..K: mppi_controller's shifting solves carry them time-shifted,
               mppi_step's as they are.  0 (default): every solve starts from fresh noise alone.
+    n_iter, return_best, add_mean: refine the distribution n_iter (1..16) times per control step on the device
+              (Engine.set_iterations; CEM / iCEM proper); return_best executes the first control of the best sample of
+              the step instead of the mean's, add_mean enters the nominal as a candidate in the last iteration.  Needs
+              device noise when n_iter > 1 and excludes u0_before when n_iter > 1 or return_best.  (1, False, False)
+              (default): one solve per step.
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
@@ -106,7 +111,8 @@ class MPPIModel:
                  adapt_noise: float = 0.0, adapt_limits=(1e-3, 10.0, 0.95), adapt_on: str = "host", ess_target: float = 0.0,
                  lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, rate_cost=None,
                  rate_anchor: bool = True, n_elite: int = 0, n_keep: int = 0, noise_knots=None, noise_basis=None,
-                 noise_steps=None, adapt_steps: float = 0.0, **overrides):
+                 noise_steps=None, adapt_steps: float = 0.0, n_iter: int = 1, return_best: bool = False,
+                 add_mean: bool = False, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -131,6 +137,15 @@ class MPPIModel:
         if isinstance(n_keep, bool) or not isinstance(n_keep, (int, np.integer)) or n_keep < 0:
             raise ValueError("MPPIModel: n_keep must be an int in 1..K (0: off)")
         self.n_keep = int(n_keep)
+        if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or not 1 <= n_iter <= 16:
+            raise ValueError("MPPIModel: n_iter must be an int in 1..16")
+        if not isinstance(return_best, (bool, np.bool_)) or not isinstance(add_mean, (bool, np.bool_)):
+            raise ValueError("MPPIModel: return_best and add_mean must be bools")
+        if n_iter > 1 and noise != "device":
+            raise ValueError("MPPIModel: n_iter > 1 needs noise = 'device' (one injected array cannot serve n iterations)")
+        if u0_before and (n_iter > 1 or return_best):
+            raise ValueError("MPPIModel: u0_before excludes n_iter > 1 and return_best")
+        self.n_iter, self.return_best, self.add_mean = int(n_iter), bool(return_best), bool(add_mean)
         self.preset = preset
         self.body_ids = dict(HUMANOID_BODY_IDS if body_ids is None else body_ids)
         self.u0_before = bool(u0_before)
@@ -216,6 +231,8 @@ class MPPIModel:
             self.engine.set_elites(self.n_elite)
         if self.n_keep > 0:
             self.engine.set_elite_keep(self.n_keep)
+        if self.n_iter > 1 or self.return_best or self.add_mean:
+            self.engine.set_iterations(self.n_iter, self.return_best, self.add_mean)
         self.noise = noise
         self.seed = int(seed)
         self.calls = 0
@@ -356,7 +373,8 @@ class MPPIModel:
         self.engine.set_noise_model(self.noise_sigma, self.noise_rho)
 
     def next_seed(self) -> int:
-        self.calls += 1
+        # (iteration i of a step draws key seed + i: consecutive steps never share a key)
+        self.calls += getattr(self, "n_iter", 1)
         return (self.seed << 32) ^ self.calls
 
     def close(self):

@@ -630,6 +630,66 @@ class Engine:
                                                _ptr(out)))
         return out
 
+    # -- inner iterations per control step (mppi_set_iterations; mppi_hip.stats.iter_best_ref states the tracking's rule)
+    def set_iterations(self, n_iter: int, return_best: bool = False, add_mean: bool = False):
+        """Refine the distribution n_iter (1..16) times per control step on the device (mppi_set_iterations; CEM / iCEM
+        proper): a step -- one solve, one chained solve, one solve of a captured graph -- is bit for bit n_iter
+        consecutive solves on the same state, all but the last without shift and env step, each with a fresh noise key
+        and a statistics slot of its own (Engine.stats(B, step=it)).  return_best: the step executes the first control
+        of the best sample seen during the step (u0, the rate anchor, the env step and the trajectory record see it; U
+        is unchanged).  add_mean: the step's last iteration enters the nominal itself as a candidate.  While any of the
+        three is on, the best sampled sequence of the step is tracked on the device (Engine.best).  Injected noise with
+        n_iter > 1 and u0_before with n_iter > 1 or return_best are refused.  Any change destroys captured graphs; a
+        prefetched noise is kept."""
+        for name, v in (("return_best", return_best), ("add_mean", add_mean)):
+            if v not in (0, 1, False, True):
+                raise ValueError(f"set_iterations: {name} must be a bool")
+        L.check(self.lib.mppi_set_iterations(self._h, int(n_iter), int(bool(return_best)), int(bool(add_mean))))
+        return self
+
+    def iterations(self) -> tuple[int, bool, bool]:
+        """(n_iter, return_best, add_mean) of mppi_get_iterations; (1, False, False) by default."""
+        n, rb, am = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        L.check(self.lib.mppi_get_iterations(self._h, ctypes.byref(n), ctypes.byref(rb), ctypes.byref(am)))
+        return int(n.value), bool(rb.value), bool(am.value)
+
+    def best(self, B: int = 1) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(v [B, nu, H], cost [B], k [B] int32, iter [B] int32): the best sampled control sequence of the last control
+        step enqueued -- the planned trajectory -- with its cost, its sample index and the iteration that drew it
+        (mppi_get_best; waits for the stream).  k = iter = -1, cost = +inf, v = 0 when no sample of the step was
+        finite."""
+        c = self.config
+        v = np.empty((B, c.nu, c.H), np.float32)
+        cost = np.empty(B, np.float32)
+        k = np.empty(B, np.int32)
+        it = np.empty(B, np.int32)
+        L.check(self.lib.mppi_get_best(self._h, B, _ptr(v), _ptr(cost), _ptr(k), _ptr(it)))
+        return v, cost, k, it
+
+    def iter_best_eval(self, U, noise, costs, it: int = 0, stored=None):
+        """The tracking kernel on host arrays U [B, nu, H], noise [B, nu, H, K] (as the rollout saw it) and costs
+        [B, K] (NaN, +-inf and ties allowed) with the handle's ctrl_clamp -> (v, cost, k, iter) as best()
+        (mppi_iter_best_eval).  stored None: the step's first iteration (the stored best is reset); else the (v, cost,
+        k, iter) carried in.  The handle's stored best is untouched; no dynamics or cost need be loaded."""
+        c = self.config
+        U = _f32(U).reshape(-1, c.nu, c.H)
+        B = U.shape[0]
+        nz = _f32(noise).reshape(B, c.nu, c.H, c.K)
+        costs = _f32(costs).reshape(B, c.K)
+        if stored is None:
+            v = np.empty((B, c.nu, c.H), np.float32)
+            cost = np.empty(B, np.float32)
+            k = np.empty(B, np.int32)
+            bi = np.empty(B, np.int32)
+        else:
+            v = _f32(stored[0]).reshape(B, c.nu, c.H).copy()
+            cost = _f32(stored[1]).reshape(B).copy()
+            k = np.ascontiguousarray(np.asarray(stored[2], np.int32)).reshape(B).copy()
+            bi = np.ascontiguousarray(np.asarray(stored[3], np.int32)).reshape(B).copy()
+        L.check(self.lib.mppi_iter_best_eval(self._h, B, _ptr(U), _ptr(nz), _ptr(costs), int(stored is None), int(it),
+                                             _ptr(v), _ptr(cost), _ptr(k), _ptr(bi)))
+        return v, cost, k, bi
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,
@@ -662,11 +722,12 @@ class Engine:
         if rc != L.MPPI_E_NONFINITE or raise_nonfinite:
             L.check(rc)
         sq = (lambda a: a[0]) if single else (lambda a: a)
-        st = {k: sq(v) for k, v in self.stats(B).items()} if stats or cross or step_moments else None
+        last = self.iterations()[0] - 1 if stats or cross or step_moments else 0  # the step's last iteration's slot
+        st = {k: sq(v) for k, v in self.stats(B, last).items()} if stats or cross or step_moments else None
         if cross:
-            st["eps_mx"] = sq(self.cross_moments(B))
+            st["eps_mx"] = sq(self.cross_moments(B, last))
         if step_moments:
-            m1, m2 = self.step_moments(B)
+            m1, m2 = self.step_moments(B, last)
             st["step_m1"], st["step_m2"] = sq(m1), sq(m2)
         return SolveResult(U=sq(Uo), costs=None if costs is None else sq(costs),
                            weights=None if weights is None else sq(weights), u0=sq(u0), status=rc, stats=st)

@@ -959,3 +959,54 @@ def adapt_noise_steps_f32(table, m1, m2, rate, sigma_min=1e-3, sigma_max=10.0, c
         fl = np.asarray(fill, np.float32)
         new = _shift_steps(new, np.full(S.shape[1], fl, np.float32) if fl.ndim == 0 else fl.reshape(1, -1))
     return new[0] if single else new
+
+
+def iter_best_ref(U, noise, costs, it: int = 0, stored=None, ctrl_clamp: float = 0.0):
+    """The best-sample tracking of mppi_set_iterations in float32 (csrc/iter_best.h), bitwise what the device computes:
+    U [B, nu, H] (or [nu, H]) the nominal the rollout perturbed, noise [B, nu, H, K] (or [nu, H, K]) as the rollout saw
+    it, costs [B, K] (or [K]) what the softmin would weigh ahead of any elite masking ->
+    (v [B, nu, H] float32, cost [B] float32, k [B] int32, iter [B] int32).
+
+        stored None  the step's first iteration: the stored best is reset to (v = +0.0, cost = +inf, k = -1, iter = -1)
+        stored       else the (v, cost, k, iter) carried in (copied, never written)
+        k*           = the lowest k attaining the minimum over the finite costs (-0.0 equals +0.0); none finite: no
+                       candidate
+        accepted iff costs[k*] < cost, strict in float32; then cost = costs[k*] bit for bit, k = k*, iter = it and
+        v[u, t]      = float32(U[u, t] + noise[u, t, k*]), clamped to +-ctrl_clamp when ctrl_clamp > 0 as
+                       csrc/rate_cost.h clamps (c + (s - s): a non-finite sum stays non-finite)
+
+    ValueError on shapes that do not agree."""
+    U = np.asarray(U, np.float32)
+    eps = np.asarray(noise, np.float32)
+    c = np.asarray(costs, np.float32)
+    single = U.ndim == 2
+    if single:
+        U, eps, c = U[None], eps[None], c[None]
+    if U.ndim != 3 or eps.ndim != 4 or eps.shape[:3] != U.shape or c.shape != (U.shape[0], eps.shape[3]):
+        raise ValueError("iter_best_ref: need U [B, nu, H], noise [B, nu, H, K] and costs [B, K]")
+    B, nu, H = U.shape
+    if stored is None:
+        v = np.zeros((B, nu, H), np.float32)
+        cost = np.full(B, np.inf, np.float32)
+        k = np.full(B, -1, np.int32)
+        bi = np.full(B, -1, np.int32)
+    else:
+        v = np.array(stored[0], np.float32).reshape(B, nu, H)
+        cost = np.array(stored[1], np.float32).reshape(B)
+        k = np.array(stored[2], np.int32).reshape(B)
+        bi = np.array(stored[3], np.int32).reshape(B)
+    clamp = np.float32(ctrl_clamp)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b in range(B):
+            fin = np.isfinite(c[b])
+            if not fin.any():
+                continue
+            ks = int(np.argmin(np.where(fin, c[b], np.float32(np.inf))))  # the first occurrence: the lowest k
+            if not c[b, ks] < cost[b]:
+                continue
+            cost[b], k[b], bi[b] = c[b, ks], ks, it
+            s = (U[b] + eps[b][:, :, ks]).astype(np.float32)
+            if clamp > 0:
+                s = (np.fmin(clamp, np.fmax(-clamp, s)) + (s - s)).astype(np.float32)
+            v[b] = s
+    return (v[0], cost[0], k[0], bi[0]) if single else (v, cost, k, bi)

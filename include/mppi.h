@@ -130,7 +130,14 @@ extern "C" {
  *      before, with the same grids and arguments; a solve without the flag likewise.  BEHAVIOUR while the table is on
  *      only: mppi_set_noise_model(NULL, 0) returns MPPI_E_STATE; mppi_set_noise_knots(n_knots > 0),
  *      mppi_set_noise_basis(n_basis > 0), mppi_set_noise_cov(Sigma), mppi_set_noise_adapt(rate > 0) and
- *      mppi_set_control_cost(gamma > 0) return MPPI_E_UNSUPPORTED. */
+ *      mppi_set_control_cost(gamma > 0) return MPPI_E_UNSUPPORTED.
+ *      Additive, version unchanged: mppi_set_iterations / mppi_get_iterations / mppi_get_best / mppi_iter_best_eval
+ *      (inner iterations per control step -- CEM / iCEM proper -- in every stream form, the best sampled sequence of the
+ *      step tracked and optionally executed on the device, the nominal entered as a candidate); kernel name "iter" in
+ *      mppi_kernel_time.  A handle that never calls the setter, or sets (1, 0, 0), launches exactly the kernels it
+ *      launched before, with the same grids and arguments.  BEHAVIOUR while it is on only: injected io.noise with
+ *      n_iter > 1 returns MPPI_E_ARG; MPPI_FLAG_U0_BEFORE with n_iter > 1 or with return_best returns
+ *      MPPI_E_UNSUPPORTED; the getters that take `step` index iterations (mppi_get_stats). */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -887,6 +894,75 @@ int mppi_keep_inject_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] ho
                           const int32_t* count /* [B] */, const int32_t* steps /* [B] */,
                           float* noise_out /* [B][nu][H][K] */);
 
+/* Inner iterations per control step (CEM-MPC, PETS, PlaNet, iCEM): the sampling distribution is refined n_iter times
+ * on the same state before the step acts, ON THE DEVICE and in every stream form -- no host loop, so an iterated
+ * planner lives inside a chained stream or a captured graph.
+ * DEFINITION.  A control step is one mppi_solve / mppi_solve_ex call, one chained solve, or one of the n_solves of a
+ * captured graph (with or without trajectory logging).  With n_iter = n it is, bit for bit, n consecutive solves of
+ * the engine at n_iter = 1 on the same x0 and ctx: iterations 0..n-2 carry the step's flags with MPPI_FLAG_SHIFT and
+ * MPPI_FLAG_ENV_STEP removed and continue from the U the previous iteration left, iteration n-1 carries the flags as
+ * given.  Hence: the kept set (mppi_set_elite_keep) is stored with shift 0 between iterations and shifted at the last;
+ * mppi_set_noise_steps_adapt refits per iteration and shifts its rows at the last; the adapted laws adapt per
+ * iteration; u_prev (the rate anchor) is stored, the trajectory recorded and the environment stepped once per control
+ * step; the ESS search, the elites, the cost terms and the bounds run per iteration.
+ * Noise keys: every iteration draws a fresh key.  With the seed counter (chained, graph, MPPI_FLAG_SEED_COUNTER) every
+ * iteration advances the counter by one, as every solve does; with a by-value seed iteration i draws key seed + i.
+ * mppi_get_seed_counter keeps its meaning (the key the next iteration would draw, prefetch accounted for); chained and
+ * graph forms prefetch the next iteration's noise as consecutive chained solves do.
+ * Inputs and outputs: host-pointer solves upload x0, ctx and U once and read U, u0, costs and weights back once;
+ * io.costs and io.weights are the last iteration's.  Injected io.noise with n_iter > 1 is MPPI_E_ARG (one array cannot
+ * serve n iterations); MPPI_FLAG_U0_BEFORE with n_iter > 1 or with return_best is MPPI_E_UNSUPPORTED.
+ * Per-step slots: every place that counts solves counts iterations -- the statistics, cross-moment, step-moment,
+ * lambda, noise-law and covariance-law slots, the launch-clock count.  A plain or chained solve fills slots
+ * 0..n_iter-1, a graph n_solves * n_iter (see mppi_get_stats for `step`).  The read-outs without per-step slots (the
+ * control and rate terms, the elite set, the kept set, the bound counts) hold the last iteration's values.  The
+ * split mode's probe still runs once, before the first iteration.  MPPI_E_NONFINITE is reported as that loop of
+ * device solves followed by one synchronisation reports it.  An error at an iteration other than the first (a launch
+ * that fails) returns at once, as the loop would: the earlier iterations stay enqueued, U and the seed counter have
+ * advanced by them, the getters still describe the step before, and with host pointers nothing has been copied back.
+ * BEST SAMPLE.  While n_iter > 1 or return_best or add_mean is set, every iteration runs iter_best_kernel behind the
+ * cost terms and the elite / keep selection and ahead of the lambda search and the reduce.  The rule is
+ * csrc/iter_best.h (host + device); mppi_hip.stats.iter_best_ref is its numpy restatement, bitwise equal.  For solve b,
+ * with c[0..K) the costs the softmin would weigh AHEAD of any elite masking (the keep store's input) and eps' the
+ * noise as the rollout saw it (injected, then projected):
+ *     k* = the first sample by (c_k, k) over the finite costs (mppi_set_elites' order with n = 1: -0 equals +0, the
+ *          lowest k wins a tie); no finite cost: no candidate
+ *     at the step's first iteration the stored best is reset first: bcost = +inf, bk = -1, biter = -1, bv = +0.0
+ *     the candidate is accepted iff c[k*] < bcost (strict, fp32: a carried elite that reproduces its cost keeps the
+ *     earlier iteration); then bcost = c[k*] bit for bit, bk = k*, biter = it and
+ *     bv[b][u][t] = U[b][u][t] + eps'[b][u][t][k*]: fp32, one rounding, then the rollouts' clamp to +-ctrl_clamp when
+ *     ctrl_clamp > 0 -- the control the rollout applied
+ * One block per solve, no global atomics, bitwise repeatable; the pad lanes K..Kp never count.  The analytic cartpole
+ * leaves its fused one-launch form while the feature is on, exactly as for elites.
+ * return_best: at the step's last iteration u0[b][u] = bv[b][u][0] (iCEM executes the first action of the best
+ * trajectory, not of the mean); when no sample of the whole step was finite u0 stays as the update left it.  The
+ * launch sits behind the update and shift, ahead of the bounds clip (lo <= u0 <= hi still holds exactly), of the
+ * u_prev store and the env step: the anchor, the env step, the trajectory record and io.u0 all see the executed
+ * control, in every stream form.  U, the nominal that warm-starts the next step, is bit for bit what it is with
+ * return_best = 0.
+ * add_mean (iCEM's "add mean to samples"): in the step's last iteration eps[b][u][t][j0] = +0.0 for every (u, t),
+ * behind the kept-elite injection and ahead of the bounds projection and the rollout, where j0 = count[b], the stored
+ * kept set's count read on the device (0 with keep off); j0 >= K writes nothing; every other element is untouched.
+ * With n_iter = 1 the one iteration is the last.  What return_best executes is then never worse, under the model,
+ * than the nominal.
+ * mppi_set_iterations: n_iter in 1..16 (default 1), return_best and add_mean 0 or 1; anything else is MPPI_E_ARG and
+ * changes nothing.  Any change destroys captured graphs; the value already in effect is a no-op that keeps them.  A
+ * prefetched noise is kept (the key sequence does not depend on the setting).  All buffers are allocated here, none
+ * inside a solve.
+ * mppi_get_best: the stored best of the last control step enqueued (after a graph launch the chain's last step) -- the
+ * planned trajectory; waits for the stream, each pointer may be NULL.  MPPI_E_STATE before any tracking solve,
+ * MPPI_E_ARG for B beyond it.
+ * mppi_iter_best_eval: the same kernel on host arrays with an output slot of its own (the handle's stored best is
+ * untouched); reset = 0: v, cost, k, iter carry the stored best in.  Needs only mppi_create; goes through the staging
+ * buffers like mppi_stats_eval (a prefetched noise is dropped, key sequence unchanged).  Kernel name "iter". */
+int mppi_set_iterations(mppi_handle* h, int n_iter, int return_best, int add_mean);
+int mppi_get_iterations(mppi_handle* h, int* n_iter, int* return_best, int* add_mean);
+int mppi_get_best(mppi_handle* h, int B, float* v /* [B][nu][H] */, float* cost /* [B] */, int32_t* k /* [B] */,
+                  int32_t* iter /* [B] */);
+int mppi_iter_best_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
+                        const float* noise /* [B][nu][H][K] host */, const float* costs /* [B][K] host */, int reset,
+                        int it, float* v, float* cost, int32_t* k, int32_t* iter /* in/out */);
+
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
  *     eps_m2 [b][u] = 1/H     sum_{t=0..H-1} sum_k w_k eps[b][u][t][k]^2
@@ -897,6 +973,9 @@ int mppi_keep_inject_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] ho
  * mppi_get_stats waits for the stream and copies to host memory: stats [B], eps_m2 / eps_m11 [B][nu]; each pointer
  * may be NULL.  step = 0 after a plain or chained solve; after mppi_graph_launch of a graph captured with the flag,
  * step = 0..n_solves-1 (solve i of the chain writes slot i; the slots are allocated before the capture begins).
+ * With mppi_set_iterations(n_iter > 1) `step` is the flat index over iterations in execution order, step * n_iter + it:
+ * 0..n_iter-1 after a plain or chained solve, 0..n_solves*n_iter-1 after a graph launch -- one mppi_solve_stats per
+ * iteration, what one watches to see an iterated planner converge.  Every getter that takes `step` counts alike.
  * MPPI_E_STATE if no solve with the flag has run on the handle; MPPI_E_ARG for step or B beyond that solve / graph.
  * The last statistics stay readable after mppi_set_noise_model destroyed the graph.
  * mppi_device_stats: the device buffers for consumers on the stream, slot-major with the handle's max_batch as the
@@ -981,7 +1060,8 @@ int mppi_sync(mppi_handle* h);
  * (the selection of mppi_set_elites), "keep" (the inject, selection and gather launches of mppi_set_elite_keep, counted
  * as one per solve), "cross" (the two launches of MPPI_FLAG_CROSS), "cov_adapt" (the update kernel of
  * mppi_set_noise_cov_adapt), "step_mom" (the pass of MPPI_FLAG_STEP_MOMENTS), "step_adapt" (the refit kernel of
- * mppi_set_noise_steps_adapt). */
+ * mppi_set_noise_steps_adapt), "iter" (the tracking, apply and mean launches of mppi_set_iterations, counted as one
+ * per iteration). */
 int mppi_profile(mppi_handle* h, int enable);
 int mppi_kernel_time(mppi_handle* h, const char* kernel, int* count, double* total_ms);
 
