@@ -368,6 +368,7 @@ inline hipError_t fc_launch(Kern kern, int grid, int block, size_t lds, hipStrea
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
+  g_rollout_func = reinterpret_cast<const void*>(kern);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, stream, a, net);
   return hipGetLastError();
 }

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include "costs.h"
+#include "gen_overlap.h"
 #include "mppi_internal.h"
 #include "philox.h"
 #include "wave_reduce.h"
@@ -50,6 +51,83 @@ hipError_t launch_noise(float* noise, int B, int nu, int H, int Kp, uint64_t see
   hipLaunchKernelGGL(noise_kernel, grid, dim3(256), 0, stream, noise, rows, nu, H, Kp, seed, seed_ctr, sigma);
   return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// a1 built to run BESIDE the rollout (mppi_api.hip chain_iter, gen_overlap.h): the same function of (seed + counter,
+// b, u, t, k) as noise_kernel, bit for bit, with the same 16-B nontemporal stores -- shaped so that one of its waves
+// fits into what two rollout waves leave of a SIMD's register file (kGenVgprs = 16 registers; fc_wave32_x3p_kernel
+// holds 248 each).  One wave per block, no LDS; block i draws the whole rows [i rpb, (i + 1) rpb), a few us of work,
+// and exits: not persistent, no spin, no flag, so a block placed ahead of a rollout block delays it by one block's run
+// at most, and the register file itself holds the generator to one wave per SIMD while the rollout runs.
+// For the register budget: the row (b, u, t), the key, the round keys and the uniform half of Philox's first two
+// rounds (philox4x32_10_row) live in SGPRs, stepped -- not divided -- from row to row; the store is a buffer store
+// against a resource over the block's own rows (uniform base, so the whole noise array may pass 4 GiB), the row and
+// chunk as the scalar offset and the lane's 16-B offset as the one address register (the hardware drops what falls
+// outside the block's rows); one quad is drawn and stored at a time: the loops are not unrolled, and q is opaque to
+// the optimiser, which would otherwise carry q * 0xD2511F53 as a 64-bit induction variable per lane.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kGenWave) __attribute__((amdgpu_num_vgpr(kGenVgprs / 2)))  // (the target doubles it)
+void noise_beside_kernel(float* __restrict__ noise, int rows, int nu, int H, int Kp, int rpb, uint64_t seed,
+                         const unsigned long long* seed_ctr, float sigma) {
+  const int r0 = blockIdx.x * rpb;
+  const int nr = min(rpb, rows - r0);
+  if (nr <= 0) return;
+  const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+  const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+  const int bu = r0 / H;
+  uint32_t t = (uint32_t)(r0 - bu * H), u = (uint32_t)(bu % nu), b = (uint32_t)(bu / nu);
+  const uint32_t nq = (uint32_t)Kp >> 2, row_bytes = (uint32_t)Kp * 4u;
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  // raw buffer (stride 0) over rows [r0, r0 + nr): 32-bit data format, offsets range-checked against its size
+  const __amdgpu_buffer_rsrc_t rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(noise + (long)r0 * Kp, 0, (int)((uint32_t)nr * row_bytes), 0x00020000);
+  const uint32_t lane_off = threadIdx.x * 16u;
+  uint32_t row_off = 0;
+#pragma unroll 1
+  for (int i = 0; i < nr; ++i) {
+#pragma unroll 1
+    for (uint32_t q0 = 0; q0 < nq; q0 += kGenWave) {
+      uint32_t q = q0 + threadIdx.x;
+      asm volatile("" : "+v"(q));
+      if (q < nq) {
+        float z[4];
+        philox_normal4_row(q, t, u, b, k0, k1, z);
+        const f4 v = {sigma * z[0], sigma * z[1], sigma * z[2], sigma * z[3]};
+        // (aux 2: the nontemporal policy, as noise_kernel's __builtin_nontemporal_store)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, v), rsrc, (int)lane_off,
+                                               (int)(row_off + q0 * 16u), 2);
+      }
+    }
+    row_off += row_bytes;
+    if (++t == (uint32_t)H) {
+      t = 0;
+      if (++u == (uint32_t)nu) {
+        u = 0;
+        ++b;
+      }
+    }
+  }
+}
+
+int gen_rows_per_block() {
+  // whole rows per block of noise_beside_kernel (MPPI_GEN_ROWS, read per launch: an A/B knob)
+  if (const char* e = std::getenv("MPPI_GEN_ROWS")) return std::min(64, std::max(1, std::atoi(e)));
+  return kGenRows;
+}
+
+hipError_t launch_noise_beside(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
+                               const unsigned long long* seed_ctr, float sigma, hipStream_t stream) {
+  const long rows = (long)B * nu * H;
+  const int rpb = gen_rows_per_block();
+  // (a lane's offset in its block's rows is 32-bit; so is the grid)
+  if (rows > 0x7fffffffL || (long)rpb * Kp * 4 > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(noise_beside_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(kGenWave), 0, stream, noise,
+                     (int)rows, nu, H, Kp, rpb, seed, seed_ctr, sigma);
+  return hipGetLastError();
+}
+
+const void* noise_beside_func() { return reinterpret_cast<const void*>(noise_beside_kernel); }
 
 hipError_t launch_seed_bump(unsigned long long* seed_ctr, long long delta, hipStream_t stream) {
   hipLaunchKernelGGL(bump_kernel, dim3(1), dim3(1), 0, stream, seed_ctr, delta);
@@ -291,23 +369,31 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
 
 constexpr bool kReduceLocal = true;
 
-hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t stream) {
+hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t stream, bool gen_block) {
   const int rows = a.nu * a.H;
   // ~256 blocks of 8 waves in total (1 per CU), each wave streaming one row at a time with 4 16-B loads in flight
   // per lane (same-box sweep over rows x loads x block count on configs #4 and #5: 1 x 4 x 256 best by ~1 %)
   // Enough rows per block to amortise each block's softmin pass over the K costs.
-  int target = 256;
+  const bool nt = (double)a.B * rows * a.Kp * 4.0 > 128.0 * 1024 * 1024;  // noise past what the caches keep
+  // The read-only pass of the overlap route (gen_block) over such a batch -- config #4 at 64 solves, 352 MB -- is
+  // bandwidth-bound with nothing to hide under it: the ticketed form on 512 blocks of 16 waves, two per CU and all
+  // resident in one round, 168 rows each (LOCAL's 1,344 blocks of 64 rows run in 2.6 rounds, each block with its own
+  // softmin prologue and update tail: 68.5 us; ticketed 256 / 512 / 1024 blocks: step 0.5034 / 0.5017 / 0.5107 ms
+  // against LOCAL's 0.5102-0.5165, the kernel 59.1 us at 512 = 6.0 TB/s; same box).  Same bits.
+  const bool wide = gen_block && nt;
+  int target = wide ? 512 : 256;
   if (const char* e = std::getenv("MPPI_REDUCE_BLOCKS")) target = std::max(1, std::atoi(e));  // (A/B knob)
   int rpb = (rows * a.B + target - 1) / target;
   rpb = rpb < 1 ? 1 : rpb;
   // plain solves with enough solves x controls for one u-row per block to fill the chip: block-local update
   // (LOCAL; config #4: 16.9 -> 13.9 us).  Graph streams keep the ticketed form: their next-noise generation wants
   // the wider grid (LOCAL + GEN: step 117.8 -> 120.7 us, same box).
-  const bool local = kReduceLocal && !gen && a.B * a.nu >= 128;
+  // MPPI_REDUCE_LOCAL=0 (read per launch; an A/B knob): the ticketed form where LOCAL would run
+  const int local_knob = env_flag("MPPI_REDUCE_LOCAL");  // (1: LOCAL also where the wide ticketed form would run)
+  const bool local = kReduceLocal && !gen && a.B * a.nu >= 128 && local_knob != 0 && (!wide || local_knob == 1);
   if (local) rpb = a.H;
   const dim3 grid((rows + rpb - 1) / rpb, a.B);
   const size_t lds = (size_t)((a.Kp > a.nu * a.H ? a.Kp : a.nu * a.H) + 40 + (local ? rpb : 0)) * sizeof(float);
-  const bool nt = (double)a.B * rows * a.Kp * 4.0 > 128.0 * 1024 * 1024;  // noise past what the caches keep
   auto kern = gen ? (nt ? reduce_kernel<true, false, true> : reduce_kernel<true, false>)
                   : (local ? (nt ? reduce_kernel<false, true, true> : reduce_kernel<false, true>)
                            : (nt ? reduce_kernel<false, false, true> : reduce_kernel<false, false>));
@@ -317,8 +403,10 @@ hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t st
     if (e != hipSuccess) return e;
   }
   // 16 waves per block for LOCAL (fewer blocks: one per u-row) and for GEN (more waves for the VALU-bound
-  // generation: config #5 step 53.0 -> 52.0 ms, config #4 -0.5 %, same box)
-  hipLaunchKernelGGL(kern, grid, dim3(local || gen ? 1024 : 512), lds, stream, a, rpb,
+  // generation: config #5 step 53.0 -> 52.0 ms, config #4 -0.5 %, same box).  gen_block: the read-only pass of a chained
+  // solve whose next noise is generated beside the rollout keeps GEN's block, so the softmin sum is partitioned over
+  // the same threads and the solve is bit for bit the fused route's whichever route a solve takes
+  hipLaunchKernelGGL(kern, grid, dim3(local || gen || gen_block ? 1024 : 512), lds, stream, a, rpb,
                      gen ? *gen : NoiseGen{nullptr, 0, 0.0f, nullptr});
   return hipGetLastError();
 }

@@ -7,6 +7,7 @@
 namespace mppi {
 
 thread_local const char* g_rollout_kernel = "";
+thread_local const void* g_rollout_func = nullptr;
 
 int current_device_cus() {
   constexpr int kMaxDev = 64;

@@ -72,9 +72,17 @@ __device__ __forceinline__ void split32p(const f32x16& v, bf16x8& hi, bf16x8& lo
 #endif
 }
 
+// Register budget: 248 of a wave's 256 at two waves per SIMD (the compiler doubles amdgpu_num_vgpr's value on this
+// unified-register-file target: 124 -> 248).  Two waves then leave 16 of the SIMD's 512 registers, one wave of the
+// co-resident noise generator (kernels_noise.hip noise_cores_kernel; gen_overlap.h has the fit rule).  The fp16 forms
+// would take 252: the cap costs them 6 spilled registers, every spill and reload in the per-tile setup outside the
+// t-loop, whose instruction counts are those of the uncapped build; the bf16 forms (230-236) are untouched.
+#ifndef MPPI_X3P_NUM_VGPR
+#define MPPI_X3P_NUM_VGPR 124
+#endif
 template <int COST, int L1T>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void fc_wave32_x3p_kernel(SolveArgs a,
-                                                                                                    FcArgs net) {
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+__attribute__((amdgpu_num_vgpr(MPPI_X3P_NUM_VGPR))) void fc_wave32_x3p_kernel(SolveArgs a, FcArgs net) {
   using Y = WaveX3Lay;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const KClock kc = kclock_begin(a);

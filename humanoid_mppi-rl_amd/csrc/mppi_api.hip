@@ -16,6 +16,7 @@
 #include "elite_keep.h"  // (the rule of mppi_set_elite_keep)
 #include "elite_select.h"  // (the rule of mppi_set_elites)
 #include "ess_target.h"  // EssTarget
+#include "gen_overlap.h"  // the rule that routes the next noise beside the rollout
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
 #include "rate_cost.h"  // rate_cost_valid
@@ -150,13 +151,16 @@ struct mppi_handle {
   bool kclock = false;        // stamp rollouts enqueued (or captured) from now on
   bool graph_kclock = false;  // the captured graph stamps its rollouts
   long kclock_launches = 0;   // stamped rollout launches since the last reset
-  // chained solves with the next solve's noise generated CONCURRENTLY with this solve's rollout (gen_overlap): a
-  // low-priority generator stream running noise_kernel + the counter bump, ordered by events against the solve stream
+  // chained solves with the next solve's noise generated CONCURRENTLY with this solve's rollout (gen_overlap.h): a
+  // low-priority generator stream running noise_beside_kernel + the counter bump, ordered by events against the solve
+  // stream
   hipStream_t gstream = nullptr;
   hipEvent_t ev_gen = nullptr;  // the generator's last launch done (the noise the next rollout reads is written)
   hipEvent_t ev_red = nullptr;  // the solve stream's last reduce done (the buffer it read may be overwritten)
   hipEvent_t ev_switch = nullptr;  // mppi_set_stream: the old stream's tail, waited on by the new one
   bool gen_pending = false;     // ev_gen guards the prefetched noise: the solve stream must wait on it before use
+  int gen_route = kGenRouteNone;  // where the last solve's next noise was generated (mppi_gen_route)
+  std::vector<std::pair<const void*, int>> func_regs;  // hipFuncGetAttributes numRegs per kernel, read once each
   const char* rollout_kernel = "";  // the kernel the last solve's rollout was routed to (mppi_rollout_kernel)
   NoiseModel noise_model;  // the sampling law (mppi_set_noise_model); inactive = white noise of cfg.sigma
   // solve diagnostics (MPPI_FLAG_STATS; kernels_stats.hip), allocated by ensure_stats before the first flagged solve or
@@ -739,8 +743,9 @@ int mppi_set_stream(mppi_handle* h, void* s) {
   const hipStream_t ns = s ? (hipStream_t)s : h->own_stream;
   if (ns != h->stream && (h->gen_pending || h->prefetch_valid)) {
     // chained-solve state spans the switch: the next chained solve reads the noise the previous one prefetched, and
-    // (MPPI_GEN_OVERLAP) the generator stream orders itself behind ev_red recorded on the CURRENT stream as "the
-    // previous reduce".  Order the new stream behind everything already on the old one, so that both hold across it.
+    // (with the generator beside the rollout) the generator stream orders itself behind ev_red recorded on the CURRENT
+    // stream as "the previous reduce".  Order the new stream behind everything already on the old one, so that both
+    // hold across it.
     HIP_TRY(hipSetDevice(h->device));
     if (!h->ev_switch) HIP_TRY(hipEventCreateWithFlags(&h->ev_switch, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(h->ev_switch, h->stream));
@@ -1241,10 +1246,27 @@ static hipError_t drop_prefetch(mppi_handle* h) {
 
 // Graph mode (captured streams of solves): this solve's noise is already in `cur` (generated by the previous
 // solve's reduce, or primed by mppi_graph_launch); this solve's reduce writes the next solve's into `next`.
+// overlap (chained solves; chain_iter): the next noise may be drawn BESIDE this solve's rollout on the generator stream,
+// which chain_iter has already ordered behind the previous reduce -- kGenForced: it is; kGenByFit: it is if the routed
+// rollout kernel leaves room for the generator's wave (gen_overlap.h gen_fits), else the reduce draws it as without.
+enum { kGenFused = 0, kGenForced = 1, kGenByFit = 2 };
 struct NoiseStep {
   float* cur;
   float* next;
+  int overlap = kGenFused;
 };
+
+// registers per wave of a kernel of this library (hipFuncGetAttributes, once per kernel and handle; 0: unknown)
+static int func_regs(mppi_handle* h, const void* f) {
+  if (!f) return 0;
+  for (const auto& e : h->func_regs)
+    if (e.first == f) return e.second;
+  hipFuncAttributes at;
+  const int n = hipFuncGetAttributes(&at, f) == hipSuccess ? at.numRegs : 0;
+  if (n <= 0) (void)hipGetLastError();
+  h->func_regs.emplace_back(f, n);
+  return n;
+}
 
 // the options of a solve enqueued (or captured) now with these flags
 static SolveOpts solve_opts(const mppi_handle* h, int flags) {
@@ -1439,13 +1461,37 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   const NoiseGen gen{ns ? ns->next : nullptr, seed, c.sigma, h->d_gticket};
   // an active noise model's rows depend on the row before them, which the fused generators (one row at a time, in
   // reduce order) cannot give: the next noise then comes from its own launch behind the reduce (below)
-  const bool gen_after = ns && ns->next && h->noise_model.active;
-  const NoiseGen* pg = ns && ns->next && !gen_after ? &gen : nullptr;
+  // (ov: the overlap the chain asked for; the analytic cartpole's fused launch generates inside the rollout, whose
+  // registers nobody reads ahead of it: by fit it stays fused)
+  int ov = ns && ns->next ? ns->overlap : kGenFused;
+  if (ov == kGenByFit && (h->dyn_kind == MPPI_DYN_CARTPOLE || h->noise_model.active)) ov = kGenFused;
+  bool gen_after = ns && ns->next && ov != kGenForced && h->noise_model.active;
+  const NoiseGen* pg = ns && ns->next && ov != kGenForced && !gen_after ? &gen : nullptr;
+  // the generator stream's launches, directly behind the rollout's on the host: the next noise into ns->next (the
+  // stream is ordered behind the previous reduce, which read that buffer), then the counter bump -- the generator stream
+  // alone reads and bumps the key counter while the overlap runs, in launch order -- and ev_gen for the next consumer
+  auto gen_beside = [&]() -> int {
+    if (h->noise_model.active)
+      HIP_TRY(launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, h->gstream,
+                                 nullptr, gen_steps(h)));
+    else
+      HIP_TRY(launch_noise_beside(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->gstream));
+    HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->gstream));
+    HIP_TRY(hipEventRecord(h->ev_gen, h->gstream));
+    h->gen_pending = true;
+    // the solve stream waits for it right here, ahead of this solve's reduce (the generator ends well inside the
+    // rollout it runs beside): whatever follows on the stream -- the next solve, a stream switch, a counter read --
+    // finds the noise written and the counter bumped.  Each cross-stream packet costs the stream ~6 us (kernel
+    // trace: 6.5 us between rollout and reduce for this wait, 7.5 us between reduce and rollout for ev_red's record)
+    HIP_TRY(wait_gen(h));
+    return MPPI_OK;
+  };
   float* wcost = a.costs;  // what the search, the reduce and the statistics weigh: the end of the chain below
   if (h->dyn_kind == MPPI_DYN_CARTPOLE && !cart_unfused) {  // one launch: the rollout blocks finish the solve (fused)
     a.part = h->d_part;
     HIP_TRY(timed(h, kRollout, [&] { return launch_cartpole_rollout(a, h->cart, pg, s); }));
     h->rollout_kernel = g_rollout_kernel;
+    if (ov == kGenForced) MPPI_TRY(gen_beside());
   } else {
     // (a targeting cartpole too: its fused epilogue forms the softmin partials with lambda before all costs exist, so
     // it runs the unfused rollout of the env step, a.part == nullptr, then the search and reduce_kernel: 3 launches;
@@ -1453,6 +1499,15 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     // yet, or with elites or kept elites, whose selection needs every cost of the solve)
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
     h->rollout_kernel = g_rollout_kernel;
+    if (ov == kGenByFit) {  // the rule's last condition, on the kernel this very launch was routed to
+      if (gen_fits(func_regs(h, g_rollout_func), func_regs(h, noise_beside_func()))) {
+        ov = kGenForced;
+        pg = nullptr;  // the read-only reduce
+      } else {
+        ov = kGenFused;
+      }
+    }
+    if (ov == kGenForced) MPPI_TRY(gen_beside());
     if (o.ctrl) {
       // the control-cost term, behind the rollout (its costs exist) and ahead of the reduce (a.U is still the nominal the
       // rollout perturbed).  An adapting handle's ctrl_lin_kernel reads d_law on the stream: at this point it still
@@ -1499,7 +1554,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
     SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
     r.costs = wcost;
-    HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s); }));
+    HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s, ov == kGenForced); }));
   }
   // return_best (mppi_set_iterations), the step's last iteration: u0 becomes the first control of the step's best sample
   // -- behind the update and shift (U, the nominal that warm-starts the next step, is untouched), ahead of the clip (so
@@ -1545,6 +1600,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     HIP_TRY(timed(h, kStepAdapt, [&] {
       return enqueue_step_adapt(h, B, stats_slot, (flags & MPPI_FLAG_SHIFT) != 0);
     }));
+  if (ns && ns->next) h->gen_route = ov == kGenForced ? kGenRouteOverlap : kGenRouteFused;
   if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
     HIP_TRY(timed(h, kNoise, [&] {
       return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s,
@@ -1645,16 +1701,20 @@ static int prime_prefetch(mppi_handle* h, int B, uint64_t seed) {
   return MPPI_OK;
 }
 
-// MPPI_GEN_OVERLAP=1 (read per call; default 0, an A/B arm): chained solves generate the next solve's noise on a
-// second, low-priority stream concurrently with this solve's rollout (noise_kernel + counter bump, the plain solves'
-// exact keys), and reduce with the read-only reduce_kernel; default: the next noise comes out of reduce_kernel<GEN>
-// after the rollout.  Same-box A/B (profiles/r04_ab_gen_overlap.log): config #4 at 64 solves 0.4795 / 0.4833 ->
-// 0.4835 / 0.4732 ms per step (the rollout 360 -> 397 us: the generator's Philox VALU lands in the issue-bound
-// rollout, where reduce_kernel<GEN> hides it under its HBM stream), 8 solves 0.1017 -> 0.1037, config #3 0.0530 ->
-// 0.0611, config #2 0.0159 -> 0.0322 (the cross-stream event waits of a short step)
-static bool gen_overlap() {
-  const char* e = std::getenv("MPPI_GEN_OVERLAP");
-  return e && e[0] == '1';
+// Where a chained solve's NEXT noise is generated (gen_overlap.h states the rule and why): beside this solve's rollout,
+// on a second, low-priority stream (noise_beside_kernel + the counter bump, the plain solves' exact keys; the reduce is
+// then the read-only pass), or inside this solve's reduce (reduce_kernel<GEN>) behind the rollout.  The outputs are
+// bitwise the same either way and the routes mix freely from solve to solve.
+// MPPI_GEN_OVERLAP (read per call): 1 forces the overlap (any sampling law: an active noise model's own generator
+// then runs on the second stream), 0 forces the fused route, unset lets the rule decide -- the plain i.i.d. law, a
+// batch whose noise is past gen_size_ok, and a routed rollout kernel that leaves the generator's wave its registers
+// (checked behind the rollout's launch, enqueue_solve).  DESIGN.md section 4 has the measurements that set the rule.
+static int gen_overlap_mode(const mppi_handle* h, int B) {
+  const int force = env_flag("MPPI_GEN_OVERLAP");
+  if (force == 0) return kGenFused;
+  if (force == 1) return kGenForced;
+  const mppi_config& c = h->cfg;
+  return !h->noise_model.active && gen_size_ok(gen_noise_bytes(B, c.nu, c.H, h->Kp)) ? kGenByFit : kGenFused;
 }
 
 static int ensure_gen_stream(mppi_handle* h) {
@@ -1673,36 +1733,26 @@ static int ensure_gen_stream(mppi_handle* h) {
 // one-solve-per-step loops chain on the stream and multi-solve streams replay graphs.
 // chain_iter: one iteration of the step (flags: the iteration's own), its statistics in slot is.it.
 static int chain_iter(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int flags, const IterStep& is) {
-  // (an adapting handle ignores the overlap arm, as a capture does: it would draw the next noise ahead of this
-  // solve's update of the law)
-  const bool overlap = gen_overlap() && !h->capturing && !h->adapt_on && !h->cov_adapt_on && !h->steps_adapt_on;
-  if (!overlap) HIP_TRY(wait_gen(h));  // leaving overlap mode: the solve stream behind the last generator launch
+  // (a capture keeps the fused route: no parallel branches in any graph; an adapting handle too: the overlap would
+  // draw the next noise ahead of this solve's update of the law)
+  const int overlap = h->capturing || h->adapt_on || h->cov_adapt_on || h->steps_adapt_on ? kGenFused
+                                                                                          : gen_overlap_mode(h, B);
+  // the solve stream behind the last generator launch: this solve's noise (buf[p]) and the counter's bump
+  HIP_TRY(wait_gen(h));
   MPPI_TRY(prime_prefetch(h, B, seed));
   float* buf[2] = {h->d_noise, h->d_noise2};
-  if (!overlap) {
-    const NoiseStep ns{buf[h->graph_parity], buf[h->graph_parity ^ 1]};
-    const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns, is.it, &is);
-    if (rc != MPPI_OK) return rc;
-    h->graph_parity ^= 1;  // this solve's reduce prefetched the next one's noise (still key-valid for B, seed)
-    return MPPI_OK;
+  if (overlap != kGenFused) {
+    // the generator stream behind the previous solve's reduce, which read buf[p ^ 1] (everything enqueued so far); its
+    // launches follow the rollout's (enqueue_solve)
+    MPPI_TRY(ensure_gen_stream(h));
+    HIP_TRY(hipEventRecord(h->ev_red, h->stream));
+    HIP_TRY(hipStreamWaitEvent(h->gstream, h->ev_red, 0));
   }
-  MPPI_TRY(ensure_gen_stream(h));
-  const mppi_config& c = h->cfg;
-  // this solve's noise (buf[p]) was written by the previous call's generator launch (or primed on the stream)
-  if (h->gen_pending) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_gen, 0));
-  // the next solve's noise into buf[p ^ 1], once the previous solve's reduce (which read buf[p ^ 1]) is done; the
-  // generator stream alone reads and bumps the key counter from here on, in launch order
-  HIP_TRY(hipEventRecord(h->ev_red, h->stream));  // = the previous reduce (everything enqueued so far)
-  HIP_TRY(hipStreamWaitEvent(h->gstream, h->ev_red, 0));
-  HIP_TRY(launch_noise_model(buf[h->graph_parity ^ 1], B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr, c.sigma,
-                             h->noise_model, h->gstream, nullptr, gen_steps(h)));
-  HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->gstream));
-  HIP_TRY(hipEventRecord(h->ev_gen, h->gstream));
-  h->gen_pending = true;
-  const NoiseStep ns{buf[h->graph_parity], nullptr};  // read-only reduce, no counter bump (the generator owns it)
+  // this solve's reduce, or the generator beside its rollout, prefetches the next one's noise into buf[p ^ 1]
+  const NoiseStep ns{buf[h->graph_parity], buf[h->graph_parity ^ 1], overlap};
   const int rc = enqueue_solve(h, B, io, seed, flags, nullptr, nullptr, &ns, is.it, &is);
   if (rc != MPPI_OK) return rc;
-  h->graph_parity ^= 1;  // the generator prefetched the next one's noise (key-valid for B, seed)
+  h->graph_parity ^= 1;  // (still key-valid for B, seed)
   return MPPI_OK;
 }
 
@@ -1882,6 +1932,25 @@ int mppi_x3_f16(mppi_handle* h, int* on, float* probe_rel_err) {
 }
 
 const char* mppi_rollout_kernel(mppi_handle* h) { return h ? h->rollout_kernel : ""; }
+
+const char* mppi_gen_route(mppi_handle* h) {
+  static const char* const n[3] = {"", "fused", "overlap"};
+  return h ? n[h->gen_route] : "";
+}
+
+int mppi_noise_beside_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out) {
+  if (!h || !noise_out) return fail(MPPI_E_ARG, "mppi_noise_beside_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_noise_beside_eval: B out of range [1, max_batch]");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(drop_prefetch(h));  // d_noise may hold the next chained solve's noise: its key is drawn again
+  hipStream_t s = h->stream;
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)B * c.nu * c.H;
+  HIP_TRY(launch_noise_beside(h->d_noise, B, c.nu, c.H, h->Kp, seed, nullptr, c.sigma, s));
+  HIP_TRY(hipMemcpy2DAsync(noise_out, K * 4, h->d_noise, Kp * 4, K * 4, rows, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MPPI_OK;
+}
 
 int mppi_solve_ex(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int flags) {
   int rc = check_solve(h, B, io, flags);

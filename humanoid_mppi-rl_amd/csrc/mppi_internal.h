@@ -216,7 +216,13 @@ inline int env_choice(const char* name, const char* one, const char* two) {
 // The rollout kernel the last fc / FA / cartpole launch on this host thread routed to (mppi_rollout_kernel): set by
 // every launcher, read by the ABI right after the launch (a handle is used from one thread).
 extern thread_local const char* g_rollout_kernel;
-inline void note_kernel(const char* name) { g_rollout_kernel = name; }
+// ... and its device function where the launcher knows it (fc_launch; nullptr otherwise): the register count of the
+// routed kernel decides whether the next noise can be generated beside it (gen_overlap.h)
+extern thread_local const void* g_rollout_func;
+inline void note_kernel(const char* name) {
+  g_rollout_kernel = name;
+  g_rollout_func = nullptr;
+}
 
 // FeatureAttentionStatePredictor (learning/model.py:48-153) rollout. Blocking shared by the host packer and the
 // kernel: 4 heads; attention is processed in chunks of fa_cw(D) columns (whole heads), the FFN hidden layer in
@@ -272,6 +278,10 @@ struct FaNet {
 hipError_t launch_noise(float* noise, int B, int nu, int H, int Kp, uint64_t seed, const unsigned long long* seed_ctr,
                         float sigma, hipStream_t stream);
 hipError_t launch_seed_bump(unsigned long long* seed_ctr, long long delta, hipStream_t stream);  // += delta
+// the same noise as launch_noise from the kernel built to run beside the rollout (noise_beside_kernel; gen_overlap.h)
+hipError_t launch_noise_beside(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
+                               const unsigned long long* seed_ctr, float sigma, hipStream_t stream);
+const void* noise_beside_func();  // (for hipFuncGetAttributes: the fit rule of gen_overlap.h)
 // The sampling law (mppi_set_noise_model; noise_model.h), a kernel argument by value: no device allocation, so a
 // solve that generates with it stays graph-capturable.  active = 0: the default law (white noise of cfg.sigma, the
 // fused generators); active = 1: eps = sigma_u[u] * AR(1)(rho) from noise_ar1_kernel (kernels_noise.hip), nu <= kMaxNu.
@@ -367,7 +377,8 @@ struct NoiseGen {
   float sigma;
   unsigned* gticket;  // [1], zero between solves
 };
-hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t stream);  // softmin + reduce + update + shift
+hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t stream,  // softmin + reduce + update + shift
+                         bool gen_block = false);  // (gen_block: no generation, reduce_kernel<GEN>'s block size)
 // analytic cartpole rollout; with a.part set it also runs a7-a9 (fused epilogue) and, given gen, writes the next
 // solve's noise (graph streams)
 hipError_t launch_cartpole_rollout(const SolveArgs& a, const CartpoleParams& p, const NoiseGen* gen, hipStream_t stream);

@@ -982,6 +982,8 @@ end
 
 "rollout_kernel: the kernel the last solve was routed to (mppi_rollout_kernel; ABI 3)."
 rollout_kernel(c::Controller) = unsafe_string(ccall((:mppi_rollout_kernel, LIB), Cstring, (Ptr{Cvoid},), c.handle))
+"gen_route: where the last chained solve generated the next solve's noise, \"overlap\" or \"fused\" (mppi_gen_route)."
+gen_route(c::Controller) = unsafe_string(ccall((:mppi_gen_route, LIB), Cstring, (Ptr{Cvoid},), c.handle))
 
 "x3_f16: (form, probe error) of the split CA's fp16 form (mppi_x3_f16; ABI 4): 2 / 1 = on with a one- / two-product last layer, 0 = off."
 function x3_f16(c::Controller)

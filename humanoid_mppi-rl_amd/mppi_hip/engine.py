@@ -900,6 +900,19 @@ class Engine:
         """The kernel the last solve's rollout was routed to (mppi_rollout_kernel)."""
         return (self.lib.mppi_rollout_kernel(self._h) or b"").decode()
 
+    def gen_route(self) -> str:
+        """Where the last chained solve generated the next solve's noise (mppi_gen_route): "overlap" (a second stream,
+        beside the rollout), "fused" (inside the reduce) or "" before the first chained solve."""
+        return (self.lib.mppi_gen_route(self._h) or b"").decode()
+
+    def noise_beside_eval(self, B: int, seed: int) -> np.ndarray:
+        """The noise [B, nu, H, K] (float32) the overlap route's generator draws for the by-value key `seed`
+        (mppi_noise_beside_eval): the default law's, bitwise noise_eval's with no noise model set."""
+        c = self.config
+        out = np.empty((int(B), c.nu, c.H, c.K), np.float32)
+        L.check(self.lib.mppi_noise_beside_eval(self._h, int(B), ctypes.c_uint64(int(seed) & (2**64 - 1)), _ptr(out)))
+        return out
+
     def set_stream(self, stream_handle: int | None):
         L.check(self.lib.mppi_set_stream(self._h, stream_handle))
 

@@ -137,7 +137,10 @@ extern "C" {
  *      mppi_kernel_time.  A handle that never calls the setter, or sets (1, 0, 0), launches exactly the kernels it
  *      launched before, with the same grids and arguments.  BEHAVIOUR while it is on only: injected io.noise with
  *      n_iter > 1 returns MPPI_E_ARG; MPPI_FLAG_U0_BEFORE with n_iter > 1 or with return_best returns
- *      MPPI_E_UNSUPPORTED; the getters that take `step` index iterations (mppi_get_stats). */
+ *      MPPI_E_UNSUPPORTED; the getters that take `step` index iterations (mppi_get_stats).
+ *      Additive, version unchanged: mppi_gen_route / mppi_noise_beside_eval.  BEHAVIOUR (timing only): a chained
+ *      solve may now generate the next solve's noise on a second, low-priority stream beside its rollout (decided per
+ *      solve; MPPI_FLAG_CHAIN below).  Every output, the seed counter included, is bit for bit what it was. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -215,10 +218,13 @@ extern "C" {
 #define MPPI_FLAG_CHAIN 0x100       /* with MPPI_FLAG_DEVICE (MPPI_FLAG_SEED_COUNTER implied): a chained solve, the
                                        stream-launched form of a graph stream -- it uses the noise the previous
                                        chained solve (or graph launch) prefetched and prefetches the next solve's
-                                       inside its reduce (env MPPI_GEN_OVERLAP=1, an A/B arm: on a second,
-                                       low-priority stream concurrently with this solve's rollout); bitwise equal to
-                                       plain counter solves either way.  Injected noise and MPPI_FLAG_COLMAJOR are
-                                       not allowed */
+                                       inside its reduce, or -- where that pays: the plain i.i.d. law, more than
+                                       128 MB of noise per solve batch and a rollout kernel that leaves room in the
+                                       register file; mppi_gen_route reports it -- on a second, low-priority stream
+                                       of the handle's own, beside this solve's rollout (env MPPI_GEN_OVERLAP=0 / 1
+                                       forces either, read per call; captured graphs never use it); bitwise equal
+                                       to plain counter solves either way.  Injected noise and MPPI_FLAG_COLMAJOR
+                                       are not allowed */
 #define MPPI_FLAG_STATS 0x200       /* also compute this solve's diagnostics (mppi_solve_stats and the weighted noise
                                        moments below) on the handle's stream, behind the reduce and before anything
                                        overwrites the solve's noise; read with mppi_get_stats.  Every solve form takes
@@ -1034,6 +1040,13 @@ int mppi_x3_layer1(mppi_handle* h, int* products, float* probe_rel_err);
 /* The rollout kernel the handle's last solve was routed to (e.g. "fc_wave32_x3p_kernel<l1=2>"); "" before the first
  * solve.  Valid until the next solve on the handle. */
 const char* mppi_rollout_kernel(mppi_handle* h);
+/* Where the handle's last chained solve (MPPI_FLAG_CHAIN) generated the next solve's noise: "overlap" (on the handle's
+ * second stream, beside the rollout), "fused" (inside the solve's reduce), "" before the first chained solve. */
+const char* mppi_gen_route(mppi_handle* h);
+/* The noise [B][nu][H][K] the overlap route's generator (noise_beside_kernel) draws for the by-value key `seed`: the
+ * default law's, bit for bit what mppi_noise_eval returns with no noise model set.  Like mppi_noise_eval it drops a
+ * prefetched noise (key sequence unchanged) and needs only mppi_create. */
+int mppi_noise_beside_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out /* [B][nu][H][K] host */);
 /* MPPI_PREC_BF16X3 with a CrossAttention net: *on = 1 if the rollouts run the fp16 form (MPPI_PREC_BF16X3 above) for
  * this handle's horizon, 2 with the opt-in one-product last layer (MPPI_X3_F16_L2=1), 0 if not (also before the first
  * solve); *probe_rel_err = the probe's max relative cost difference between the fp16 form and three products, the
