@@ -11,6 +11,7 @@
 #include "gen_overlap.h"
 #include "mppi_internal.h"
 #include "philox.h"
+#include "population.h"
 #include "wave_reduce.h"
 
 namespace mppi {
@@ -183,7 +184,13 @@ __device__ void update_solve(const SolveArgs& a, int b, float* su /* LDS, >= nu*
 // NT: nontemporal noise loads, for batches whose noise (> 128 MB) no longer sits in L2 / the Infinity Cache after the
 // rollout read it (config #4 at 64 solves: 352 MB; step 0.5017 / 0.5032 -> 0.4918 / 0.4920 ms, same box; 8 solves,
 // 44 MB: no change either way -- round 2 had measured nontemporal loads 2 us slower there)
-template <bool GEN, bool LOCAL, bool NT = false>
+// TWO (population-size decay, mppi_set_population; the extents and predicates: population.h): the next iteration samples
+// another count, so its rows lie at another pitch, gen.Kp_next.  The wave's walk over a row then runs to the longer of
+// the two rows: loads and fmas where q < nq -- the same quads in the same order as without TWO, so the sums are bit for
+// bit those of the one-pitch form -- and generation where q < nq_next, the same counters, key, ticket and nontemporal
+// stores into rows of Kp_next floats.  LDS holds w at the read pitch, as ever.  Without TWO every extent below is the
+// constant it was and the instantiations compile to the code they had.
+template <bool GEN, bool LOCAL, bool NT = false, bool TWO = false>
 __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_block, NoiseGen gen) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* w = smem;                // [max(Kp, nu*H)]
@@ -197,8 +204,13 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
   const int r1 = min(rows, r0 + rows_per_block);
   typedef float f4 __attribute__((ext_vector_type(4)));
   const int nq = a.Kp >> 2;
+  static_assert(!TWO || (GEN && !LOCAL), "the two-pitch form is the fused reduce + generate");
+  const PopWalk walk = pop_walk(a.Kp, TWO ? gen.Kp_next : a.Kp);
+  const int nq_gen = TWO ? walk.nq_next : nq, nq_walk = TWO ? walk.nq_walk : nq;
+  const long gen_pitch = TWO ? (long)gen.Kp_next : (long)a.Kp;
   // each wave streams kRR rows at once, kRU quads per lane in flight per row (kRR * kRU 16-B loads outstanding)
   constexpr int kRR = 1, kRU = 4;
+  static_assert(kRU == kPopTileQuads, "population.h restates the tile");
   f4 e[kRR][kRU];
   auto issue = [&](int r, int q0) {
 #pragma unroll
@@ -232,11 +244,11 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
       const int row = r + i;
       if (row >= r1) continue;
       const int u = row / a.H, t = row - u * a.H;
-      f4* dst = reinterpret_cast<f4*>(gen.next + ((long)b * rows + row) * a.Kp);
+      f4* dst = reinterpret_cast<f4*>(gen.next + ((long)b * rows + row) * gen_pitch);
 #pragma unroll
       for (int j = 0; j < kRU; ++j) {
         const int q = q0 + 64 * j;
-        if (q >= nq) continue;
+        if (q >= nq_gen) continue;
         float z[4];
         philox_normal4((uint32_t)q, (uint32_t)t, (uint32_t)u, (uint32_t)b, gk0, gk1, z);
         __builtin_nontemporal_store(f4{gen.sigma * z[0], gen.sigma * z[1], gen.sigma * z[2], gen.sigma * z[3]},
@@ -285,8 +297,9 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
     float acc[kRR];
 #pragma unroll
     for (int i = 0; i < kRR; ++i) acc[i] = 0.0f;
-    for (int q0 = lane; q0 < nq; q0 += 64 * kRU) {
-      if (r != rfirst || q0 != lane) issue(r, q0);  // (the first tile is already in flight)
+    for (int q0 = lane; q0 < nq_walk; q0 += 64 * kRU) {
+      // (the first tile is already in flight; TWO: past the read row's end there is nothing to load)
+      if ((r != rfirst || q0 != lane) && (!TWO || q0 < nq)) issue(r, q0);
       if constexpr (GEN) generate(r, q0);  // VALU work while the tile's loads are in flight
 #pragma unroll
       for (int j = 0; j < kRU; ++j) {
@@ -394,7 +407,11 @@ hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t st
   if (local) rpb = a.H;
   const dim3 grid((rows + rpb - 1) / rpb, a.B);
   const size_t lds = (size_t)((a.Kp > a.nu * a.H ? a.Kp : a.nu * a.H) + 40 + (local ? rpb : 0)) * sizeof(float);
-  auto kern = gen ? (nt ? reduce_kernel<true, false, true> : reduce_kernel<true, false>)
+  // population-size decay: the next iteration's rows at another pitch take the two-pitch form; equal pitches, as ever,
+  // the one-pitch kernel
+  const bool two = gen && gen->Kp_next != 0 && gen->Kp_next != a.Kp;
+  auto kern = gen ? (two ? (nt ? reduce_kernel<true, false, true, true> : reduce_kernel<true, false, false, true>)
+                         : (nt ? reduce_kernel<true, false, true> : reduce_kernel<true, false>))
                   : (local ? (nt ? reduce_kernel<false, true, true> : reduce_kernel<false, true>)
                            : (nt ? reduce_kernel<false, false, true> : reduce_kernel<false, false>));
   if (lds > 64 * 1024) {
@@ -407,7 +424,7 @@ hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t st
   // solve whose next noise is generated beside the rollout keeps GEN's block, so the softmin sum is partitioned over
   // the same threads and the solve is bit for bit the fused route's whichever route a solve takes
   hipLaunchKernelGGL(kern, grid, dim3(local || gen || gen_block ? 1024 : 512), lds, stream, a, rpb,
-                     gen ? *gen : NoiseGen{nullptr, 0, 0.0f, nullptr});
+                     gen ? *gen : NoiseGen{nullptr, 0, 0.0f, nullptr, 0});
   return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@
 #include "noise_basis.h"  // basis_law_valid
 #include "noise_knots.h"  // knot_table
 #include "noise_model.h"  // ar1_innovation_scale
+#include "population.h"  // the rule of mppi_set_population
 #include "step_law.h"  // StepAdapt
 
 namespace mppi {
@@ -327,6 +328,42 @@ struct mppi_handle {
   float* d_best_U = nullptr;         // [max_batch][nu][H] mppi_iter_best_eval's U (the resident d_U stays as it is)
   int best_B = 0;                    // batch of the last tracking solve / graph launch (0: none ran)
   bool iter_on() const { return iter_n > 1 || iter_best || iter_mean; }
+  // population-size decay (mppi_set_population; population.h).  While pop_n > 0 (== iter_n), iteration i of every
+  // control step draws, rolls out and weighs pop_K[i] samples: enqueue_solve sets `shape` to the iteration's own (K_i,
+  // Kp_i) for as long as it enqueues that iteration, and every helper it calls reads the sample count and the K axis'
+  // pitch from there -- the buffers, sized for cfg.K, are re-read densely at that shape.  Outside enqueue_solve, and
+  // on every handle without a table, shape is (cfg.K, Kp): the *_eval entries stay at cfg.K.  Slot offsets inside a
+  // buffer ([2][max_batch][Kp] and the like) stay those of Kp.
+  int pop_n = 0;  // 0: off (a table whose entries all equal cfg.K is stored as off)
+  int32_t pop_K[kPopMaxIter] = {0};
+  struct Shape {
+    int K, Kp;
+  } shape{0, 0};
+  Shape iter_shape(int it) const {
+    return pop_n > 0 ? Shape{(int)pop_K[it], pop_pitch((int)pop_K[it])} : Shape{cfg.K, Kp};
+  }
+  // the shape of a control step's last iteration: what io.costs / io.weights and the [B][K] read-outs of slot 0 hold
+  Shape last_shape() const { return iter_shape(pop_n > 0 ? pop_n - 1 : 0); }
+  // the kernel iteration `it` of the last control step was routed to (mppi_iter_rollout_kernel)
+  const char* iter_kernel[kPopMaxIter] = {nullptr};
+};
+
+// The shape a [B][K] read-out of output slot `slot` was written at: slot 0 is the last solve's -- with a population
+// table the step's last iteration's, K_last samples at pitch Kp_last -- and every other slot an evaluation's, at cfg.K.
+static mppi_handle::Shape readout_shape(const mppi_handle* h, int slot) {
+  return slot == 0 ? h->last_shape() : mppi_handle::Shape{h->cfg.K, h->Kp};
+}
+
+static int pop_check(const mppi_handle* h, const char* who, int n_iter, int n_elite, int n_keep, int add_mean);
+
+// enqueue_solve's iteration shape on the handle, restored on every way out
+struct ShapeScope {
+  mppi_handle* h;
+  mppi_handle::Shape saved;
+  ShapeScope(mppi_handle* h_, mppi_handle::Shape s) : h(h_), saved(h_->shape) { h->shape = s; }
+  ~ShapeScope() { h->shape = saved; }
+  ShapeScope(const ShapeScope&) = delete;
+  ShapeScope& operator=(const ShapeScope&) = delete;
 };
 
 static hipEvent_t take_event(mppi_handle* h) {
@@ -565,6 +602,7 @@ int mppi_create(const mppi_config* cfg, int device, mppi_handle** out) {
   h->cfg = c;
   h->device = device;
   h->Kp = (c.K + kKpAlign - 1) / kKpAlign * kKpAlign;
+  h->shape = {c.K, h->Kp};
   h->cart = default_cartpole();
   const size_t B = (size_t)c.max_batch;
   auto alloc = [&](void** p, size_t bytes) -> hipError_t {
@@ -976,7 +1014,7 @@ static float* step_m2(const mppi_handle* h, int slot) { return step_m1(h, h->ste
 // solves (d_stats_w holds their weights).
 static hipError_t enqueue_step_mom(mppi_handle* h, int B, const float* noise, int slot) {
   const mppi_config& c = h->cfg;
-  const StepMomArgs sa{B, c.nu, c.H, h->Kp, h->d_stats_w, noise, step_m1(h, slot), step_m2(h, slot)};
+  const StepMomArgs sa{B, c.nu, c.H, h->shape.Kp, h->d_stats_w, noise, step_m1(h, slot), step_m2(h, slot)};
   return launch_step_moments(sa, h->stream);
 }
 
@@ -1045,7 +1083,7 @@ static hipError_t enqueue_stats(mppi_handle* h, int B, const float* costs, const
                                 const float* lambda_dev = nullptr) {
   const mppi_config& c = h->cfg;
   const size_t off = (size_t)slot * c.max_batch;
-  const StatsArgs sa{B, c.nu, c.H, c.K, h->Kp, c.lambda, c.norm_eps, costs, noise, h->d_stats_w, h->d_stats_part,
+  const StatsArgs sa{B, c.nu, c.H, h->shape.K, h->shape.Kp, c.lambda, c.norm_eps, costs, noise, h->d_stats_w, h->d_stats_part,
                      h->d_stats + off, h->d_stats_m2 + off * c.nu, h->d_stats_m11 + off * c.nu, lambda_dev};
   return launch_stats(sa, h->stream);
 }
@@ -1054,7 +1092,7 @@ static hipError_t enqueue_stats(mppi_handle* h, int B, const float* costs, const
 // solves (d_stats_w holds their weights).
 static hipError_t enqueue_cross(mppi_handle* h, int B, const float* noise, int slot) {
   const mppi_config& c = h->cfg;
-  const CrossArgs ca{B, c.nu, c.H, h->Kp, h->d_stats_w, noise, h->d_cross_part,
+  const CrossArgs ca{B, c.nu, c.H, h->shape.Kp, h->d_stats_w, noise, h->d_cross_part,
                      h->d_cross_mx + (size_t)slot * c.max_batch * c.nu * c.nu};
   return launch_cross(ca, h->stream);
 }
@@ -1070,8 +1108,8 @@ static hipError_t enqueue_ctrl(mppi_handle* h, int B, const float* U, const floa
   ca.B = B;
   ca.nu = c.nu;
   ca.H = c.H;
-  ca.K = c.K;
-  ca.Kp = h->Kp;
+  ca.K = h->shape.K;
+  ca.Kp = h->shape.Kp;
   ca.U = U;
   ca.noise = noise;
   ca.costs = costs;
@@ -1100,8 +1138,8 @@ static BoundsArgs bounds_args(const mppi_handle* h, int B, int slot = 0) {
   ba.B = B;
   ba.nu = c.nu;
   ba.H = c.H;
-  ba.K = c.K;
-  ba.Kp = h->Kp;
+  ba.K = h->shape.K;
+  ba.Kp = h->shape.Kp;
   ba.part = h->d_bpart;
   ba.counts = h->d_bcounts + (size_t)slot * c.max_batch * c.nu;
   std::memcpy(ba.lo, h->bounds_lo, sizeof(ba.lo));
@@ -1127,8 +1165,8 @@ static hipError_t enqueue_rate(mppi_handle* h, int B, const float* U, const floa
   ra.B = B;
   ra.nu = c.nu;
   ra.H = c.H;
-  ra.K = c.K;
-  ra.Kp = h->Kp;
+  ra.K = h->shape.K;
+  ra.Kp = h->shape.Kp;
   ra.anchor = h->rate_anchor;
   ra.clamp = c.ctrl_clamp;
   ra.U = U;
@@ -1146,7 +1184,7 @@ static hipError_t enqueue_rate(mppi_handle* h, int B, const float* U, const floa
 static hipError_t enqueue_elite(mppi_handle* h, int B, const float* costs, int slot) {
   const mppi_config& c = h->cfg;
   const size_t ob = (size_t)slot * c.max_batch;
-  return launch_elite_select(costs, B, c.K, h->Kp, h->elite_n, h->d_elite_wcost + ob * h->Kp,
+  return launch_elite_select(costs, B, h->shape.K, h->shape.Kp, h->elite_n, h->d_elite_wcost + ob * h->Kp,
                              h->d_elite_idx + ob * h->elite_n, h->d_elite_count + ob, h->d_elite_tau + ob, h->stream);
 }
 
@@ -1160,8 +1198,8 @@ static KeepArgs keep_args(const mppi_handle* h, int B, const float* U, float* no
   ka.B = B;
   ka.nu = c.nu;
   ka.H = c.H;
-  ka.K = c.K;
-  ka.Kp = h->Kp;
+  ka.K = h->shape.K;
+  ka.Kp = h->shape.Kp;
   ka.n_keep = h->keep_n;
   ka.pitch = keep_pitch(h->keep_n);
   ka.clamp = c.ctrl_clamp;
@@ -1181,14 +1219,13 @@ static KeepArgs keep_args(const mppi_handle* h, int B, const float* U, float* no
 // kernel into the feature's scratch -- then the gather.
 static hipError_t enqueue_keep_store(mppi_handle* h, int B, const float* U, float* noise, const float* costs, int shift,
                                      bool shared, int slot) {
-  const mppi_config& c = h->cfg;
   KeepArgs ka = keep_args(h, B, U, noise, slot);
   ka.costs = costs;
   if (shared) {
     ka.sel_idx = h->d_elite_idx;
     ka.sel_count = h->d_elite_count;
   } else {
-    const hipError_t e = launch_elite_select(costs, B, c.K, h->Kp, h->keep_n, h->d_keep_ecost, h->d_keep_sel,
+    const hipError_t e = launch_elite_select(costs, B, h->shape.K, h->shape.Kp, h->keep_n, h->d_keep_ecost, h->d_keep_sel,
                                              h->d_keep_selcount, h->d_keep_tau, h->stream);
     if (e != hipSuccess) return e;
     ka.sel_idx = h->d_keep_sel;
@@ -1216,6 +1253,9 @@ static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if ((h->dyn_kind == MPPI_DYN_MLP || h->dyn_kind == MPPI_DYN_CROSS_ATTN) && h->net.arch != kArchGeneric &&
       (c.nx > kMaxNx || c.nu > kMaxNu))
     return fail(MPPI_E_UNSUPPORTED, "learned dynamics: nx <= 64, nu <= 32");
+  if (io->noise && h->pop_n > 0)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_solve: injected noise with a mppi_set_population table (the iterations' "
+                                    "sample counts differ)");
   if (io->noise && h->iter_n > 1)
     return fail(MPPI_E_ARG, "mppi_solve: injected noise with mppi_set_iterations n_iter > 1 (one array cannot serve "
                             "every iteration)");
@@ -1338,9 +1378,16 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   const bool resident = (flags & MPPI_FLAG_RESIDENT_U) != 0;
   const bool colmajor = (flags & MPPI_FLAG_COLMAJOR) != 0;
   hipStream_t s = h->stream;
-  const int nx = c.nx, nu = c.nu, H = c.H, K = c.K, Kp = h->Kp;
-  const size_t rowsU = (size_t)B * nu * H;
   const int it = is ? is->it : 0;
+  // population-size decay: this iteration's own sample count and pitch -- every launch below, and every helper through
+  // h->shape, is the solve of a handle created with cfg.K = K; the next iteration's pitch is what the generators of
+  // ns->next write (the step's last iteration is followed by the next step's first: the full pitch).  No table: cfg.K
+  // and h->Kp, all three
+  const mppi_handle::Shape sh = h->iter_shape(it);
+  const ShapeScope shape_scope(h, sh);
+  const int nx = c.nx, nu = c.nu, H = c.H, K = sh.K, Kp = sh.Kp;
+  const int Kp_next = h->iter_shape(is && is->it + 1 < is->n ? is->it + 1 : 0).Kp;
+  const size_t rowsU = (size_t)B * nu * H;
   const bool first = it == 0, last = !is || is->it + 1 == is->n;  // of the control step's iterations
 
   SolveArgs a;
@@ -1458,7 +1505,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   if (o.bounds) HIP_TRY(timed(h, kBounds, [&] { return enqueue_bounds_project(h, B, a.U, a.noise); }));
 
   // ---- a2-a6: rollout + cost; a7-a9: softmin + weighted-noise reduce + update + shift
-  const NoiseGen gen{ns ? ns->next : nullptr, seed, c.sigma, h->d_gticket};
+  const NoiseGen gen{ns ? ns->next : nullptr, seed, c.sigma, h->d_gticket, Kp_next != Kp ? Kp_next : 0};
   // an active noise model's rows depend on the row before them, which the fused generators (one row at a time, in
   // reduce order) cannot give: the next noise then comes from its own launch behind the reduce (below)
   // (ov: the overlap the chain asked for; the analytic cartpole's fused launch generates inside the rollout, whose
@@ -1467,15 +1514,24 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   if (ov == kGenByFit && (h->dyn_kind == MPPI_DYN_CARTPOLE || h->noise_model.active)) ov = kGenFused;
   bool gen_after = ns && ns->next && ov != kGenForced && h->noise_model.active;
   const NoiseGen* pg = ns && ns->next && ov != kGenForced && !gen_after ? &gen : nullptr;
+  // population-size decay, an A/B knob read per launch: MPPI_GEN_TWO_PITCH=0 takes the next noise at another pitch out
+  // of the reduce into a launch of its own behind it (noise_kernel; the reduce keeps GEN's block, so the bits stay);
+  // =shrink / =grow keep the two-pitch form only where the next pitch is the smaller / the larger.  Unset: the
+  // two-pitch form at every such boundary (DESIGN.md section 4 has the measurements)
+  bool two_sep = false;
+  if (pg && Kp_next != Kp) {
+    const int side = env_choice("MPPI_GEN_TWO_PITCH", "shrink", "grow");
+    two_sep = env_flag("MPPI_GEN_TWO_PITCH") == 0 || (side == 1 && Kp_next > Kp) || (side == 2 && Kp_next < Kp);
+  }
   // the generator stream's launches, directly behind the rollout's on the host: the next noise into ns->next (the
   // stream is ordered behind the previous reduce, which read that buffer), then the counter bump -- the generator stream
   // alone reads and bumps the key counter while the overlap runs, in launch order -- and ev_gen for the next consumer
   auto gen_beside = [&]() -> int {
     if (h->noise_model.active)
-      HIP_TRY(launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, h->gstream,
+      HIP_TRY(launch_noise_model(ns->next, B, nu, H, Kp_next, seed, h->d_seed_ctr, c.sigma, h->noise_model, h->gstream,
                                  nullptr, gen_steps(h)));
     else
-      HIP_TRY(launch_noise_beside(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->gstream));
+      HIP_TRY(launch_noise_beside(ns->next, B, nu, H, Kp_next, seed, h->d_seed_ctr, c.sigma, h->gstream));
     HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->gstream));
     HIP_TRY(hipEventRecord(h->ev_gen, h->gstream));
     h->gen_pending = true;
@@ -1490,7 +1546,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   if (h->dyn_kind == MPPI_DYN_CARTPOLE && !cart_unfused) {  // one launch: the rollout blocks finish the solve (fused)
     a.part = h->d_part;
     HIP_TRY(timed(h, kRollout, [&] { return launch_cartpole_rollout(a, h->cart, pg, s); }));
-    h->rollout_kernel = g_rollout_kernel;
+    h->rollout_kernel = h->iter_kernel[it] = g_rollout_kernel;
     if (ov == kGenForced) MPPI_TRY(gen_beside());
   } else {
     // (a targeting cartpole too: its fused epilogue forms the softmin partials with lambda before all costs exist, so
@@ -1498,14 +1554,20 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     // and a cartpole with the control-cost or the rate term, whose epilogue would weigh costs the term has not reached
     // yet, or with elites or kept elites, whose selection needs every cost of the solve)
     HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
-    h->rollout_kernel = g_rollout_kernel;
-    if (ov == kGenByFit) {  // the rule's last condition, on the kernel this very launch was routed to
+    h->rollout_kernel = h->iter_kernel[it] = g_rollout_kernel;
+    if (ov == kGenByFit) {  // the rule's last condition, on the kernel this very launch (this iteration's) was routed to
       if (gen_fits(func_regs(h, g_rollout_func), func_regs(h, noise_beside_func()))) {
         ov = kGenForced;
         pg = nullptr;  // the read-only reduce
       } else {
         ov = kGenFused;
       }
+    }
+    if (two_sep && pg) {  // (the overlap did not take it: the separate launch behind the reduce, below)
+      gen_after = true;
+      pg = nullptr;
+    } else {
+      two_sep = false;
     }
     if (ov == kGenForced) MPPI_TRY(gen_beside());
     if (o.ctrl) {
@@ -1554,7 +1616,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
     SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
     r.costs = wcost;
-    HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s, ov == kGenForced); }));
+    HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s, ov == kGenForced || two_sep); }));
   }
   // return_best (mppi_set_iterations), the step's last iteration: u0 becomes the first control of the step's best sample
   // -- behind the update and shift (U, the nominal that warm-starts the next step, is untouched), ahead of the clip (so
@@ -1603,7 +1665,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   if (ns && ns->next) h->gen_route = ov == kGenForced ? kGenRouteOverlap : kGenRouteFused;
   if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
     HIP_TRY(timed(h, kNoise, [&] {
-      return launch_noise_model(ns->next, B, nu, H, Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, s,
+      return launch_noise_model(ns->next, B, nu, H, Kp_next, seed, h->d_seed_ctr, c.sigma, h->noise_model, s,
                                 gen_law(h), gen_steps(h));
     }));
     HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, s));
@@ -1633,13 +1695,14 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     HIP_TRY(launch_rollout(h, e, s));
   }
 
-  // ---- outputs (the step's last iteration's)
+  // ---- outputs (the step's last iteration's: rows of cfg.K, of which that iteration's K samples are written -- with a
+  // population table the rest of each row is left as the caller holds it)
   if (!last) return MPPI_OK;
   const hipMemcpyKind d2x = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   if (io->costs)
-    HIP_TRY(hipMemcpy2DAsync(io->costs, (size_t)K * 4, h->d_costs, (size_t)Kp * 4, (size_t)K * 4, B, d2x, s));
+    HIP_TRY(hipMemcpy2DAsync(io->costs, (size_t)c.K * 4, h->d_costs, (size_t)Kp * 4, (size_t)K * 4, B, d2x, s));
   if (io->weights)
-    HIP_TRY(hipMemcpy2DAsync(io->weights, (size_t)K * 4, h->d_weights, (size_t)Kp * 4, (size_t)K * 4, B, d2x, s));
+    HIP_TRY(hipMemcpy2DAsync(io->weights, (size_t)c.K * 4, h->d_weights, (size_t)Kp * 4, (size_t)K * 4, B, d2x, s));
   if (io->u0 && !dev) HIP_TRY(hipMemcpyAsync(io->u0, h->d_u0, (size_t)B * nu * 4, d2x, s));
   h->Uhost.clear();
   if (!dev && (!resident || io->U)) {  // (RESIDENT_U with a host io.U: a copy of the resident U)
@@ -1709,12 +1772,13 @@ static int prime_prefetch(mppi_handle* h, int B, uint64_t seed) {
 // then runs on the second stream), 0 forces the fused route, unset lets the rule decide -- the plain i.i.d. law, a
 // batch whose noise is past gen_size_ok, and a routed rollout kernel that leaves the generator's wave its registers
 // (checked behind the rollout's launch, enqueue_solve).  DESIGN.md section 4 has the measurements that set the rule.
-static int gen_overlap_mode(const mppi_handle* h, int B) {
+// Kp_gen: the pitch of the noise to generate (the next iteration's: mppi_set_population)
+static int gen_overlap_mode(const mppi_handle* h, int B, int Kp_gen) {
   const int force = env_flag("MPPI_GEN_OVERLAP");
   if (force == 0) return kGenFused;
   if (force == 1) return kGenForced;
   const mppi_config& c = h->cfg;
-  return !h->noise_model.active && gen_size_ok(gen_noise_bytes(B, c.nu, c.H, h->Kp)) ? kGenByFit : kGenFused;
+  return !h->noise_model.active && gen_size_ok(gen_noise_bytes(B, c.nu, c.H, Kp_gen)) ? kGenByFit : kGenFused;
 }
 
 static int ensure_gen_stream(mppi_handle* h) {
@@ -1735,8 +1799,10 @@ static int ensure_gen_stream(mppi_handle* h) {
 static int chain_iter(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, int flags, const IterStep& is) {
   // (a capture keeps the fused route: no parallel branches in any graph; an adapting handle too: the overlap would
   // draw the next noise ahead of this solve's update of the law)
-  const int overlap = h->capturing || h->adapt_on || h->cov_adapt_on || h->steps_adapt_on ? kGenFused
-                                                                                          : gen_overlap_mode(h, B);
+  const int Kp_gen = h->iter_shape(is.it + 1 < is.n ? is.it + 1 : 0).Kp;
+  const int overlap = h->capturing || h->adapt_on || h->cov_adapt_on || h->steps_adapt_on
+                          ? kGenFused
+                          : gen_overlap_mode(h, B, Kp_gen);
   // the solve stream behind the last generator launch: this solve's noise (buf[p]) and the counter's bump
   HIP_TRY(wait_gen(h));
   MPPI_TRY(prime_prefetch(h, B, seed));
@@ -1790,6 +1856,10 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
 // each: the CA surrogate's dynamics do not depend on the controls (its action encoder never reaches the output), so
 // the form's error is one number per state -- more states, not more samples, find the worst.  For the same reason the
 // probe keeps its own white noise of cfg.sigma whatever mppi_set_noise_model selected: it is a per-state measure.
+// With a population table (mppi_set_population) the iterations of a step run at several shapes, each routed by fc_route
+// on its own (B, Kp_i).  The probe is not per shape and needs no second run: it decides per loaded net and cost, on
+// min(Kp, 64) samples of the full population, by routes of its own (above) -- the two kernels of the fp16 form whatever
+// the batch -- so one decision covers whichever of x3p, x3h and the M-split kernel an iteration is routed to.
 static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
   if (h->dyn_kind != MPPI_DYN_CROSS_ATTN || h->cfg.precision != MPPI_PREC_BF16X3 || h->net.arch != kArchCA ||
       h->net.x3_l1 != 0)
@@ -2819,8 +2889,9 @@ int mppi_get_control_cost(mppi_handle* h, float* gamma) {
 static int copy_ctrl(mppi_handle* h, int B, int slot, float* term, float* lin) {
   const mppi_config& c = h->cfg;
   const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, rows = (size_t)c.nu * c.H;
+  const mppi_handle::Shape sh = readout_shape(h, slot);  // (rows of cfg.K, of which the solve's K samples are written)
   if (term)
-    HIP_TRY(hipMemcpy2D(term, K * 4, h->d_term + (size_t)slot * c.max_batch * Kp, Kp * 4, K * 4, B,
+    HIP_TRY(hipMemcpy2D(term, K * 4, h->d_term + (size_t)slot * c.max_batch * Kp, (size_t)sh.Kp * 4, (size_t)sh.K * 4, B,
                         hipMemcpyDeviceToHost));
   if (lin)
     HIP_TRY(hipMemcpy(lin, h->d_lin + (size_t)slot * c.max_batch * rows, (size_t)B * rows * 4, hipMemcpyDeviceToHost));
@@ -3027,8 +3098,9 @@ int mppi_get_prev_control(mppi_handle* h, int B, float* u_prev) {
 // slot `slot` of the rate term -> host (the stream is idle)
 static int copy_rate(mppi_handle* h, int B, int slot, float* term) {
   const size_t K = (size_t)h->cfg.K, Kp = (size_t)h->Kp;
-  HIP_TRY(hipMemcpy2D(term, K * 4, h->d_rate_term + (size_t)slot * h->cfg.max_batch * Kp, Kp * 4, K * 4, B,
-                      hipMemcpyDeviceToHost));
+  const mppi_handle::Shape sh = readout_shape(h, slot);  // (rows of cfg.K, of which the solve's K samples are written)
+  HIP_TRY(hipMemcpy2D(term, K * 4, h->d_rate_term + (size_t)slot * h->cfg.max_batch * Kp, (size_t)sh.Kp * 4,
+                      (size_t)sh.K * 4, B, hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 
@@ -3067,6 +3139,7 @@ int mppi_set_elites(mppi_handle* h, int n_elite) {
   const mppi_config& c = h->cfg;
   if (n_elite < 0 || n_elite > c.K) return fail(MPPI_E_ARG, "mppi_set_elites: n_elite must be in [0, K] (0 disables)");
   if (n_elite == h->elite_n) return MPPI_OK;  // no change: captured graphs stay
+  MPPI_TRY(pop_check(h, "mppi_set_elites", h->iter_n, n_elite, h->keep_n, h->iter_mean));
   HIP_TRY(hipSetDevice(h->device));
   // stale state: the captured graphs hold n_elite (or the selection's absence) in their launches, and the set's rows
   // have n_elite entries; everything in flight finishes first.  A prefetched noise is kept: the selection does not
@@ -3104,8 +3177,10 @@ static int copy_elites(mppi_handle* h, int B, int slot, int32_t* idx, int32_t* c
     HIP_TRY(hipMemcpy(idx, h->d_elite_idx + ob * h->elite_n, (size_t)B * h->elite_n * 4, hipMemcpyDeviceToHost));
   if (count) HIP_TRY(hipMemcpy(count, h->d_elite_count + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
   if (tau) HIP_TRY(hipMemcpy(tau, h->d_elite_tau + ob, (size_t)B * 4, hipMemcpyDeviceToHost));
+  const mppi_handle::Shape sh = readout_shape(h, slot);  // (rows of cfg.K, of which the solve's K samples are written)
   if (ecost)
-    HIP_TRY(hipMemcpy2D(ecost, K * 4, h->d_elite_wcost + ob * Kp, Kp * 4, K * 4, B, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(ecost, K * 4, h->d_elite_wcost + ob * Kp, (size_t)sh.Kp * 4, (size_t)sh.K * 4, B,
+                        hipMemcpyDeviceToHost));
   return MPPI_OK;
 }
 
@@ -3138,6 +3213,7 @@ int mppi_set_elite_keep(mppi_handle* h, int n_keep) {
   const mppi_config& c = h->cfg;
   if (n_keep < 0 || n_keep > c.K) return fail(MPPI_E_ARG, "mppi_set_elite_keep: n_keep must be in [0, K] (0 disables)");
   if (n_keep == h->keep_n) return MPPI_OK;  // no change: captured graphs and the stored set stay
+  MPPI_TRY(pop_check(h, "mppi_set_elite_keep", h->iter_n, h->elite_n, n_keep, h->iter_mean));
   HIP_TRY(hipSetDevice(h->device));
   // stale state: the captured graphs hold n_keep (or the feature's absence) in their launches, and the set's rows have
   // n_keep entries; everything in flight finishes first.  A prefetched noise is kept: the injection happens in the
@@ -3306,6 +3382,16 @@ int mppi_keep_inject_eval(mppi_handle* h, int B, const float* U, const float* no
   return MPPI_OK;
 }
 
+// A population table in effect (mppi_set_population) against the settings a setter is about to make: the one check
+// (population.h pop_validate) that mppi_set_population itself runs, so the refusal holds in either order of the calls.
+static int pop_check(const mppi_handle* h, const char* who, int n_iter, int n_elite, int n_keep, int add_mean) {
+  if (h->pop_n == 0) return MPPI_OK;
+  const int e = pop_validate(h->pop_K, h->pop_n, h->cfg.K, n_iter, n_elite, n_keep, add_mean);
+  if (e == kPopOk) return MPPI_OK;
+  return fail(MPPI_E_ARG, std::string(who) + ": against the mppi_set_population table in effect, " + pop_error_text(e) +
+                              " (call mppi_set_population(h, NULL, 0) first)");
+}
+
 // The tracking's buffers (mppi_set_iterations, mppi_iter_best_eval): allocated once, never inside a solve.
 static int ensure_iter(mppi_handle* h) {
   if (h->d_best_v) return MPPI_OK;
@@ -3324,6 +3410,7 @@ int mppi_set_iterations(mppi_handle* h, int n_iter, int return_best, int add_mea
   if ((return_best != 0 && return_best != 1) || (add_mean != 0 && add_mean != 1))
     return fail(MPPI_E_ARG, "mppi_set_iterations: return_best and add_mean must be 0 or 1");
   if (n_iter == h->iter_n && return_best == h->iter_best && add_mean == h->iter_mean) return MPPI_OK;  // graphs stay
+  MPPI_TRY(pop_check(h, "mppi_set_iterations", n_iter, h->elite_n, h->keep_n, add_mean));
   HIP_TRY(hipSetDevice(h->device));
   // stale state: the captured graphs hold the iteration structure in their launches; everything in flight finishes
   // first.  A prefetched noise is kept: the key sequence does not depend on the setting
@@ -3342,6 +3429,53 @@ int mppi_get_iterations(mppi_handle* h, int* n_iter, int* return_best, int* add_
   if (return_best) *return_best = h->iter_best;
   if (add_mean) *add_mean = h->iter_mean;
   return MPPI_OK;
+}
+
+int mppi_set_population(mppi_handle* h, const int32_t* K_it, int n) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_population: null handle");
+  if (!K_it && n != 0) return fail(MPPI_E_ARG, "mppi_set_population: NULL (off) goes with n == 0");
+  int32_t tab[kPopMaxIter] = {0};
+  int tn = 0;
+  if (K_it) {
+    const int e = pop_validate(K_it, n, h->cfg.K, h->iter_n, h->elite_n, h->keep_n, h->iter_mean);
+    if (e != kPopOk) return fail(MPPI_E_ARG, std::string("mppi_set_population: ") + pop_error_text(e));
+    if (!pop_is_off(K_it, n, h->cfg.K)) {  // (every entry cfg.K: the feature off, stored as such)
+      tn = n;
+      std::memcpy(tab, K_it, (size_t)n * sizeof(int32_t));
+    }
+  }
+  if (tn == h->pop_n && std::memcmp(tab, h->pop_K, sizeof(tab)) == 0) return MPPI_OK;  // in effect: graphs, prefetch stay
+  HIP_TRY(hipSetDevice(h->device));
+  // stale state, as in mppi_set_noise_model: the captured graphs hold every iteration's shape in their launches (a
+  // launch still in flight finishes first), and a prefetched noise is dropped (the counter steps back: the key sequence
+  // is unchanged).  Nothing is allocated: every buffer was sized for cfg.K and is re-read at the iterations' shapes
+  HIP_TRY(drop_prefetch(h));
+  MPPI_TRY(drop_graphs(h, true));
+  h->pop_n = tn;
+  std::memcpy(h->pop_K, tab, sizeof(tab));
+  // the [B][K] read-outs of the last solve lie at the old table's last shape: none to read until the next solve
+  h->ctrl_B = h->rate_B = h->elite_B = 0;
+  return MPPI_OK;
+}
+
+int mppi_get_population(mppi_handle* h, int32_t* K_it, int* n) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_population: null handle");
+  if (K_it)
+    for (int i = 0; i < kPopMaxIter; ++i) K_it[i] = i < h->pop_n ? h->pop_K[i] : 0;
+  if (n) *n = h->pop_n;
+  return MPPI_OK;
+}
+
+int mppi_population_icem(int K, int n_iter, double gamma, int k_min, int32_t* K_it) {
+  if (!K_it) return fail(MPPI_E_ARG, "mppi_population_icem: null argument");
+  if (pop_icem(K, n_iter, gamma, k_min, K_it) != 0)
+    return fail(MPPI_E_ARG, "mppi_population_icem: need gamma >= 1, 1 <= k_min <= K and n_iter in [1, 16]");
+  return MPPI_OK;
+}
+
+const char* mppi_iter_rollout_kernel(mppi_handle* h, int it) {
+  if (!h || it < 0 || it >= h->iter_n || !h->iter_kernel[it]) return "";
+  return h->iter_kernel[it];
 }
 
 // slot `slot` of the stored best -> host (the stream is idle); each pointer may be nullptr

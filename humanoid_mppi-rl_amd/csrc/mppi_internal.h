@@ -376,6 +376,9 @@ struct NoiseGen {
   uint64_t seed;
   float sigma;
   unsigned* gticket;  // [1], zero between solves
+  // the pitch of `next`'s rows where it differs from the pitch the reduce reads (mppi_set_population: the next
+  // iteration samples another count); 0: the read pitch.  Last, so no other field moves
+  int Kp_next = 0;
 };
 hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t stream,  // softmin + reduce + update + shift
                          bool gen_block = false);  // (gen_block: no generation, reduce_kernel<GEN>'s block size)

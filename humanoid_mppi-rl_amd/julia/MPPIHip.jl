@@ -920,6 +920,38 @@ function iterations(c::Controller)
 end
 
 """
+    set_population!(c, schedule)
+
+A sample count per inner iteration (mppi_set_population; iCEM's shrinking budget): iteration `i` of every control step
+draws, rolls out and weighs `schedule[i]` samples, bit for bit the solve of a controller created with `K = schedule[i]`.
+`length(schedule)` must equal `n_iter` of `set_iterations!`, `schedule[1] == K`, every entry in `1:K` and at least
+`n_elite` and `n_keep` (`n_keep + 1` with `add_mean`).  `nothing` turns it off; `K` throughout is the feature off.  Any
+change destroys captured graphs.
+"""
+function set_population!(c::Controller, schedule::Union{Nothing, AbstractVector{<:Integer}})
+    if schedule === nothing
+        check(ccall((:mppi_set_population, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint), c.handle, C_NULL, 0))
+        return c
+    end
+    tab = Vector{Int32}(schedule)
+    GC.@preserve tab check(ccall((:mppi_set_population, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint), c.handle,
+                                 pointer(tab), length(tab)))
+    return c
+end
+
+"""
+    population(c) -> Union{Nothing, Vector{Int}}
+
+The schedule of `set_population!` (mppi_get_population); `nothing` while it is off.
+"""
+function population(c::Controller)
+    tab, n = zeros(Int32, 16), Ref{Cint}(0)
+    GC.@preserve tab check(ccall((:mppi_get_population, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ref{Cint}), c.handle,
+                                 pointer(tab), n))
+    return n[] == 0 ? nothing : Int.(tab[1:n[]])
+end
+
+"""
     best(c) -> (v::Matrix{Float32}, cost::Float32, k::Int, iter::Int)
 
 The best sampled control sequence of the last control step made with `set_iterations!` on (mppi_get_best; waits for

@@ -42,7 +42,8 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_get_noise_basis", "mppi_set_noise_steps", "mppi_get_noise_steps", "mppi_set_noise_steps_adapt",
             "mppi_get_noise_steps_adapt", "mppi_get_step_moments", "mppi_step_moments_eval", "mppi_set_iterations",
             "mppi_get_iterations", "mppi_get_best", "mppi_iter_best_eval", "mppi_gen_route",
-            "mppi_noise_beside_eval"]
+            "mppi_noise_beside_eval", "mppi_set_population", "mppi_get_population", "mppi_population_icem",
+            "mppi_iter_rollout_kernel"]
 
 
 class MPPIError(RuntimeError):
@@ -183,6 +184,10 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_get_iterations": (i32, [vp] + [ctypes.POINTER(i32)] * 3),
         "mppi_get_best": (i32, [vp, i32, vp, vp, vp, vp]),
         "mppi_iter_best_eval": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "mppi_set_population": (i32, [vp, vp, i32]),
+        "mppi_get_population": (i32, [vp, vp, ctypes.POINTER(i32)]),
+        "mppi_population_icem": (i32, [i32, i32, ctypes.c_double, i32, vp]),
+        "mppi_iter_rollout_kernel": (ctypes.c_char_p, [vp, i32]),
         "mppi_kernel_clock_read": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_double)]),
     }

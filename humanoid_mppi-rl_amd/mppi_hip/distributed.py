@@ -282,7 +282,8 @@ def combine_k_shards(costs: np.ndarray, dU_r: np.ndarray, lam: float, norm_eps: 
 
 
 def solve_k_sharded(solve_shard: Callable, x0: np.ndarray, U: np.ndarray, lam: float, update: str = "add",
-                    U_clamp: float = 0.0, norm_eps: float = 0.0, shift_fill: float | None = None, group=None):
+                    U_clamp: float = 0.0, norm_eps: float = 0.0, shift_fill: float | None = None, group=None,
+                    engine=None):
     """One MPPI solve whose K samples are spread over the ranks (each rank draws its own K/world samples).
 
     solve_shard(x0, U) -> (costs [K_r], dU_r [nu, H]) runs this rank's shard (e.g. Engine.solve on an engine created
@@ -291,7 +292,17 @@ def solve_k_sharded(solve_shard: Callable, x0: np.ndarray, U: np.ndarray, lam: f
     when shift_fill is given (src/cartpole_mppi.py:96-106, src/mppi.jl:91-98).  Returns (U_new, u0).
 
     K-sharded solves keep the default sampling law (white noise of one sigma): the shards' engines are not given a
-    noise model (Engine.set_noise_model) here."""
+    noise model (Engine.set_noise_model) here.
+
+    engine: the shard's Engine, when the caller has one to name (a bound Engine method as solve_shard names it by
+    itself).  An engine with a population table on (Engine.set_population) is refused, MPPI_E_UNSUPPORTED, before
+    anything runs: its costs are the last iteration's K_last samples and its iterations' dU are not one weighted sum
+    over K_r, so the combine below has no meaning for it (decay across K-sharded ranks is not built)."""
+    eng = engine if engine is not None else getattr(solve_shard, "__self__", None)
+    if eng is not None and callable(getattr(eng, "population", None)) and eng.population() is not None:
+        from ._lib import MPPI_E_UNSUPPORTED, MPPIError
+        raise MPPIError(MPPI_E_UNSUPPORTED, "solve_k_sharded: the shard's engine has a population table on "
+                                            "(Engine.set_population): decay across K-sharded ranks is not supported")
     costs, dU_r = solve_shard(x0, U)
     dU = combine_k_shards(costs, dU_r, lam, norm_eps, group)
     Un = dU if update == "replace" else np.asarray(U, np.float64) + dU

@@ -690,6 +690,37 @@ class Engine:
                                              _ptr(v), _ptr(cost), _ptr(k), _ptr(bi)))
         return v, cost, k, bi
 
+    # -- population-size decay (mppi_set_population; mppi_hip.stats.icem_population computes iCEM's schedule)
+    def set_population(self, schedule):
+        """A sample count per inner iteration (mppi_set_population; iCEM's shrinking budget): iteration i of every control
+        step draws, rolls out and weighs schedule[i] samples and is bit for bit the solve of an engine created with
+        K = schedule[i], the state handed over from iteration to iteration.  len(schedule) must equal n_iter of
+        set_iterations, schedule[0] == K, every entry in [1, K] and >= n_elite, n_keep (n_keep + 1 with add_mean).
+        None turns it off; a schedule of K throughout is the feature off.  costs / weights of a solve and the [B, K]
+        read-outs then hold the last iteration's samples in their first schedule[-1] entries per row.  Any change
+        destroys captured graphs and drops a prefetched noise (key sequence unchanged)."""
+        if schedule is None:
+            L.check(self.lib.mppi_set_population(self._h, None, 0))
+            return self
+        tab = np.ascontiguousarray(np.asarray(schedule, np.int64).reshape(-1))
+        if tab.size and (np.abs(tab) >= 2**31).any():
+            raise ValueError("set_population: entries must fit int32")
+        tab = tab.astype(np.int32)
+        L.check(self.lib.mppi_set_population(self._h, _ptr(tab), int(tab.size)))
+        return self
+
+    def population(self):
+        """The schedule of set_population as a tuple of ints, or None while it is off (mppi_get_population)."""
+        tab = np.zeros(16, np.int32)
+        n = ctypes.c_int(0)
+        L.check(self.lib.mppi_get_population(self._h, _ptr(tab), ctypes.byref(n)))
+        return tuple(int(v) for v in tab[: n.value]) if n.value else None
+
+    def iter_rollout_kernel(self, it: int) -> str:
+        """The kernel iteration `it` of the last control step's rollout was routed to (mppi_iter_rollout_kernel); ""
+        outside [0, n_iter) or before any solve."""
+        return (self.lib.mppi_iter_rollout_kernel(self._h, int(it)) or b"").decode()
+
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,
               want_costs: bool = True, want_weights: bool = False, colmajor: bool = False,

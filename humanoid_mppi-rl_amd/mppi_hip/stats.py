@@ -1010,3 +1010,22 @@ def iter_best_ref(U, noise, costs, it: int = 0, stored=None, ctrl_clamp: float =
                 s = (np.fmin(clamp, np.fmax(-clamp, s)) + (s - s)).astype(np.float32)
             v[b] = s
     return (v[0], cost[0], k[0], bi[0]) if single else (v, cost, k, bi)
+
+
+def icem_population(K: int, n_iter: int, gamma: float, k_min: int) -> np.ndarray:
+    """iCEM's sample budget per inner iteration, N_i = max(N / gamma^i, k_min), as mppi_population_icem computes it
+    (csrc/population.h pop_icem) -> int32 [n_iter], the table Engine.set_population takes:
+
+        d = 1.0;  for i < n_iter:  K_it[i] = max(k_min, int(K / d));  d *= gamma
+
+    in double, a division, a truncation and a product per entry -- correctly rounded operations only, no pow -- so the
+    table equals the C helper's on any host.  ValueError unless gamma >= 1, 1 <= k_min <= K and 1 <= n_iter <= 16."""
+    K, n_iter, k_min, gamma = int(K), int(n_iter), int(k_min), float(gamma)
+    if not gamma >= 1.0 or K < 1 or k_min < 1 or k_min > K or n_iter < 1 or n_iter > 16:
+        raise ValueError("icem_population: need gamma >= 1, 1 <= k_min <= K and n_iter in [1, 16]")
+    out = np.empty(n_iter, np.int32)
+    d = 1.0
+    for i in range(n_iter):
+        out[i] = max(k_min, int(float(K) / d))
+        d *= gamma
+    return out

@@ -138,6 +138,12 @@ extern "C" {
  *      launched before, with the same grids and arguments.  BEHAVIOUR while it is on only: injected io.noise with
  *      n_iter > 1 returns MPPI_E_ARG; MPPI_FLAG_U0_BEFORE with n_iter > 1 or with return_best returns
  *      MPPI_E_UNSUPPORTED; the getters that take `step` index iterations (mppi_get_stats).
+ *      Additive, version unchanged: mppi_set_population / mppi_get_population / mppi_population_icem /
+ *      mppi_iter_rollout_kernel (population-size decay: a sample count per inner iteration, iCEM's shrinking budget, in
+ *      every stream form).  A handle that never calls the setter, or sets a table whose entries all equal cfg.K,
+ *      launches exactly the kernels it launched before, with the same grids and arguments.  BEHAVIOUR while a table is on
+ *      only: mppi_set_iterations, mppi_set_elites and mppi_set_elite_keep return MPPI_E_ARG for a change the table does
+ *      not admit; io.costs / io.weights and the [B][K] read-outs hold the step's last iteration's samples (below).
  *      Additive, version unchanged: mppi_gen_route / mppi_noise_beside_eval.  BEHAVIOUR (timing only): a chained
  *      solve may now generate the next solve's noise on a second, low-priority stream beside its rollout (decided per
  *      solve; MPPI_FLAG_CHAIN below).  Every output, the seed counter included, is bit for bit what it was. */
@@ -968,6 +974,43 @@ int mppi_get_best(mppi_handle* h, int B, float* v /* [B][nu][H] */, float* cost 
 int mppi_iter_best_eval(mppi_handle* h, int B, const float* U /* [B][nu][H] host */,
                         const float* noise /* [B][nu][H][K] host */, const float* costs /* [B][K] host */, int reset,
                         int it, float* v, float* cost, int32_t* k, int32_t* iter /* in/out */);
+
+/* Population-size decay (iCEM's sample budget, N_i = max(N / gamma^i, k_min)): K_it[i] is the number of samples
+ * iteration i of every control step draws, rolls out and weighs.  The table is explicit: the ABI carries no
+ * floating-point rule; mppi_population_icem computes iCEM's.  The rule is csrc/population.h (host + device).
+ * THE DEFINITION.  With a table on, iteration i of a control step is, bit for bit, the solve that a handle created with
+ * cfg.K = K_it[i] and everything else equal would run: the same stream form, the same state, ctx and flags (all but
+ * the last iteration without MPPI_FLAG_SHIFT and MPPI_FLAG_ENV_STEP), the same noise key -- the seed counter advances
+ * by one per iteration, as without a table -- and the state iteration i - 1 left handed over: U, the kept set, the
+ * per-step scale table, u_prev, the adapted laws.  Philox counters are (k / 4, t, u, b) and do not depend on the row
+ * pitch, so iteration i sees the first K_it[i] columns of its key's noise, at pitch Kp_i = K_it[i] rounded up to 64.
+ * It follows that the rollout kernel is routed per iteration on (B, Kp_i) (mppi_iter_rollout_kernel), the ESS target is
+ * a fraction of K_it[i], the statistics, moments and lambda slots of iteration i describe K_it[i] samples, and the
+ * best sample's k indexes that iteration's samples.  io.costs / io.weights and the [B][K] read-outs without per-step
+ * slots (mppi_get_control_term, mppi_get_rate_term, the masked costs of the elites) are the step's LAST iteration's:
+ * the row pitch stays cfg.K, the first K_last = K_it[n - 1] entries of each row are written and the rest are left
+ * untouched; the device costs of mppi_device_buffers lie at pitch Kp_last.  The *_eval entries stay at cfg.K.
+ * Every buffer was sized for cfg.K and is re-read densely at the iteration's shape: no kernel's addressing changes.
+ * In chained and captured streams the next iteration's noise is drawn inside this iteration's reduce at the next
+ * iteration's pitch (the two-pitch form of the fused reduce + generate; equal pitches take the one-pitch kernel).
+ * mppi_set_population(K_it, n): MPPI_E_ARG, nothing changed, unless n equals the handle's n_iter
+ * (mppi_set_iterations), K_it[0] == cfg.K, every K_it[i] is in [1, cfg.K], and n_elite, n_keep and -- with add_mean --
+ * n_keep + 1 are <= every K_it[i]; mppi_set_iterations, mppi_set_elites and mppi_set_elite_keep refuse (MPPI_E_ARG) a
+ * change that would break these while a table is on.  (NULL, 0) turns it off; a table whose entries all equal cfg.K IS
+ * the feature off: the same branches, arguments and launches.  Any change destroys captured graphs and drops a
+ * prefetched noise as mppi_set_noise_model does (the key sequence is unchanged) and forgets the last solve's [B][K]
+ * read-outs; a call with the table already in effect is a no-op that keeps all of them.  Nothing is allocated, here or
+ * inside a solve.  Injected io.noise with a table on returns MPPI_E_UNSUPPORTED.
+ * mppi_get_population: K_it [16] (entries behind n are 0) and n, 0 while off; each pointer may be NULL.
+ * mppi_population_icem: d = 1.0; for i < n_iter: K_it[i] = max(k_min, (int)(K / d)); d *= gamma -- in double, only
+ * correctly rounded operations (no pow), so mppi_hip.stats.icem_population is exact on any host.  Needs gamma >= 1,
+ * 1 <= k_min <= K and n_iter in 1..16, else MPPI_E_ARG.  No handle.
+ * mppi_iter_rollout_kernel: the kernel iteration `it` of the last control step enqueued (or captured) was routed to;
+ * "" for it outside [0, n_iter) or before any solve.  With or without a table. */
+int mppi_set_population(mppi_handle* h, const int32_t* K_it /* [n] host, or NULL: off */, int n);
+int mppi_get_population(mppi_handle* h, int32_t* K_it /* [16] or NULL */, int* n /* 0 while off */);
+int mppi_population_icem(int K, int n_iter, double gamma, int k_min, int32_t* K_it /* [n_iter] */);
+const char* mppi_iter_rollout_kernel(mppi_handle* h, int it);
 
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
