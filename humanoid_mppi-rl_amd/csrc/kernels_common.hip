@@ -12,6 +12,7 @@
 #include "mppi_internal.h"
 #include "philox.h"
 #include "population.h"
+#include "reduce_regen.h"
 #include "wave_reduce.h"
 
 namespace mppi {
@@ -25,10 +26,13 @@ namespace mppi {
 // last block for a plain solve, in bump_kernel right behind a graph's prefetched noise (mppi_api.hip).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void noise_kernel(float* __restrict__ noise, int rows, int nu, int H, int Kp,
-                                                    uint64_t seed, const unsigned long long* seed_ctr, float sigma) {
+                                                    uint64_t seed, const unsigned long long* seed_ctr, float sigma,
+                                                    unsigned long long* key_out) {
   const int row = blockIdx.z * 65535 + blockIdx.y;  // (b*nu + u)*H + t
   const int kq = blockIdx.x * 256 + threadIdx.x;
   const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+  // the key travels with the buffer (reduce_regen.h): one lane of one block
+  if (key_out && row == 0 && kq == 0) *key_out = key;
   if (row < rows && 4 * kq < Kp) {
     const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
     const int t = row % H;
@@ -46,10 +50,10 @@ __global__ __launch_bounds__(256) void noise_kernel(float* __restrict__ noise, i
 __global__ void bump_kernel(unsigned long long* seed_ctr, long long delta) { *seed_ctr += (unsigned long long)delta; }
 
 hipError_t launch_noise(float* noise, int B, int nu, int H, int Kp, uint64_t seed, const unsigned long long* seed_ctr,
-                        float sigma, hipStream_t stream) {
+                        float sigma, hipStream_t stream, unsigned long long* key_out) {
   const int rows = B * nu * H;
   const dim3 grid((Kp / 4 + 255) / 256, rows < 65535 ? rows : 65535, (rows + 65534) / 65535);
-  hipLaunchKernelGGL(noise_kernel, grid, dim3(256), 0, stream, noise, rows, nu, H, Kp, seed, seed_ctr, sigma);
+  hipLaunchKernelGGL(noise_kernel, grid, dim3(256), 0, stream, noise, rows, nu, H, Kp, seed, seed_ctr, sigma, key_out);
   return hipGetLastError();
 }
 
@@ -69,11 +73,13 @@ hipError_t launch_noise(float* noise, int B, int nu, int H, int Kp, uint64_t see
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kGenWave) __attribute__((amdgpu_num_vgpr(kGenVgprs / 2)))  // (the target doubles it)
 void noise_beside_kernel(float* __restrict__ noise, int rows, int nu, int H, int Kp, int rpb, uint64_t seed,
-                         const unsigned long long* seed_ctr, float sigma) {
+                         const unsigned long long* seed_ctr, float sigma, unsigned long long* key_out) {
   const int r0 = blockIdx.x * rpb;
   const int nr = min(rpb, rows - r0);
   if (nr <= 0) return;
   const uint64_t key = seed + (seed_ctr ? *seed_ctr : 0ull);
+  // the key travels with the buffer (reduce_regen.h): one lane of one block, ahead of the loop's registers
+  if (key_out && blockIdx.x == 0 && threadIdx.x == 0) *key_out = key;
   const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
   const int bu = r0 / H;
   uint32_t t = (uint32_t)(r0 - bu * H), u = (uint32_t)(bu % nu), b = (uint32_t)(bu / nu);
@@ -118,13 +124,14 @@ int gen_rows_per_block() {
 }
 
 hipError_t launch_noise_beside(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
-                               const unsigned long long* seed_ctr, float sigma, hipStream_t stream) {
+                               const unsigned long long* seed_ctr, float sigma, hipStream_t stream,
+                               unsigned long long* key_out) {
   const long rows = (long)B * nu * H;
   const int rpb = gen_rows_per_block();
   // (a lane's offset in its block's rows is 32-bit; so is the grid)
   if (rows > 0x7fffffffL || (long)rpb * Kp * 4 > 0x7fffffffL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(noise_beside_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(kGenWave), 0, stream, noise,
-                     (int)rows, nu, H, Kp, rpb, seed, seed_ctr, sigma);
+                     (int)rows, nu, H, Kp, rpb, seed, seed_ctr, sigma, key_out);
   return hipGetLastError();
 }
 
@@ -190,8 +197,17 @@ __device__ void update_solve(const SolveArgs& a, int b, float* su /* LDS, >= nu*
 // bit those of the one-pitch form -- and generation where q < nq_next, the same counters, key, ticket and nontemporal
 // stores into rows of Kp_next floats.  LDS holds w at the read pitch, as ever.  Without TWO every extent below is the
 // constant it was and the instantiations compile to the code they had.
-template <bool GEN, bool LOCAL, bool NT = false, bool TWO = false>
-__global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_block, NoiseGen gen) {
+// REGEN (the read-only forms; the rule: reduce_regen.h): gen.regen eighths of the quads the pass would read are computed
+// instead, gen.sigma * philox_normal4(q, t, u, b, *gen.regen_key) -- what the generator of this very noise stored, bit
+// for bit -- into the registers the loads would have filled.  A row's tile loads its first slots, as ever, and computes
+// its last regen_row_quads -- by the rule none or all of them: whole rows read, whole rows computed, other waves of the
+// SIMD streaming meanwhile; the fmas over e and w follow in the one order there is.  Without REGEN the instantiations
+// compile to the code they had.
+// Its wide form holds two blocks of 16 waves per CU only at 64 registers or fewer: REGEN asks the compiler for 8 waves
+// per SIMD (the others keep the 4 a block of 1,024 implies, and with it their code).
+template <bool GEN, bool LOCAL, bool NT = false, bool TWO = false, bool REGEN = false>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(REGEN ? 8 : 4)))
+void reduce_kernel(SolveArgs a, int rows_per_block, NoiseGen gen) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* w = smem;                // [max(Kp, nu*H)]
   float* red = smem + (a.Kp > a.nu * a.H ? a.Kp : a.nu * a.H);  // [40] scratch (2 per wave + the arrival flag)
@@ -211,10 +227,16 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
   // each wave streams kRR rows at once, kRU quads per lane in flight per row (kRR * kRU 16-B loads outstanding)
   constexpr int kRR = 1, kRU = 4;
   static_assert(kRU == kPopTileQuads, "population.h restates the tile");
+  static_assert(!(GEN && REGEN), "the fused reduce + generate has its vector ALUs taken");
+  static_assert(!REGEN || (kRR == 1 && kRU == kRegenTileQuads), "reduce_regen.h restates the tile");
   f4 e[kRR][kRU];
-  auto issue = [&](int r, int q0) {
+  // (nre: the tile slots of row r that are regenerated, not loaded; wave-uniform, 0 without REGEN)
+  auto issue = [&](int r, int q0, int nre) {
 #pragma unroll
     for (int j = 0; j < kRU; ++j) {
+      if constexpr (REGEN) {
+        if (regen_slot(nre, j)) continue;
+      }
       const int q = min(q0 + 64 * j, nq - 1);
 #pragma unroll
       for (int i = 0; i < kRR; ++i) {
@@ -230,13 +252,32 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
   };
   // the first tile of this wave's first rows does not depend on the weights: in flight during the softmin pass
   const int rfirst = r0 + wv * kRR;
-  if (rfirst < r1) issue(rfirst, lane);
+  // REGEN: a wave's place in the alternation of an odd share, stepped from one of its rows to the next
+  int alt = wv;
+  if (rfirst < r1) issue(rfirst, lane, REGEN ? regen_row_quads(gen.regen, alt) : 0);
   uint32_t gk0 = 0, gk1 = 0;
   if constexpr (GEN) {
     const uint64_t key = gen.seed + *a.seed_ctr;
     gk0 = (uint32_t)key;
     gk1 = (uint32_t)(key >> 32);
   }
+  if constexpr (REGEN) {  // the key THIS noise was drawn with, as its generator recorded it
+    const uint64_t key = *gen.regen_key;
+    gk0 = (uint32_t)key;
+    gk1 = (uint32_t)(key >> 32);
+  }
+  // the tile's last nre slots of row r (quads q0 + 64 j) computed into e, beside the loads of its first ones
+  auto regenerate = [&](int r, int q0, int nre) {
+    const int u = r / a.H, t = r - u * a.H;
+#pragma unroll
+    for (int j = 0; j < kRU; ++j) {
+      const int q = q0 + 64 * j;
+      if (!regen_slot(nre, j) || q >= nq) continue;
+      float z[4];
+      philox_normal4((uint32_t)q, (uint32_t)t, (uint32_t)u, (uint32_t)b, gk0, gk1, z);
+      e[0][j] = f4{gen.sigma * z[0], gen.sigma * z[1], gen.sigma * z[2], gen.sigma * z[3]};
+    }
+  };
   // next solve's noise for the tile (rows r, r+1; quads q0 + 64 j)
   auto generate = [&](int r, int q0) {
 #pragma unroll
@@ -293,14 +334,16 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
   }
 
   const f4* w4 = reinterpret_cast<const f4*>(w);
-  for (int r = rfirst; r < r1; r += nw * kRR) {
+  for (int r = rfirst; r < r1; r += nw * kRR, ++alt) {
     float acc[kRR];
 #pragma unroll
     for (int i = 0; i < kRR; ++i) acc[i] = 0.0f;
+    const int nre = REGEN ? regen_row_quads(gen.regen, alt) : 0;
     for (int q0 = lane; q0 < nq_walk; q0 += 64 * kRU) {
       // (the first tile is already in flight; TWO: past the read row's end there is nothing to load)
-      if ((r != rfirst || q0 != lane) && (!TWO || q0 < nq)) issue(r, q0);
+      if ((r != rfirst || q0 != lane) && (!TWO || q0 < nq)) issue(r, q0, nre);
       if constexpr (GEN) generate(r, q0);  // VALU work while the tile's loads are in flight
+      if constexpr (REGEN) regenerate(r, q0, nre);  // likewise
 #pragma unroll
       for (int j = 0; j < kRU; ++j) {
         if (q0 + 64 * j < nq) {
@@ -374,7 +417,10 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
     if constexpr (GEN) {  // every block of every solve has read the counter: advance it once
       if (__hip_atomic_fetch_add(gen.gticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1) {
         __hip_atomic_store(gen.gticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        atomicAdd(a.seed_ctr, 1ull);
+        const unsigned long long ctr = atomicAdd(a.seed_ctr, 1ull);
+        // the key travels with the buffer it was drawn into (reduce_regen.h): the counter every block read, from the
+        // one lane that advances it
+        if (gen.key_out) *gen.key_out = gen.seed + ctr;
       }
     }
   }
@@ -382,8 +428,12 @@ __global__ __launch_bounds__(1024) void reduce_kernel(SolveArgs a, int rows_per_
 
 constexpr bool kReduceLocal = true;
 
-hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t stream, bool gen_block) {
+hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t stream, bool gen_block,
+                         const RegenArgs* regen) {
   const int rows = a.nu * a.H;
+  // the read-only forms that regenerate a share of what they would read (reduce_regen.h; the caller applied the rule)
+  const bool re = regen && regen->eighths > 0;
+  if (re && (gen || !regen->key || regen->eighths > kRegenMaxEighths)) return hipErrorInvalidValue;
   // ~256 blocks of 8 waves in total (1 per CU), each wave streaming one row at a time with 4 16-B loads in flight
   // per lane (same-box sweep over rows x loads x block count on configs #4 and #5: 1 x 4 x 256 best by ~1 %)
   // Enough rows per block to amortise each block's softmin pass over the K costs.
@@ -414,6 +464,10 @@ hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t st
                          : (nt ? reduce_kernel<true, false, true> : reduce_kernel<true, false>))
                   : (local ? (nt ? reduce_kernel<false, true, true> : reduce_kernel<false, true>)
                            : (nt ? reduce_kernel<false, false, true> : reduce_kernel<false, false>));
+  if (re)
+    kern = local ? (nt ? reduce_kernel<false, true, true, false, true> : reduce_kernel<false, true, false, false, true>)
+                 : (nt ? reduce_kernel<false, false, true, false, true>
+                       : reduce_kernel<false, false, false, false, true>);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds);
@@ -423,8 +477,13 @@ hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t st
   // generation: config #5 step 53.0 -> 52.0 ms, config #4 -0.5 %, same box).  gen_block: the read-only pass of a chained
   // solve whose next noise is generated beside the rollout keeps GEN's block, so the softmin sum is partitioned over
   // the same threads and the solve is bit for bit the fused route's whichever route a solve takes
-  hipLaunchKernelGGL(kern, grid, dim3(local || gen || gen_block ? 1024 : 512), lds, stream, a, rpb,
-                     gen ? *gen : NoiseGen{nullptr, 0, 0.0f, nullptr, 0});
+  NoiseGen g = gen ? *gen : NoiseGen{nullptr, 0, 0.0f, nullptr, 0};
+  if (re) {
+    g.sigma = regen->sigma;
+    g.regen = regen->eighths;
+    g.regen_key = regen->key;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(local || gen || gen_block ? 1024 : 512), lds, stream, a, rpb, g);
   return hipGetLastError();
 }
 

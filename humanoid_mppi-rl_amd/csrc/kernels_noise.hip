@@ -566,8 +566,9 @@ static int ar1_knob() {
 
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
                               const unsigned long long* seed_ctr, float sigma, const NoiseModel& model,
-                              hipStream_t stream, const float* d_law, const float* d_steps) {
-  if (!model.active) return launch_noise(noise, B, nu, H, Kp, seed, seed_ctr, sigma, stream);
+                              hipStream_t stream, const float* d_law, const float* d_steps,
+                              unsigned long long* key_out) {
+  if (!model.active) return launch_noise(noise, B, nu, H, Kp, seed, seed_ctr, sigma, stream, key_out);
   if (nu > kMaxNu) return hipErrorInvalidValue;  // (mppi_set_noise_model refuses such a handle)
   const int nbu = B * nu, nq = Kp / 4;
   // a table of per-step scales (mppi_set_noise_steps refuses it beside every law below but sigma_u and rho)

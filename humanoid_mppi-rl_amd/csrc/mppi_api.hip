@@ -17,6 +17,7 @@
 #include "elite_select.h"  // (the rule of mppi_set_elites)
 #include "ess_target.h"  // EssTarget
 #include "gen_overlap.h"  // the rule that routes the next noise beside the rollout
+#include "reduce_regen.h"  // the rule by which the read-only reduce regenerates part of the noise it sums
 #include "fc_route.h"  // fc_route, x3_l1_terms, kX3ProbeTol (the split CA's probe)
 #include "mppi_internal.h"
 #include "rate_cost.h"  // rate_cost_valid
@@ -161,6 +162,16 @@ struct mppi_handle {
   hipEvent_t ev_switch = nullptr;  // mppi_set_stream: the old stream's tail, waited on by the new one
   bool gen_pending = false;     // ev_gen guards the prefetched noise: the solve stream must wait on it before use
   int gen_route = kGenRouteNone;  // where the last solve's next noise was generated (mppi_gen_route)
+  // The reduce that regenerates part of the noise it reads (reduce_regen.h).  d_nkey [2]: the key each noise buffer
+  // (d_noise, d_noise2) was drawn with, written on the device by the kernel that drew it.  pristine [2], the content side
+  // of the rule, kept on the host: the buffer holds exactly what the plain i.i.d. generator wrote for that key, for B
+  // solves at pitch Kp -- set where such a generator is enqueued, cleared wherever anything else writes the buffer
+  unsigned long long* d_nkey = nullptr;
+  struct Pristine {
+    bool ok = false;
+    int B = 0, Kp = 0;
+  } pristine[2];
+  int reduce_regen = 0;  // the eighths the last solve's reduce regenerated (mppi_reduce_regen)
   std::vector<std::pair<const void*, int>> func_regs;  // hipFuncGetAttributes numRegs per kernel, read once each
   const char* rollout_kernel = "";  // the kernel the last solve's rollout was routed to (mppi_rollout_kernel)
   NoiseModel noise_model;  // the sampling law (mppi_set_noise_model); inactive = white noise of cfg.sigma
@@ -567,7 +578,7 @@ void mppi_destroy(mppi_handle* h) {
                   h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
                   h->d_keep_idx, h->d_keep_count, h->d_keep_steps, h->d_keep_sel, h->d_keep_selcount, h->d_keep_tau,
                   h->d_keep_ecost, h->d_keep_U, h->d_steps, h->d_step_mom, h->d_best_v, h->d_best_cost, h->d_best_k,
-                  h->d_best_iter, h->d_best_U};
+                  h->d_best_iter, h->d_best_U, h->d_nkey};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
@@ -622,6 +633,7 @@ int mppi_create(const mppi_config* cfg, int device, mppi_handle** out) {
   if (e == hipSuccess) e = alloc((void**)&h->d_status, 16);
   if (e == hipSuccess) e = alloc((void**)&h->d_tickets, B * 4);
   if (e == hipSuccess) e = alloc((void**)&h->d_seed_ctr, 8);
+  if (e == hipSuccess) e = alloc((void**)&h->d_nkey, 16);
   if (e == hipSuccess) e = alloc((void**)&h->d_env_noise, B * c.nu * kKpAlign * 4);
   if (e == hipSuccess) e = alloc((void**)&h->d_env_costs, B * kKpAlign * 4);
   if (e == hipSuccess) e = alloc((void**)&h->d_env_status, 16);
@@ -1278,6 +1290,8 @@ static hipError_t launch_rollout(mppi_handle* h, const SolveArgs& a, hipStream_t
 // stepped back so the next consumer draws exactly the key the prefetch took: the key sequence of any interleaving
 // of plain solves and graph launches equals a loop of plain solves.
 static hipError_t drop_prefetch(mppi_handle* h) {
+  // (every caller goes on to write d_noise, or to draw the buffers again: nothing is pristine until a generator says so)
+  h->pristine[0].ok = h->pristine[1].ok = false;
   if (const hipError_t e = wait_gen(h); e != hipSuccess) return e;
   if (!h->prefetch_valid) return hipSuccess;
   h->prefetch_valid = false;
@@ -1295,6 +1309,26 @@ struct NoiseStep {
   float* next;
   int overlap = kGenFused;
 };
+
+// reduce_regen.h's content side.  noise_slot: which of the pair a noise pointer is; noise_drawn: a generator was enqueued
+// that writes all of it for B solves at pitch Kp with the key word beside it (plain: noise_kernel, noise_beside_kernel
+// or reduce_kernel<GEN>, the three that evaluate one function); noise_written: anything else wrote into it.  A capture
+// records launches that run later, any number of times: it leaves the host's view alone, and mppi_graph_launch clears it
+static int noise_slot(const mppi_handle* h, const float* noise) { return h->d_noise2 && noise == h->d_noise2 ? 1 : 0; }
+static void noise_drawn(mppi_handle* h, const float* noise, bool plain, int B, int Kp) {
+  if (h->capturing) return;
+  mppi_handle::Pristine& p = h->pristine[noise_slot(h, noise)];
+  p.ok = plain;
+  p.B = B;
+  p.Kp = Kp;
+}
+static void noise_written(mppi_handle* h, const float* noise) {
+  if (!h->capturing) h->pristine[noise_slot(h, noise)].ok = false;
+}
+static bool noise_pristine(const mppi_handle* h, const float* noise, int B, int Kp) {
+  const mppi_handle::Pristine& p = h->pristine[noise_slot(h, noise)];
+  return !h->capturing && p.ok && p.Kp == Kp && p.B >= B;
+}
 
 // registers per wave of a kernel of this library (hipFuncGetAttributes, once per kernel and handle; 0: unknown)
 static int func_regs(mppi_handle* h, const void* f) {
@@ -1409,6 +1443,8 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   a.cost_kind = h->cost_kind;
   std::memcpy(a.ctx_default, h->cost_params, sizeof(a.ctx_default));
   a.noise = ns ? ns->cur : h->d_noise;
+  // the device word beside a noise buffer: the key its generator records there (reduce_regen.h)
+  auto key_word = [&](const float* noise) { return h->d_nkey + noise_slot(h, noise); };
   a.costs = h->d_costs;
   a.dU = h->d_dU;
   a.weights = io->weights ? h->d_weights : nullptr;
@@ -1473,11 +1509,13 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     }
     MPPI_TRY(stage_noise(h, src, rowsU, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
     if (!tmp.empty()) HIP_TRY(hipStreamSynchronize(s));
+    noise_written(h, a.noise);
   } else if (!ns) {
     HIP_TRY(timed(h, kNoise, [&] {
       return launch_noise_model(a.noise, B, nu, H, Kp, seed, a.seed_ctr, c.sigma, h->noise_model, s, gen_law(h),
-                                gen_steps(h));
+                                gen_steps(h), key_word(a.noise));
     }));
+    noise_drawn(h, a.noise, !h->noise_model.active, B, Kp);
   }
 
   // keep / shift elites: the stored set into the first columns of this solve's noise, behind whatever filled it -- the
@@ -1487,7 +1525,10 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // the bounds projection and the rollout.  The x3 probe runs before any of this with buffers of its own and the env
   // step reads d_env_noise: neither sees the injection.  count and steps are read on the device: the launch is there
   // for every solve of a handle with the feature on and changes nothing while the set is empty
-  if (o.keep) HIP_TRY(timed(h, kKeep, [&] { return launch_keep_inject(keep_args(h, B, a.U, a.noise, 0), s); }));
+  if (o.keep) {
+    HIP_TRY(timed(h, kKeep, [&] { return launch_keep_inject(keep_args(h, B, a.U, a.noise, 0), s); }));
+    noise_written(h, a.noise);
+  }
 
   // add_mean (mppi_set_iterations), the step's last iteration: the column behind the carried set zeroed, so the nominal
   // itself is one of the candidates -- behind the injection (which never writes that column) and ahead of the bounds
@@ -1497,15 +1538,25 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       return launch_iter_mean(a.noise, o.keep ? h->d_keep_count : nullptr, h->keep_n, B, nu, H, K, Kp, s);
     }, iter_count));
     iter_count = 0;
+    noise_written(h, a.noise);
   }
 
   // per-actuator bounds: the solve's noise -- drawn above, prefetched by the previous solve's generator, or the copy of
   // an injected io.noise (never the caller's array) -- projected in place against the nominal U, ahead of the rollout
   // and of every other reader of this solve's noise
-  if (o.bounds) HIP_TRY(timed(h, kBounds, [&] { return enqueue_bounds_project(h, B, a.U, a.noise); }));
+  if (o.bounds) {
+    HIP_TRY(timed(h, kBounds, [&] { return enqueue_bounds_project(h, B, a.U, a.noise); }));
+    noise_written(h, a.noise);
+  }
+  // the reduce may regenerate part of this solve's noise instead of reading it (reduce_regen.h): the content side, now
+  // that everything that writes a.noise ahead of the rollout is enqueued, and the knob (read per launch)
+  const bool regen_ok = noise_pristine(h, a.noise, B, Kp);
+  const int regen_force = regen_knob(std::getenv("MPPI_REDUCE_REGEN"));
+  h->reduce_regen = 0;
 
   // ---- a2-a6: rollout + cost; a7-a9: softmin + weighted-noise reduce + update + shift
-  const NoiseGen gen{ns ? ns->next : nullptr, seed, c.sigma, h->d_gticket, Kp_next != Kp ? Kp_next : 0};
+  const NoiseGen gen{ns ? ns->next : nullptr, seed, c.sigma, h->d_gticket, Kp_next != Kp ? Kp_next : 0,
+                     ns && ns->next ? key_word(ns->next) : nullptr};
   // an active noise model's rows depend on the row before them, which the fused generators (one row at a time, in
   // reduce order) cannot give: the next noise then comes from its own launch behind the reduce (below)
   // (ov: the overlap the chain asked for; the analytic cartpole's fused launch generates inside the rollout, whose
@@ -1531,7 +1582,9 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       HIP_TRY(launch_noise_model(ns->next, B, nu, H, Kp_next, seed, h->d_seed_ctr, c.sigma, h->noise_model, h->gstream,
                                  nullptr, gen_steps(h)));
     else
-      HIP_TRY(launch_noise_beside(ns->next, B, nu, H, Kp_next, seed, h->d_seed_ctr, c.sigma, h->gstream));
+      HIP_TRY(launch_noise_beside(ns->next, B, nu, H, Kp_next, seed, h->d_seed_ctr, c.sigma, h->gstream,
+                                  key_word(ns->next)));
+    noise_drawn(h, ns->next, !h->noise_model.active, B, Kp_next);
     HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->gstream));
     HIP_TRY(hipEventRecord(h->ev_gen, h->gstream));
     h->gen_pending = true;
@@ -1547,6 +1600,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     a.part = h->d_part;
     HIP_TRY(timed(h, kRollout, [&] { return launch_cartpole_rollout(a, h->cart, pg, s); }));
     h->rollout_kernel = h->iter_kernel[it] = g_rollout_kernel;
+    if (pg) noise_written(h, ns->next);  // (its generator records no key)
     if (ov == kGenForced) MPPI_TRY(gen_beside());
   } else {
     // (a targeting cartpole too: its fused epilogue forms the softmin partials with lambda before all costs exist, so
@@ -1568,6 +1622,14 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       pg = nullptr;
     } else {
       two_sep = false;
+    }
+    // a forced share (MPPI_REDUCE_REGEN=1..7) reaches the fused route too, by the same separation: the next noise in a
+    // launch of its own behind the reduce, which keeps GEN's block and becomes a read-only form (the rule by itself
+    // leaves the fused routes alone: their vector ALUs are taken, or their reduce is latency-bound)
+    bool regen_sep = false;
+    if (pg && regen_force > 0 && regen_ok) {
+      regen_sep = gen_after = true;
+      pg = nullptr;
     }
     if (ov == kGenForced) MPPI_TRY(gen_beside());
     if (o.ctrl) {
@@ -1616,7 +1678,14 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       HIP_TRY(timed(h, kLambda, [&] { return launch_lambda_search(wcost, B, K, Kp, h->ess, c.lambda, lam, s); }));
     SolveArgs r = a;  // the reduce's arguments: a's, weighing wcost
     r.costs = wcost;
-    HIP_TRY(timed(h, kReduce, [&] { return launch_reduce(r, pg, s, ov == kGenForced || two_sep); }));
+    // the share of its noise the reduce regenerates: none for the fused reduce + generate
+    const RegenArgs rg{pg ? 0 : regen_share(regen_ok, regen_noise_bytes(B, nu, H, Kp), regen_force), key_word(a.noise),
+                       c.sigma};
+    HIP_TRY(timed(h, kReduce, [&] {
+      return launch_reduce(r, pg, s, ov == kGenForced || two_sep || regen_sep, rg.eighths ? &rg : nullptr);
+    }));
+    h->reduce_regen = rg.eighths;
+    if (pg) noise_drawn(h, ns->next, true, B, Kp_next);  // reduce_kernel<GEN> drew it, key word included
   }
   // return_best (mppi_set_iterations), the step's last iteration: u0 becomes the first control of the step's best sample
   // -- behind the update and shift (U, the nominal that warm-starts the next step, is untouched), ahead of the clip (so
@@ -1666,9 +1735,10 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   if (gen_after) {  // the overlap arm's key and counter protocol, on the solve stream: noise with seed + counter, bump
     HIP_TRY(timed(h, kNoise, [&] {
       return launch_noise_model(ns->next, B, nu, H, Kp_next, seed, h->d_seed_ctr, c.sigma, h->noise_model, s,
-                                gen_law(h), gen_steps(h));
+                                gen_law(h), gen_steps(h), key_word(ns->next));
     }));
     HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, s));
+    noise_drawn(h, ns->next, !h->noise_model.active, B, Kp_next);
   }
 
   // ---- env step: x0 <- f(x0, u0), the rollout kernel over one sample, one step, zero noise, U = u0, final
@@ -1755,9 +1825,11 @@ static int prime_prefetch(mppi_handle* h, int B, uint64_t seed) {
   if (h->prefetch_valid && (h->prefetch_B != B || h->prefetch_seed != seed)) HIP_TRY(drop_prefetch(h));
   if (h->prefetch_valid) return MPPI_OK;
   const mppi_config& c = h->cfg;
-  HIP_TRY(launch_noise_model(h->graph_parity ? h->d_noise2 : h->d_noise, B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr,
-                             c.sigma, h->noise_model, h->stream, gen_law(h), gen_steps(h)));
+  float* const buf = h->graph_parity ? h->d_noise2 : h->d_noise;
+  HIP_TRY(launch_noise_model(buf, B, c.nu, c.H, h->Kp, seed, h->d_seed_ctr, c.sigma, h->noise_model, h->stream,
+                             gen_law(h), gen_steps(h), h->d_nkey + noise_slot(h, buf)));
   HIP_TRY(launch_seed_bump(h->d_seed_ctr, 1, h->stream));
+  noise_drawn(h, buf, !h->noise_model.active, B, h->Kp);
   h->prefetch_valid = true;
   h->prefetch_B = B;
   h->prefetch_seed = seed;
@@ -2003,6 +2075,8 @@ int mppi_x3_f16(mppi_handle* h, int* on, float* probe_rel_err) {
 
 const char* mppi_rollout_kernel(mppi_handle* h) { return h ? h->rollout_kernel : ""; }
 
+int mppi_reduce_regen(mppi_handle* h) { return h ? h->reduce_regen : 0; }
+
 const char* mppi_gen_route(mppi_handle* h) {
   static const char* const n[3] = {"", "fused", "overlap"};
   return h ? n[h->gen_route] : "";
@@ -2138,6 +2212,7 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
   // first launch (or after plain solves / a counter reset / chained solves of another batch): generate the noise
   MPPI_TRY(prime_prefetch(h, h->graph_B, h->graph_seed));
   HIP_TRY(hipGraphLaunch(h->graph_exec[h->graph_parity], h->stream));
+  h->pristine[0].ok = h->pristine[1].ok = false;  // (the replay wrote both buffers; the host followed none of it)
   if (h->graph_kclock) h->kclock_launches += h->graph_n;
   note_ran(h, h->graph_opts, h->graph_B, h->graph_n);
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise

@@ -275,12 +275,15 @@ struct FaNet {
 
 // Launchers (return hipSuccess or the launch error). All enqueue on `stream` only.
 // device noise into noise[B][nu][H][Kp]; seed_ctr (or nullptr): device key offset
+// key_out (or nullptr): the device word that receives the key the noise was drawn with, seed + *seed_ctr, written by
+// one lane of one block (reduce_regen.h: the reduce that regenerates part of this noise reads the key from there)
 hipError_t launch_noise(float* noise, int B, int nu, int H, int Kp, uint64_t seed, const unsigned long long* seed_ctr,
-                        float sigma, hipStream_t stream);
+                        float sigma, hipStream_t stream, unsigned long long* key_out = nullptr);
 hipError_t launch_seed_bump(unsigned long long* seed_ctr, long long delta, hipStream_t stream);  // += delta
 // the same noise as launch_noise from the kernel built to run beside the rollout (noise_beside_kernel; gen_overlap.h)
 hipError_t launch_noise_beside(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
-                               const unsigned long long* seed_ctr, float sigma, hipStream_t stream);
+                               const unsigned long long* seed_ctr, float sigma, hipStream_t stream,
+                               unsigned long long* key_out = nullptr);
 const void* noise_beside_func();  // (for hipFuncGetAttributes: the fit rule of gen_overlap.h)
 // The sampling law (mppi_set_noise_model; noise_model.h), a kernel argument by value: no device allocation, so a
 // solve that generates with it stays graph-capturable.  active = 0: the default law (white noise of cfg.sigma, the
@@ -315,10 +318,12 @@ constexpr int basis_rows_padded(int R) { return (R + 3) / 4 * 4; }  // rows of b
 // device memory instead of the by-value model (noise_ar1_dev_kernel / noise_ar1_lds_dev_kernel).  d_steps (or nullptr):
 // the table of per-step scales S [B][nu][H] of mppi_set_noise_steps (device memory the setter owns, moved on the stream
 // by step_adapt_kernel) -- the same two generators reading their scale per step from it, rho and c from the model
-// (noise_ar1_steps_kernel / noise_ar1_lds_steps_kernel); never beside d_law, a knot law, a basis or a covariance
+// (noise_ar1_steps_kernel / noise_ar1_lds_steps_kernel); never beside d_law, a knot law, a basis or a covariance.
+// key_out: launch_noise's, passed on with an inactive model only (no other generator's noise can be regenerated)
 hipError_t launch_noise_model(float* noise, int B, int nu, int H, int Kp, uint64_t seed,
                               const unsigned long long* seed_ctr, float sigma, const NoiseModel& model,
-                              hipStream_t stream, const float* d_law = nullptr, const float* d_steps = nullptr);
+                              hipStream_t stream, const float* d_law = nullptr, const float* d_steps = nullptr,
+                              unsigned long long* key_out = nullptr);
 // The device law [kLawFloats] = sigma_u[kMaxNu], rho, c: set from a by-value model on the stream, and moved one step
 // by the rule of noise_adapt.h from one statistics slot (stats [B], m2 / m11 [B][nu]) after the law the solve drew
 // from was recorded into hist[0..nu] (sigma_u, rho).  One wave each; capturable.
@@ -379,9 +384,22 @@ struct NoiseGen {
   // the pitch of `next`'s rows where it differs from the pitch the reduce reads (mppi_set_population: the next
   // iteration samples another count); 0: the read pitch.  Last, so no other field moves
   int Kp_next = 0;
+  // ... and behind it: the device word that receives the key `next` is drawn with (or nullptr), as launch_noise's
+  unsigned long long* key_out = nullptr;
+  // reduce_kernel<REGEN> (reduce_regen.h; never beside `next`): the eighths of the noise it READS that are regenerated
+  // instead of loaded, from the key in *regen_key -- the word the generator of that noise wrote -- and `sigma`
+  int regen = 0;
+  const unsigned long long* regen_key = nullptr;
+};
+// The reduce that regenerates part of the noise it reads (reduce_regen.h): eighths in 1..7 and the noise's key word
+struct RegenArgs {
+  int eighths = 0;
+  const unsigned long long* key = nullptr;
+  float sigma = 0.0f;
 };
 hipError_t launch_reduce(const SolveArgs& a, const NoiseGen* gen, hipStream_t stream,  // softmin + reduce + update + shift
-                         bool gen_block = false);  // (gen_block: no generation, reduce_kernel<GEN>'s block size)
+                         bool gen_block = false,  // (gen_block: no generation, reduce_kernel<GEN>'s block size)
+                         const RegenArgs* regen = nullptr);  // (never beside gen)
 // analytic cartpole rollout; with a.part set it also runs a7-a9 (fused epilogue) and, given gen, writes the next
 // solve's noise (graph streams)
 hipError_t launch_cartpole_rollout(const SolveArgs& a, const CartpoleParams& p, const NoiseGen* gen, hipStream_t stream);

@@ -43,7 +43,7 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_get_noise_steps_adapt", "mppi_get_step_moments", "mppi_step_moments_eval", "mppi_set_iterations",
             "mppi_get_iterations", "mppi_get_best", "mppi_iter_best_eval", "mppi_gen_route",
             "mppi_noise_beside_eval", "mppi_set_population", "mppi_get_population", "mppi_population_icem",
-            "mppi_iter_rollout_kernel"]
+            "mppi_iter_rollout_kernel", "mppi_reduce_regen"]
 
 
 class MPPIError(RuntimeError):
@@ -124,6 +124,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_x3_layer1": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float)]),
         "mppi_rollout_kernel": (ctypes.c_char_p, [vp]),
         "mppi_gen_route": (ctypes.c_char_p, [vp]),
+        "mppi_reduce_regen": (i32, [vp]),
         "mppi_noise_beside_eval": (i32, [vp, i32, ctypes.c_uint64, vp]),
         "mppi_x3_f16": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float)]),
         "mppi_set_noise_model": (i32, [vp, _fp, ctypes.c_float]),

@@ -936,6 +936,11 @@ class Engine:
         beside the rollout), "fused" (inside the reduce) or "" before the first chained solve."""
         return (self.lib.mppi_gen_route(self._h) or b"").decode()
 
+    def reduce_regen(self) -> int:
+        """The eighths of its noise the last solve's reduce regenerated from the noise's key instead of reading them
+        (mppi_reduce_regen); 0 when it read everything.  MPPI_REDUCE_REGEN=0 turns it off, 1..7 force a share."""
+        return int(self.lib.mppi_reduce_regen(self._h))
+
     def noise_beside_eval(self, B: int, seed: int) -> np.ndarray:
         """The noise [B, nu, H, K] (float32) the overlap route's generator draws for the by-value key `seed`
         (mppi_noise_beside_eval): the default law's, bitwise noise_eval's with no noise model set."""

@@ -146,7 +146,10 @@ extern "C" {
  *      not admit; io.costs / io.weights and the [B][K] read-outs hold the step's last iteration's samples (below).
  *      Additive, version unchanged: mppi_gen_route / mppi_noise_beside_eval.  BEHAVIOUR (timing only): a chained
  *      solve may now generate the next solve's noise on a second, low-priority stream beside its rollout (decided per
- *      solve; MPPI_FLAG_CHAIN below).  Every output, the seed counter included, is bit for bit what it was. */
+ *      solve; MPPI_FLAG_CHAIN below).  Every output, the seed counter included, is bit for bit what it was.
+ *      Additive, version unchanged: mppi_reduce_regen.  BEHAVIOUR (timing only): a solve's read-only reduce may compute
+ *      part of the noise it sums from the key the noise was drawn with instead of reading it (decided per solve;
+ *      mppi_reduce_regen below).  Every output is bit for bit what it was. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -1090,6 +1093,14 @@ const char* mppi_gen_route(mppi_handle* h);
  * default law's, bit for bit what mppi_noise_eval returns with no noise model set.  Like mppi_noise_eval it drops a
  * prefetched noise (key sequence unchanged) and needs only mppi_create. */
 int mppi_noise_beside_eval(mppi_handle* h, int B, uint64_t seed, float* noise_out /* [B][nu][H][K] host */);
+/* The eighths of its noise the handle's last solve's reduce regenerated from the noise's key instead of reading them
+ * (1..7); 0 when it read everything, and before the first solve or for a NULL handle.  The reduce regenerates only
+ * where the noise buffer holds exactly what the default i.i.d. generator drew for the key recorded beside it, at the
+ * pitch being read -- never with injected io.noise, an active noise model, control bounds, kept elites or add_mean, nor
+ * inside a captured graph or a reduce that also generates the next noise -- and, by itself, only where one batch's noise
+ * is past 128 MiB (the reduce is then bandwidth-bound).  MPPI_REDUCE_REGEN (read per solve): 0 turns it off, 1..7 force
+ * that many eighths wherever the content allows, whatever the size.  The outputs are bit for bit the same either way. */
+int mppi_reduce_regen(mppi_handle* h);
 /* MPPI_PREC_BF16X3 with a CrossAttention net: *on = 1 if the rollouts run the fp16 form (MPPI_PREC_BF16X3 above) for
  * this handle's horizon, 2 with the opt-in one-product last layer (MPPI_X3_F16_L2=1), 0 if not (also before the first
  * solve); *probe_rel_err = the probe's max relative cost difference between the fp16 form and three products, the
