@@ -213,6 +213,11 @@ __global__ __launch_bounds__(64 * fa_nw(D, NT, NH)) void fa_rollout_kernel(Solve
 #pragma unroll
   for (int i = 0; i < MPPI_CTX_MAX; ++i) cx[i] = a.ctx ? a.ctx[(long)b * MPPI_CTX_MAX + i] : a.ctx_default[i];
   float cost = 0.0f, cu0 = 0.0f, cusq = 0.0f;
+  // sum over the steps of |u|^2: non-finite iff a control of the sample was (or its square overflowed).  The encoding's
+  // ReLU (fmaxf) turns a non-finite token into its bare position embedding, so the rows and tiles the samples share
+  // stay finite (no 0 x NaN in the attention's P V), and a running cost that does not read the actuator would come out
+  // finite too: such a sample's cost is +inf
+  float cuacc = 0.0f;
   auto eval_cost = [&](float u0, float usq, int t1) { return fa_cost(a.cost_kind, XU + tid * L, u0, usq, cx, t1); };
 
   f32x4 res[MPW][NT];  // residual stream, D layout
@@ -330,6 +335,7 @@ __global__ __launch_bounds__(64 * fa_nw(D, NT, NH)) void fa_rollout_kernel(Solve
         s2 = fmaf(u, u, s2);
       }
       cusq = s2;
+      cuacc += s2;
       cu0 = XU[tid * L + nx];
     }
 
@@ -573,7 +579,7 @@ __global__ __launch_bounds__(64 * fa_nw(D, NT, NH)) void fa_rollout_kernel(Solve
   kclock_record(a, kc);  // after the horizon's last barrier
   if (cown) {
     if (a.terminal_weight != 0.0f) cost += a.terminal_weight * eval_cost(0.0f, 0.0f, a.H);
-    if (ck < a.K) a.costs[(long)b * a.Kp + ck] = isfinite(cost) ? cost : INFINITY;
+    if (ck < a.K) a.costs[(long)b * a.Kp + ck] = isfinite(cost) && cuacc < INFINITY ? cost : INFINITY;
   }
   if (a.xout && k0 == 0 && tid < nx) a.xout[(long)b * nx + tid] = XU[tid];  // env step: sample 0's final state
 }

@@ -470,6 +470,10 @@ __global__ __launch_bounds__(256) void fal_encode_kernel(SolveArgs a, FalEnc e, 
     float u = a.U[((long)b * nu + tid) * a.H + t] + a.noise[(((long)b * nu + tid) * a.H + t) * a.Kp + k];
     if (a.ctrl_clamp > 0.0f) u = fminf(a.ctrl_clamp, fmaxf(-a.ctrl_clamp, u));
     XU[nx + tid] = u;
+    // a non-finite control: the sample's cost is +inf, as in fa_rollout_kernel, which tests the summed |u|^2 (the
+    // encoding's ReLU hides the token from the net, and the running cost may not read this actuator); written after
+    // thread 0's update above and before the next step's
+    if (!(fabsf(u) < INFINITY)) e.cost[gk] = INFINITY;
   }
   __syncthreads();
   auto vec = [&](int off, int c) { return *reinterpret_cast<const f32x4*>(e.img + off + 4 * (256 * c + 4 * lane)); };

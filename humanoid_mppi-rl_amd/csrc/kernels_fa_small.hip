@@ -142,6 +142,12 @@ void fa_small_kernel(SolveArgs a, FaArgs f) {
   const bool cown = h == 0 && tid < G;  // wave 0, lane s: the running cost of sample s
   const int cbase = (tid / Gt) * 16 + (tid % Gt) * L;
   float cost = 0.0f;
+  // sum over the steps of |u|^2: non-finite iff a control of the sample was (or its square overflowed).  The encoding's
+  // ReLU (fmaxf) turns a non-finite token into its bare position embedding, so the tile the samples share stays finite,
+  // and a running cost that does not read the actuator (cartpole_est reads none) would come out finite too: such a
+  // sample's cost is +inf (kernels_fa.hip does the same).  One v_add per step in wave 0; keeping the sum in another
+  // wave and handing it over through LDS after the horizon measured 0.9 % slower per cartpole estimator solve.
+  float uacc = 0.0f;
 
   f32x4 res[NT][4];  // residual stream of every tile, D layout: feature 16 mt + 4 g + r of token n
   // LayerNorm over the 64 features of token n (population variance, eps 1e-5) without its affine map (folded into
@@ -367,6 +373,7 @@ void fa_small_kernel(SolveArgs a, FaArgs f) {
         const float* xr = XU + cbase;
         float usq = 0.0f;
         for (int j = 0; j < nu; ++j) usq = fmaf(xr[nx + j], xr[nx + j], usq);
+        uacc += usq;
         cost += fa_cost(a.cost_kind, xr, nu > 0 ? xr[nx] : 0.0f, usq, cx, t + 1);
       }
       __builtin_amdgcn_wave_barrier();
@@ -381,7 +388,7 @@ void fa_small_kernel(SolveArgs a, FaArgs f) {
   if (cown) {
     if (a.terminal_weight != 0.0f) cost += a.terminal_weight * fa_cost(a.cost_kind, XU + cbase, 0.0f, 0.0f, cx, a.H);
     const int ck = k0 + tid;
-    if (ck < a.K) a.costs[(long)b * a.Kp + ck] = isfinite(cost) ? cost : INFINITY;
+    if (ck < a.K) a.costs[(long)b * a.Kp + ck] = isfinite(cost) && uacc < INFINITY ? cost : INFINITY;
   }
   if (a.xout && k0 == 0 && h == 0 && g == 0 && rvalid && tok < nx && n < L)  // env step: sample 0's final state
     a.xout[(long)b * nx + tok] = xu[0];

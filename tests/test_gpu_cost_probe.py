@@ -279,7 +279,7 @@ def test_ca_kernels(M, monkeypatch, group, i):
 # --------------------------------------------------------------------------------------- a non-finite sample
 
 @pytest.mark.parametrize("bad", [np.nan, np.inf], ids=["nan", "inf"])
-@pytest.mark.parametrize("route", ["f32", "bf16", "x3", "bf16-wave1", "x3m"])
+@pytest.mark.parametrize("route", list(MLP_ROUTES))
 def test_nonfinite_sample_poisons_only_itself(M, monkeypatch, route, bad):
     """One designed control of one sample is NaN (or +inf) at the middle step of H = 3: that sample's cost is non-finite
     and its weight 0, every other sample's cost is bitwise the cost of the same solve without it, and the solve's
@@ -310,3 +310,41 @@ def test_nonfinite_sample_poisons_only_itself(M, monkeypatch, route, bad):
     np.testing.assert_allclose(b.weights.sum(), 1.0, atol=1e-5)
     w = R.softmin_weights(np.where(others, a.costs.astype(np.float64), np.inf), 1.0)
     np.testing.assert_allclose(b.weights, w, atol=1e-5)
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf], ids=["nan", "inf"])
+@pytest.mark.parametrize("group", list(CA_ROUTES))
+def test_nonfinite_sample_poisons_only_itself_ca(M, monkeypatch, group, bad):
+    """The same on the folded humanoid cross-attention net (the shipped checkpoint, K = 64, B = 1 as the CA sweep), on
+    every kernel of CA_ROUTES: one control of one sample is NaN (or +inf) at the middle step of H = 3."""
+    from conftest import golden, golden_sd
+    from mppi_hip.nets import cross_attention_blob
+    precision, arms = CA_ROUTES[group]
+    K, H, k_bad, t_bad, u_bad = 64, 3, 37, 1, 4
+    rs = np.random.RandomState(6)
+    clean = (0.75 * rs.randn(21, H, K)).astype(np.float32)
+    dirty = clean.copy()
+    dirty[u_bad, t_bad, k_bad] = bad
+    x0 = golden("g5_ca_humanoid_fwd.npz")["x0_stride20"][3].astype(np.float32)
+    U = (0.1 * rs.randn(21, H)).astype(np.float32)
+    others = np.arange(K) != k_bad
+    _set_knobs(monkeypatch, arms[0][0] if group.startswith("generic") else {})
+    eng = M.Engine(M.Config(nx=55, nu=21, H=H, K=K, max_batch=1, lambda_=1.0, sigma=1.0, terminal_weight=1.0,
+                            precision=precision))
+    try:
+        eng.load_dynamics(*cross_attention_blob(golden_sd("ca_humanoid_weights.npz"))).set_cost("humanoid_v3")
+        for env, kernel in arms:
+            _set_knobs(monkeypatch, env)
+            a = eng.solve(x0, U, noise=clean, want_weights=True)
+            b = eng.solve(x0, U, noise=dirty, want_weights=True)
+            kern = eng.rollout_kernel()
+            assert kern == kernel, (kern, kernel)
+            assert np.isfinite(a.costs).all() and a.status == 0
+            assert not np.isfinite(b.costs[k_bad]) and b.weights[k_bad] == 0.0, kernel
+            np.testing.assert_array_equal(b.costs[others], a.costs[others], err_msg=kernel)
+            assert b.status == 0
+            np.testing.assert_allclose(b.weights.sum(), 1.0, atol=1e-5)
+            w = R.softmin_weights(np.where(others, a.costs.astype(np.float64), np.inf), 1.0)
+            np.testing.assert_allclose(b.weights, w, atol=1e-5)
+    finally:
+        eng.close()

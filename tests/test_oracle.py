@@ -227,3 +227,38 @@ def test_fa_general_shapes_match_reference_module(name):
     sd = mod.weights(spec)
     y = N.fa_forward(sd, g["x"].astype(np.float64), int(spec["nx"]), int(spec["heads"]))
     np.testing.assert_allclose(y, g["y"], rtol=1e-4, atol=2e-5)
+
+
+@pytest.mark.parametrize("precision", ["fp64", "fp32", "bf16"])
+@pytest.mark.parametrize("name", ["small-L5-2layers", "general-D128-4heads"])
+def test_fa_oracle_is_row_independent(name, precision):
+    """The premise of tests/test_gpu_fa_isolation.py: the oracle's FA dynamics treat every sample (row) on its own.
+    With one NaN (or +inf) control row every other row's next state keeps its bits, and R.mppi_solve gives a
+    non-finite cost for that column only."""
+    import fa_isolation_cases as C
+    c, i = C.BY_NAME[name], C.inputs(name)
+    dyn = N.fa_dynamics(C.weights(name), c.nx, nheads=c.heads, precision=precision)
+    dt = np.float64 if precision == "fp64" else np.float32
+    b, k, K = C.VICTIM_SOLVE, 5, 16
+    x = np.repeat(i["x0"][b].astype(dt)[None, :], K, axis=0)
+    u = (i["U0"][b][:, 0][None, :] + i["noise"][b][:, 0, :K].T).astype(dt)
+    clean = dyn(x, u)
+    assert np.isfinite(clean).all()
+    pre = R.Preset("t", K=K, H=C.H, lam=C.LAM, sigma=C.SIGMA, terminal_weight=C.TERMINAL_WEIGHT)
+    ctx = np.array(R.QUAD_GOAL) if c.cost == "quad_est" else None
+    ref = R.mppi_solve(pre, dyn, R.COSTS[c.cost], i["x0"][b], i["U0"][b], i["noise"][b][..., :K], ctx=ctx, dtype=dt)
+    assert np.isfinite(ref["costs"]).all()
+    others = np.arange(K) != k
+    for bad in (np.nan, np.inf):
+        ud = u.copy()
+        ud[k, c.dirty_actuator] = bad
+        got = dyn(x, ud)
+        assert not np.isfinite(got[k]).all()
+        assert got[others].tobytes() == clean[others].tobytes()
+        noise = i["noise"][b][..., :K].copy()
+        noise[c.dirty_actuator, C.DIRTY_STEP, k] = bad
+        with np.errstate(invalid="ignore"):
+            d = R.mppi_solve(pre, dyn, R.COSTS[c.cost], i["x0"][b], i["U0"][b], noise, ctx=ctx, dtype=dt)
+        assert not np.isfinite(d["costs"][k])
+        assert d["costs"][others].tobytes() == ref["costs"][others].tobytes()
+        assert d["weights"][k] == 0.0
