@@ -1924,7 +1924,9 @@ static int chain_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed, 
 // the probe covers -- fc_wave32_x3p_kernel (the large batches) and fc_rollout_kernel_x3h (the few-tiles shards), by
 // routes of its own (launch_fc_route) whatever the probe's batch -- kept only if both are within kX3ProbeTol of the
 // three-product costs
-// (FcNet::x3_f16 = 1, x3_f16_err = the larger error), else not (-1).  The probe covers up to kProbeB of the first batch's solves at kProbeK samples
+// (FcNet::x3_f16 = 1, x3_f16_err = the larger error), else not (-1).  A kernel that cannot hold the shape
+// (fc_route_can_run: fc_wave32_x3p_kernel outside 20 <= nu <= 22) is left out of the probe, as no route reaches it; if
+// neither can, the form stays off.  The probe covers up to kProbeB of the first batch's solves at kProbeK samples
 // each: the CA surrogate's dynamics do not depend on the controls (its action encoder never reaches the output), so
 // the form's error is one number per state -- more states, not more samples, find the worst.  For the same reason the
 // probe keeps its own white noise of cfg.sigma whatever mppi_set_noise_model selected: it is a per-state measure.
@@ -1964,7 +1966,7 @@ static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
   unsigned* p_st = reinterpret_cast<unsigned*>(p_ctx + (size_t)Bp * MPPI_CTX_MAX);
   hipStream_t s = h->stream;
   std::vector<float> hc1(nC), hc2(nC), hc3(nC), hch(nC), stage;
-  bool x3h = false;
+  bool x3h = false, x3p = false;
   auto run = [&]() -> hipError_t {
     const hipMemcpyKind k = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipError_t e = hipMemcpyAsync(p_x0, io->x0, (size_t)Bp * c.nx * 4, k, s);
@@ -2006,11 +2008,15 @@ static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
       const FcRoute r = fc_route(n.arch, n.precision, a, n.fa, terms, -1, cus, knobs);
       if (e == hipSuccess) e = launch_fc_route(a, n, r, s);
     }
-    if (f16) {  // the fp16 form (form 1; a knob that forces the form forces the probe's too) on fc_wave32_x3p_kernel
-      a.costs = p_c1;
-      const FcRoute rp = {FcKernel::x3p, x3_form(c.H, 3, 1, n.fa.w32f16_off, knobs), 1};
-      if (e == hipSuccess) e = launch_fc_route(a, n, rp, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(hc1.data(), p_c1, nC * 4, hipMemcpyDeviceToHost, s);
+    if (f16) {  // the fp16 form (form 1; a knob that forces the form forces the probe's too) on fc_wave32_x3p_kernel,
+                // where that kernel holds the shape (its operands take 20 <= nu <= 22: no route reaches it elsewhere)
+      x3p = fc_route_can_run(FcKernel::x3p, a, n.fa);
+      if (x3p) {
+        a.costs = p_c1;
+        const FcRoute rp = {FcKernel::x3p, x3_form(c.H, 3, 1, n.fa.w32f16_off, knobs), 1};
+        if (e == hipSuccess) e = launch_fc_route(a, n, rp, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(hc1.data(), p_c1, nC * 4, hipMemcpyDeviceToHost, s);
+      }
       a.costs = p_ch;
       x3h = fc_route_can_run(FcKernel::x3h, a, n.fa) && x3_f16_on(c.H, 1, n.fa.wmf16_off, knobs) && knobs.x3h;
       if (x3h) {  // ... and on fc_rollout_kernel_x3h
@@ -2043,9 +2049,10 @@ static int x3_probe(mppi_handle* h, int B, const mppi_io* io, int flags) {
   const double w2 = diff(hc2);
   h->net.x3_l1 = w2 <= kX3ProbeTol ? 2 : 3;
   h->net.x3_l1_err = (float)w2;
-  const double w1 = f16 ? std::fmax(diff(hc1), x3h ? diff(hch) : 0.0) : (double)INFINITY;
+  const bool f16_ran = f16 && (x3p || x3h);  // (neither kernel holds the shape: the form stays off, unmeasured)
+  const double w1 = f16_ran ? std::fmax(x3p ? diff(hc1) : 0.0, x3h ? diff(hch) : 0.0) : (double)INFINITY;
   h->net.x3_f16 = w1 <= kX3ProbeTol ? 1 : -1;
-  h->net.x3_f16_err = f16 ? (float)w1 : -1.0f;
+  h->net.x3_f16_err = f16_ran ? (float)w1 : -1.0f;
   return MPPI_OK;
 }
 

@@ -922,7 +922,8 @@ class Engine:
         """(form, probe_rel_err) of the split CA's fp16 form (mppi_x3_f16): 2 = on with the one-product last layer, 1 =
         on with the two-product one, 0 = off for this handle's horizon (also before the first solve and after
         set_cost, which resets the probe); and the probe's max relative cost difference between the fp16 form and three
-        products, the larger of its runs on fc_wave32_x3p_kernel and fc_rollout_kernel_x3h (-1: no probe ran)."""
+        products, the larger of its runs on fc_wave32_x3p_kernel and fc_rollout_kernel_x3h, each where it can hold the
+        shape (-1: no probe ran)."""
         n, e = ctypes.c_int(), ctypes.c_float()
         L.check(self.lib.mppi_x3_f16(self._h, ctypes.byref(n), ctypes.byref(e)))
         return int(n.value), float(e.value)

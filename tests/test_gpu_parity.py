@@ -1115,7 +1115,8 @@ def test_max_K_ca_softmin_and_update_properties(M):
 def test_max_dims_mlp_long_horizon(M, precision):
     """The fc-stack maxima at once: nx = 64 state slots, nu = 32 control slots, and nu * H = 16384 (the U row limit,
     H = 512), seeded MLPStatePredictor(64, 32) weights, quad_est cost (replace update), vs the oracle: fp32 costs
-    rtol 1e-4 and the full solve checks; bf16 costs rtol 5e-3 vs the bf16-rounding oracle."""
+    rtol 1e-4 and the full solve checks; bf16 costs rtol 5e-3 vs the bf16-rounding oracle.  A dense net at these bars
+    cannot see one misplaced slot: tests/test_gpu_slot_probe.py holds where every state and control slot lands."""
     from mppi_hip.nets import mlp_blob, synthetic_mlp
     nx, nu, K, H = 64, 32, 48, 512
     sd = synthetic_mlp(nx, nu, seed=9)
