@@ -15,6 +15,7 @@
 #include "ctrl_bounds.h"  // ctrl_bounds_valid
 #include "elite_keep.h"  // (the rule of mppi_set_elite_keep)
 #include "elite_select.h"  // (the rule of mppi_set_elites)
+#include "ensemble.h"  // (the rule of mppi_set_ensemble)
 #include "ess_target.h"  // EssTarget
 #include "gen_overlap.h"  // the rule that routes the next noise beside the rollout
 #include "reduce_regen.h"  // the rule by which the read-only reduce regenerates part of the noise it sums
@@ -72,11 +73,12 @@ enum KernelId {
   kStepMom = 13,
   kStepAdapt = 14,
   kIter = 15,
-  kNumKernels = 16
+  kEnsemble = 16,
+  kNumKernels = 17
 };
 const char* kKernelNames[kNumKernels] = {"noise", "rollout", "reduce", "update", "stats", "lambda", "ctrl_cost",
                                          "bounds", "rate_cost", "elites", "keep", "cross", "cov_adapt", "step_mom",
-                                         "step_adapt", "iter"};
+                                         "step_adapt", "iter", "ensemble"};
 
 struct PendingEvt {
   int id;
@@ -100,6 +102,7 @@ struct SolveOpts {
   bool step_mom = false;    // MPPI_FLAG_STEP_MOMENTS
   bool step_adapt = false;  // mppi_set_noise_steps_adapt
   bool iter = false;        // mppi_set_iterations: the best sample of the step is tracked
+  bool ens = false;         // mppi_set_ensemble: n rollouts and the combining launch
 };
 
 }  // namespace
@@ -357,6 +360,31 @@ struct mppi_handle {
   Shape last_shape() const { return iter_shape(pop_n > 0 ? pop_n - 1 : 0); }
   // the kernel iteration `it` of the last control step was routed to (mppi_iter_rollout_kernel)
   const char* iter_kernel[kPopMaxIter] = {nullptr};
+  // dynamics-model ensembles (mppi_set_ensemble; ensemble.h, kernels_ensemble.hip).  Member 0 is what
+  // mppi_load_dynamics loaded (net / net_env / fa / cart above); members 1..ens_extra, loaded densely by
+  // mppi_load_member through the same build and upload path, live in ens_mem[1..] (entry 0 is never read).  While
+  // ens_n > 1 every solve launches one rollout per member e < ens_n on the same x0, U, ctx and noise, member e writing
+  // row e of d_ens_costs, then ensemble_kernel, which writes d_costs and d_ens_sd; everything behind reads d_costs as
+  // before.  The env step runs member ens_env.  The buffers are allocated by the first enabling call, zero-filled; the
+  // member rows are max_batch * Kp apart whatever the iteration's shape (each row is re-read densely at it).
+  // d_ens_eval: mppi_ensemble_eval's own members [MPPI_ENS_MAX][max_batch][Kp], costs and sd [max_batch][Kp] each,
+  // allocated by its first call: an evaluation touches nothing a solve reads or writes.
+  struct Member {
+    CartpoleParams cart{};
+    FcNet net, net_env;
+    FaNet fa;
+  } ens_mem[MPPI_ENS_MAX];
+  int ens_extra = 0;               // members loaded behind member 0
+  int ens_n = 1;                   // n_members (1: off)
+  int ens_mode = MPPI_ENS_MEAN;
+  float ens_kappa = 0.0f;
+  int ens_env = 0;                 // env_member
+  float* d_ens_costs = nullptr;    // [MPPI_ENS_MAX][max_batch][Kp]
+  float* d_ens_sd = nullptr;       // [max_batch][Kp]
+  float* d_ens_eval = nullptr;     // [MPPI_ENS_MAX + 2][max_batch][Kp]
+  int ens_B = 0;                   // batch of the last solve / graph launch with an ensemble (0: none ran)
+  int graph_ens = 1;               // the members the captured graph's solves roll (stamped launches per solve)
+  int ens_loaded() const { return dyn_kind ? 1 + ens_extra : 0; }
 };
 
 // The shape a [B][K] read-out of output slot `slot` was written at: slot 0 is the last solve's -- with a population
@@ -507,6 +535,20 @@ static CartpoleParams default_cartpole() {
   return p;
 }
 
+// The ensemble's members behind member 0 (mppi_load_member): their device images freed, the slots as new.  The stream
+// is idle and no captured graph holds them (the callers see to both).
+static void free_member(mppi_handle::Member& m) {
+  if (m.net.fa.img) (void)hipFree(const_cast<char*>(m.net.fa.img));
+  if (m.net_env.fa.img) (void)hipFree(const_cast<char*>(m.net_env.fa.img));
+  if (m.fa.d_img) (void)hipFree(m.fa.d_img);
+  if (m.fa.d_ws) (void)hipFree(m.fa.d_ws);
+  m = mppi_handle::Member();
+}
+static void free_members(mppi_handle* h) {
+  for (int e = 1; e < MPPI_ENS_MAX; ++e) free_member(h->ens_mem[e]);
+  h->ens_extra = 0;
+}
+
 // --------------------------------------------------------------------------------------- presets
 
 struct PresetRow {
@@ -578,10 +620,11 @@ void mppi_destroy(mppi_handle* h) {
                   h->d_elite_wcost, h->d_elite_idx, h->d_elite_count, h->d_elite_tau, h->d_keep_v, h->d_keep_cost,
                   h->d_keep_idx, h->d_keep_count, h->d_keep_steps, h->d_keep_sel, h->d_keep_selcount, h->d_keep_tau,
                   h->d_keep_ecost, h->d_keep_U, h->d_steps, h->d_step_mom, h->d_best_v, h->d_best_cost, h->d_best_k,
-                  h->d_best_iter, h->d_best_U, h->d_nkey};
+                  h->d_best_iter, h->d_best_U, h->d_nkey, h->d_ens_costs, h->d_ens_sd, h->d_ens_eval};
   for (hipGraphExec_t& g : h->graph_exec)
     if (g) (void)hipGraphExecDestroy(g);
   if (h->gstream) (void)hipStreamSynchronize(h->gstream);
+  free_members(h);
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   if (h->ev_gen) (void)hipEventDestroy(h->ev_gen);
@@ -646,12 +689,14 @@ int mppi_create(const mppi_config* cfg, int device, mppi_handle** out) {
   return MPPI_OK;
 }
 
-int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes) {
-  if (!h) return fail(MPPI_E_ARG, "mppi_load_dynamics: null handle");
-  HIP_TRY(hipSetDevice(h->device));
+// One dynamics model built, uploaded and put into (cart, net_dst, env_dst, fa_dst): the handle's own for
+// mppi_load_dynamics (member 0), a slot of ens_mem for mppi_load_member.  A failure leaves the destination as it was.
+static int load_dyn(mppi_handle* h, const char* who_, int kind, const void* blob, size_t nbytes, CartpoleParams& cart,
+                    FcNet& net_dst, FcNet& env_dst, FaNet& fa_dst) {
+  const std::string who = std::string(who_) + ": ";
   if (kind == MPPI_DYN_CARTPOLE) {
     if (h->cfg.nx != 4 || h->cfg.nu != 1) return fail(MPPI_E_ARG, "cartpole dynamics need nx=4, nu=1");
-    h->cart = default_cartpole();
+    cart = default_cartpole();
     if (!h->d_part) {  // [max_batch][Kp/256][2 + H] partial records (fixed by the config: allocated once)
       const size_t n = (size_t)h->cfg.max_batch * ((h->Kp + 255) / 256) * (2 + h->cfg.H) * sizeof(float);
       HIP_TRY(hipMalloc(&h->d_part, n));
@@ -659,13 +704,12 @@ int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes
     }
     if (blob) {
       if (nbytes != 10 * sizeof(float)) return fail(MPPI_E_ARG, "cartpole params: expected 10 floats");
-      std::memcpy(&h->cart, blob, sizeof(CartpoleParams));
+      std::memcpy(&cart, blob, sizeof(CartpoleParams));
     }
-    h->dyn_kind = kind;
     return MPPI_OK;
   }
   if (kind == MPPI_DYN_MLP || kind == MPPI_DYN_CROSS_ATTN) {
-    if (!blob || nbytes == 0) return fail(MPPI_E_ARG, "mppi_load_dynamics: weight blob required");
+    if (!blob || nbytes == 0) return fail(MPPI_E_ARG, who + "weight blob required");
     std::vector<unsigned char> img, img_env;
     FcNet net, net_env;
     try {
@@ -673,16 +717,16 @@ int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes
       if (h->cfg.precision == MPPI_PREC_BF16X3)
         img_env = build_fc_net(kind, blob, nbytes, MPPI_PREC_FP32, h->cfg.nx, h->cfg.nu, net_env);
     } catch (const std::exception& ex) {
-      return fail(MPPI_E_UNSUPPORTED, std::string("mppi_load_dynamics: ") + ex.what());
+      return fail(MPPI_E_UNSUPPORTED, who + ex.what());
     }
     if (h->cfg.precision == MPPI_PREC_BF16 && net.fa.lds_bytes > 128 * 1024)
-      return fail(MPPI_E_UNSUPPORTED, "mppi_load_dynamics: LDS part of the packed bf16 image exceeds 128 KiB");
+      return fail(MPPI_E_UNSUPPORTED, who + "LDS part of the packed bf16 image exceeds 128 KiB");
     HIP_TRY(hipStreamSynchronize(h->stream));
     void* d = nullptr;
     HIP_TRY(hipMalloc(&d, img.size()));
     if (const hipError_t e = hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice); e != hipSuccess) {
       (void)hipFree(d);
-      return fail(MPPI_E_HIP, std::string("mppi_load_dynamics: image upload: ") + hipGetErrorString(e));
+      return fail(MPPI_E_HIP, who + "image upload: " + hipGetErrorString(e));
     }
     void* d_env = nullptr;
     if (!img_env.empty()) {
@@ -691,40 +735,39 @@ int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes
       if (e != hipSuccess) {
         (void)hipFree(d);
         (void)hipFree(d_env);
-        return fail(MPPI_E_HIP, std::string("mppi_load_dynamics: env-step image upload: ") + hipGetErrorString(e));
+        return fail(MPPI_E_HIP, who + "env-step image upload: " + hipGetErrorString(e));
       }
     }
-    if (h->net.fa.img) (void)hipFree(const_cast<char*>(h->net.fa.img));
-    if (h->net_env.fa.img) (void)hipFree(const_cast<char*>(h->net_env.fa.img));
+    if (net_dst.fa.img) (void)hipFree(const_cast<char*>(net_dst.fa.img));
+    if (env_dst.fa.img) (void)hipFree(const_cast<char*>(env_dst.fa.img));
     net.fa.img = static_cast<const char*>(d);
     net_env.fa.img = static_cast<const char*>(d_env);
-    h->net_env = net_env;
+    env_dst = net_env;
     net.x3_l1 = 0;  // a new net: the split layer-1 probe runs again at the next solve (x3_probe)
-    h->net = net;
-    h->dyn_kind = kind;
+    net_dst = net;
     return MPPI_OK;
   }
   if (kind == MPPI_DYN_FEATURE_ATTN) {
-    if (!blob || nbytes == 0) return fail(MPPI_E_ARG, "mppi_load_dynamics: weight blob required");
+    if (!blob || nbytes == 0) return fail(MPPI_E_ARG, who + "weight blob required");
     if (h->cfg.precision == MPPI_PREC_BF16X3)
-      return fail(MPPI_E_UNSUPPORTED, "mppi_load_dynamics: MPPI_PREC_BF16X3 is built for the fc nets (MLP, CA) only");
+      return fail(MPPI_E_UNSUPPORTED, who + "MPPI_PREC_BF16X3 is built for the fc nets (MLP, CA) only");
     std::vector<unsigned char> img;
     FaNet net;
     try {
       img = build_fa_net(blob, nbytes, h->cfg.precision, h->cfg.nx, h->cfg.nu, net);
     } catch (const std::exception& ex) {
-      return fail(MPPI_E_UNSUPPORTED, std::string("mppi_load_dynamics: ") + ex.what());
+      return fail(MPPI_E_UNSUPPORTED, who + ex.what());
     }
     const int lds = fa_lds_bytes(net.D, net.precision, net.nh, net.L);
     if (lds <= 0 || lds > 160 * 1024)
-      return fail(MPPI_E_UNSUPPORTED, "mppi_load_dynamics: feature-attention shape does not fit the kernel's LDS");
+      return fail(MPPI_E_UNSUPPORTED, who + "feature-attention shape does not fit the kernel's LDS");
     HIP_TRY(hipStreamSynchronize(h->stream));
     // the new image first: the loaded net stays in place (and usable) if anything below fails
     void* d = nullptr;
     HIP_TRY(hipMalloc(&d, img.size()));
     if (const hipError_t e = hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice); e != hipSuccess) {
       (void)hipFree(d);
-      return fail(MPPI_E_HIP, std::string("mppi_load_dynamics: image upload: ") + hipGetErrorString(e));
+      return fail(MPPI_E_HIP, who + "image upload: " + hipGetErrorString(e));
     }
     net.d_img = d;
     const char* lay_env = getenv("MPPI_FA_LAYERED");
@@ -743,13 +786,54 @@ int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes
       }
       (void)hipGetLastError();  // a failed optional allocation leaves no sticky error behind
     }
-    if (h->fa.d_img) (void)hipFree(h->fa.d_img);
-    if (h->fa.d_ws) (void)hipFree(h->fa.d_ws);
-    h->fa = net;
-    h->dyn_kind = kind;
+    if (fa_dst.d_img) (void)hipFree(fa_dst.d_img);
+    if (fa_dst.d_ws) (void)hipFree(fa_dst.d_ws);
+    fa_dst = net;
     return MPPI_OK;
   }
-  return fail(MPPI_E_UNSUPPORTED, "mppi_load_dynamics: unknown dynamics kind");
+  return fail(MPPI_E_UNSUPPORTED, who + "unknown dynamics kind");
+}
+
+int mppi_load_dynamics(mppi_handle* h, int kind, const void* blob, size_t nbytes) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_load_dynamics: null handle");
+  if (h->ens_n > 1)
+    return fail(MPPI_E_STATE, "mppi_load_dynamics: an ensemble is on (call mppi_set_ensemble(h, 1, ...) first, or "
+                              "replace a member with mppi_load_member)");
+  HIP_TRY(hipSetDevice(h->device));
+  MPPI_TRY(load_dyn(h, "mppi_load_dynamics", kind, blob, nbytes, h->cart, h->net, h->net_env, h->fa));
+  h->dyn_kind = kind;
+  free_members(h);  // member 0 is new, maybe of another kind: the members behind it go (the stream is idle, no graph holds them)
+  return MPPI_OK;
+}
+
+int mppi_load_member(mppi_handle* h, int e, int kind, const void* blob, size_t nbytes) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_load_member: null handle");
+  if (e < 1 || e >= MPPI_ENS_MAX) return fail(MPPI_E_ARG, "mppi_load_member: e must be in [1, MPPI_ENS_MAX)");
+  if (h->dyn_kind == 0) return fail(MPPI_E_STATE, "mppi_load_member: call mppi_load_dynamics first (member 0)");
+  if (kind != h->dyn_kind) return fail(MPPI_E_ARG, "mppi_load_member: the members are of member 0's kind");
+  if (e > h->ens_loaded())
+    return fail(MPPI_E_ARG, "mppi_load_member: members are loaded densely (e beyond the number loaded)");
+  if (kind == MPPI_DYN_CROSS_ATTN && h->cfg.precision == MPPI_PREC_BF16X3)
+    return fail(MPPI_E_UNSUPPORTED, "mppi_load_member / mppi_set_ensemble: the CrossAttention net at MPPI_PREC_BF16X3 "
+                                    "takes its split form from a probe of member 0 alone; no ensemble of it is built");
+  if (kind == MPPI_DYN_CARTPOLE && blob && nbytes != 10 * sizeof(float))
+    return fail(MPPI_E_ARG, "mppi_load_member: cartpole params: expected 10 floats");
+  HIP_TRY(hipSetDevice(h->device));
+  // built and uploaded beside the member it replaces, so that a blob the loader refuses changes nothing
+  mppi_handle::Member m;
+  MPPI_TRY(load_dyn(h, "mppi_load_member", kind, blob, nbytes, m.cart, m.net, m.net_env, m.fa));
+  // a member in use sits by value in the captured graphs' launches: they go before its image does (load_dyn has waited
+  // for the stream)
+  if (e < h->ens_n) {
+    if (const int rc = drop_graphs(h, true); rc != MPPI_OK) {
+      free_member(m);
+      return rc;
+    }
+  }
+  free_member(h->ens_mem[e]);
+  h->ens_mem[e] = m;
+  if (e == h->ens_loaded()) h->ens_extra += 1;
+  return MPPI_OK;
 }
 
 int mppi_set_cost(mppi_handle* h, int kind, const float* params, int nparams) {
@@ -1278,11 +1362,14 @@ static int check_solve(mppi_handle* h, int B, const mppi_io* io, int flags) {
   return MPPI_OK;
 }
 
-static hipError_t launch_rollout(mppi_handle* h, const SolveArgs& a, hipStream_t s) {
-  if (h->dyn_kind == MPPI_DYN_CARTPOLE) return launch_cartpole_rollout(a, h->cart, nullptr, s);
-  if (h->dyn_kind == MPPI_DYN_FEATURE_ATTN) return launch_fa_rollout(a, h->fa, s);
-  if (a.xout && h->net_env.fa.img) return launch_fc_rollout(a, h->net_env, s);  // the split mode's env step: exact fp32
-  return launch_fc_rollout(a, h->net, s);
+// member: which model of an ensemble rolls (mppi_set_ensemble); 0, every handle without one: what mppi_load_dynamics loaded
+static hipError_t launch_rollout(mppi_handle* h, const SolveArgs& a, hipStream_t s, int member = 0) {
+  const mppi_handle::Member* m = member > 0 ? &h->ens_mem[member] : nullptr;
+  if (h->dyn_kind == MPPI_DYN_CARTPOLE) return launch_cartpole_rollout(a, m ? m->cart : h->cart, nullptr, s);
+  if (h->dyn_kind == MPPI_DYN_FEATURE_ATTN) return launch_fa_rollout(a, m ? m->fa : h->fa, s);
+  const FcNet& env = m ? m->net_env : h->net_env;
+  if (a.xout && env.fa.img) return launch_fc_rollout(a, env, s);  // the split mode's env step: exact fp32
+  return launch_fc_rollout(a, m ? m->net : h->net, s);
 }
 
 // A graph launch leaves the next launch's first noise prefetched, generated with one counter value ahead.  When
@@ -1358,6 +1445,7 @@ static SolveOpts solve_opts(const mppi_handle* h, int flags) {
   o.step_mom = (flags & MPPI_FLAG_STEP_MOMENTS) != 0;
   o.step_adapt = h->steps_adapt_on;
   o.iter = h->iter_on();
+  o.ens = h->ens_n > 1;
   return o;
 }
 
@@ -1389,6 +1477,7 @@ static void note_ran(mppi_handle* h, const SolveOpts& o, int B, int n) {
     h->stepm_n = n;
   }
   if (o.iter) h->best_B = B;
+  if (o.ens) h->ens_B = B;
 }
 
 // One iteration of a control step (mppi_set_iterations): its index and the step's count.  The first iteration stages the
@@ -1460,14 +1549,16 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
   // o.ctrl: the softmin weighs d_wcost = costs + term; o.rate: d_rate_wcost = (costs [+ control term]) + rate term;
   // o.elite: d_elite_wcost, the chain's end on the elite set (below)
   const SolveOpts o = solve_opts(h, flags);
-  const bool cart_unfused = (lam || o.ctrl || o.rate || o.elite || o.keep || o.iter) && h->dyn_kind == MPPI_DYN_CARTPOLE;
+  const bool cart_unfused =
+      (lam || o.ctrl || o.rate || o.elite || o.keep || o.iter || o.ens) && h->dyn_kind == MPPI_DYN_CARTPOLE;
   int iter_count = 1;  // "iter" is counted once per iteration, by the first of its launches
   // launch clock: only solves that use the seed counter are stamped (bench.py's timed paths); the cartpole's unfused
   // rollout carries no stamp
   a.kclock = (h->kclock && a.seed_ctr && !cart_unfused) ? h->d_kclock : nullptr;
   a.kclock_ctr = h->d_kclock ? h->d_kclock + 2 * (size_t)kClockSlots : nullptr;
   a.kclock_ticket = h->d_kclock ? reinterpret_cast<unsigned*>(h->d_kclock + 2 * (size_t)kClockSlots + 1) : nullptr;
-  if (a.kclock && !h->capturing) h->kclock_launches += 1;  // graph replays count graph_n each (mppi_graph_launch)
+  // graph replays count graph_n each (mppi_graph_launch); an ensemble stamps every member's launch
+  if (a.kclock && !h->capturing) h->kclock_launches += o.ens ? h->ens_n : 1;
 
   // ---- inputs
   if (dev) {
@@ -1607,7 +1698,15 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     // it runs the unfused rollout of the env step, a.part == nullptr, then the search and reduce_kernel: 3 launches;
     // and a cartpole with the control-cost or the rate term, whose epilogue would weigh costs the term has not reached
     // yet, or with elites or kept elites, whose selection needs every cost of the solve)
-    HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, a, s); }));
+    // an ensemble (mppi_set_ensemble): member e rolls the same x0, U, ctx and noise into row e of the members' costs --
+    // rows max_batch * Kp apart whatever this iteration's shape, each written densely at it.  Member 0 first: the
+    // kernel reports, the fit decision of the noise overlap and the generator beside the rollout are its launch's
+    auto member_args = [&](int e) {
+      SolveArgs m = a;
+      m.costs = h->d_ens_costs + (size_t)e * c.max_batch * h->Kp;
+      return m;
+    };
+    HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, o.ens ? member_args(0) : a, s); }));
     h->rollout_kernel = h->iter_kernel[it] = g_rollout_kernel;
     if (ov == kGenByFit) {  // the rule's last condition, on the kernel this very launch (this iteration's) was routed to
       if (gen_fits(func_regs(h, g_rollout_func), func_regs(h, noise_beside_func()))) {
@@ -1632,6 +1731,15 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
       pg = nullptr;
     }
     if (ov == kGenForced) MPPI_TRY(gen_beside());
+    if (o.ens) {
+      // the members behind member 0, in order on the stream, then the one combining launch: d_costs and the spread
+      // from the n rows.  From here on the solve is the single-model solve on those costs
+      for (int e = 1; e < h->ens_n; ++e)
+        HIP_TRY(timed(h, kRollout, [&] { return launch_rollout(h, member_args(e), s, e); }));
+      const EnsembleArgs ea{h->ens_n, h->ens_mode, h->ens_kappa, ensemble_rcp(h->ens_n), (long)B * Kp / 4,
+                            (long)c.max_batch * h->Kp, h->d_ens_costs, a.costs, h->d_ens_sd};
+      HIP_TRY(timed(h, kEnsemble, [&] { return launch_ensemble(ea, s); }));
+    }
     if (o.ctrl) {
       // the control-cost term, behind the rollout (its costs exist) and ahead of the reduce (a.U is still the nominal the
       // rollout perturbed).  An adapting handle's ctrl_lin_kernel reads d_law on the stream: at this point it still
@@ -1762,7 +1870,7 @@ static int enqueue_solve(mppi_handle* h, int B, const mppi_io* io, uint64_t seed
     e.terminal_weight = 0.0f;
     e.xout = const_cast<float*>(io->x0);
     if (rec_x) HIP_TRY(launch_record(io->x0, a.u0, rec_x, rec_u, B * nx, B * nu, s));
-    HIP_TRY(launch_rollout(h, e, s));
+    HIP_TRY(launch_rollout(h, e, s, o.ens ? h->ens_env : 0));  // (an ensemble steps under its env_member)
   }
 
   // ---- outputs (the step's last iteration's: rows of cfg.K, of which that iteration's K samples are written -- with a
@@ -2204,6 +2312,7 @@ int mppi_graph_capture_traj(mppi_handle* h, int B, const mppi_io* io, uint64_t s
   h->capturing = false;
   h->graph_kclock = h->kclock;
   h->graph_opts = solve_opts(h, flags);
+  h->graph_ens = h->ens_n;
   h->graph_B = B;
   h->graph_n = n_total;  // (what a launch counts: slots, stamped rollouts, the noise pair's parity)
   h->graph_seed = seed;
@@ -2220,7 +2329,7 @@ int mppi_graph_launch(mppi_handle* h, int sync) {
   MPPI_TRY(prime_prefetch(h, h->graph_B, h->graph_seed));
   HIP_TRY(hipGraphLaunch(h->graph_exec[h->graph_parity], h->stream));
   h->pristine[0].ok = h->pristine[1].ok = false;  // (the replay wrote both buffers; the host followed none of it)
-  if (h->graph_kclock) h->kclock_launches += h->graph_n;
+  if (h->graph_kclock) h->kclock_launches += (long)h->graph_n * h->graph_ens;
   note_ran(h, h->graph_opts, h->graph_B, h->graph_n);
   h->graph_parity = (h->graph_parity + h->graph_n) % 2;  // the launch prefetched the next one's first noise
   if (!sync) return MPPI_OK;
@@ -3536,7 +3645,7 @@ int mppi_set_population(mppi_handle* h, const int32_t* K_it, int n) {
   h->pop_n = tn;
   std::memcpy(h->pop_K, tab, sizeof(tab));
   // the [B][K] read-outs of the last solve lie at the old table's last shape: none to read until the next solve
-  h->ctrl_B = h->rate_B = h->elite_B = 0;
+  h->ctrl_B = h->rate_B = h->elite_B = h->ens_B = 0;
   return MPPI_OK;
 }
 
@@ -3608,6 +3717,124 @@ int mppi_iter_best_eval(mppi_handle* h, int B, const float* U, const float* nois
   HIP_TRY(timed(h, kIter, [&] { return launch_iter_best(ia, s); }));
   HIP_TRY(hipStreamSynchronize(s));
   return copy_best(h, B, 1, v, cost, k, iter);
+}
+
+int mppi_set_ensemble(mppi_handle* h, int n_members, int mode, float kappa, int env_member) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_set_ensemble: null handle");
+  if (n_members < 1 || n_members > MPPI_ENS_MAX)
+    return fail(MPPI_E_ARG, "mppi_set_ensemble: n_members must be in [1, MPPI_ENS_MAX]");
+  if (!ensemble_mode_valid(mode)) return fail(MPPI_E_ARG, "mppi_set_ensemble: mode must be one of MPPI_ENS_*");
+  if (!ensemble_kappa_valid(kappa)) return fail(MPPI_E_ARG, "mppi_set_ensemble: kappa must be finite");
+  if (env_member < 0 || env_member >= n_members)
+    return fail(MPPI_E_ARG, "mppi_set_ensemble: env_member must be in [0, n_members)");
+  if (n_members > 1 && n_members > h->ens_loaded())
+    return fail(MPPI_E_ARG, "mppi_set_ensemble: n_members beyond the members loaded (mppi_load_dynamics is member 0, "
+                            "mppi_load_member the others)");
+  if (n_members == h->ens_n && (n_members == 1 || (mode == h->ens_mode && kappa == h->ens_kappa &&
+                                                   env_member == h->ens_env))) {
+    if (n_members == 1) h->ens_mode = mode, h->ens_kappa = kappa;  // (read by nothing while off)
+    return MPPI_OK;  // in effect: graphs and prefetch stay
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  if (n_members > 1 && !h->d_ens_costs) {  // the first enabling call: the members' rows and the spread, zero-filled
+    const size_t row = (size_t)h->cfg.max_batch * h->Kp * 4;
+    float *mc = nullptr, *sd = nullptr;
+    MPPI_TRY(alloc_group("mppi_set_ensemble", {{(void**)&mc, MPPI_ENS_MAX * row}, {(void**)&sd, row}}));
+    hipError_t e = hipMemset(mc, 0, MPPI_ENS_MAX * row);
+    if (e == hipSuccess) e = hipMemset(sd, 0, row);
+    if (e != hipSuccess) {
+      (void)hipFree(mc);
+      (void)hipFree(sd);
+      return fail(MPPI_E_HIP, std::string("mppi_set_ensemble: ") + hipGetErrorString(e));
+    }
+    h->d_ens_costs = mc;
+    h->d_ens_sd = sd;
+  }
+  // stale state, as in mppi_set_noise_model: the captured graphs hold the members and the rule's settings in their
+  // launches (a launch still in flight finishes first), and a prefetched noise is dropped (the counter steps back: the
+  // key sequence is unchanged)
+  HIP_TRY(drop_prefetch(h));
+  MPPI_TRY(drop_graphs(h, true));
+  h->ens_n = n_members;
+  h->ens_mode = mode;
+  h->ens_kappa = kappa;
+  h->ens_env = env_member;
+  h->ens_B = 0;  // the read-outs describe a solve under the setting in effect: none yet
+  return MPPI_OK;
+}
+
+int mppi_get_ensemble(mppi_handle* h, int* n_members, int* mode, float* kappa, int* env_member, int* n_loaded) {
+  if (!h) return fail(MPPI_E_ARG, "mppi_get_ensemble: null handle");
+  if (n_members) *n_members = h->ens_n;
+  if (mode) *mode = h->ens_mode;
+  if (kappa) *kappa = h->ens_kappa;
+  if (env_member) *env_member = h->ens_env;
+  if (n_loaded) *n_loaded = h->ens_loaded();
+  return MPPI_OK;
+}
+
+// [B][K] of a [max_batch][Kp] device row written by the last solve -> host (the stream is idle)
+static int copy_ens_row(mppi_handle* h, int B, const float* src, float* dst) {
+  const mppi_handle::Shape sh = readout_shape(h, 0);  // (rows of cfg.K, of which the solve's K samples are written)
+  HIP_TRY(hipMemcpy2D(dst, (size_t)h->cfg.K * 4, src, (size_t)sh.Kp * 4, (size_t)sh.K * 4, B, hipMemcpyDeviceToHost));
+  return MPPI_OK;
+}
+
+static int ens_readout_check(mppi_handle* h, const char* who, int B) {
+  if (h->ens_B == 0)
+    return fail(MPPI_E_STATE, std::string(who) + ": no solve with the ensemble in effect has run on the handle");
+  if (B < 1 || B > h->ens_B) return fail(MPPI_E_ARG, std::string(who) + ": B beyond the batch of the last ensemble solve");
+  return MPPI_OK;
+}
+
+int mppi_get_member_costs(mppi_handle* h, int B, int e, float* costs) {
+  if (!h || !costs) return fail(MPPI_E_ARG, "mppi_get_member_costs: null argument");
+  MPPI_TRY(ens_readout_check(h, "mppi_get_member_costs", B));
+  if (e < 0 || e >= h->ens_n) return fail(MPPI_E_ARG, "mppi_get_member_costs: e must be in [0, n_members)");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_ens_row(h, B, h->d_ens_costs + (size_t)e * h->cfg.max_batch * h->Kp, costs);
+}
+
+int mppi_get_ensemble_spread(mppi_handle* h, int B, float* sd) {
+  if (!h || !sd) return fail(MPPI_E_ARG, "mppi_get_ensemble_spread: null argument");
+  MPPI_TRY(ens_readout_check(h, "mppi_get_ensemble_spread", B));
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return copy_ens_row(h, B, h->d_ens_sd, sd);
+}
+
+int mppi_ensemble_eval(mppi_handle* h, int B, int n, int mode, float kappa, const float* member_costs, float* costs,
+                       float* sd) {
+  if (!h || !member_costs) return fail(MPPI_E_ARG, "mppi_ensemble_eval: null argument");
+  const mppi_config& c = h->cfg;
+  if (B < 1 || B > c.max_batch) return fail(MPPI_E_ARG, "mppi_ensemble_eval: B out of range [1, max_batch]");
+  if (n < 2 || n > MPPI_ENS_MAX) return fail(MPPI_E_ARG, "mppi_ensemble_eval: n must be in [2, MPPI_ENS_MAX]");
+  if (!ensemble_mode_valid(mode)) return fail(MPPI_E_ARG, "mppi_ensemble_eval: mode must be one of MPPI_ENS_*");
+  if (!ensemble_kappa_valid(kappa)) return fail(MPPI_E_ARG, "mppi_ensemble_eval: kappa must be finite");
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t K = (size_t)c.K, Kp = (size_t)h->Kp, row = (size_t)c.max_batch * Kp;
+  if (!h->d_ens_eval) {  // the evaluation's own members, costs and spread: no buffer of a solve is touched
+    float* p = nullptr;
+    MPPI_TRY(alloc_group("mppi_ensemble_eval", {{(void**)&p, (MPPI_ENS_MAX + 2) * row * 4}}));
+    if (const hipError_t e = hipMemset(p, 0, (MPPI_ENS_MAX + 2) * row * 4); e != hipSuccess) {  // (the pads K..Kp)
+      (void)hipFree(p);
+      return fail(MPPI_E_HIP, std::string("mppi_ensemble_eval: ") + hipGetErrorString(e));
+    }
+    h->d_ens_eval = p;
+  }
+  hipStream_t s = h->stream;
+  float* const d_costs = h->d_ens_eval + MPPI_ENS_MAX * row;
+  float* const d_sd = d_costs + row;
+  for (int e = 0; e < n; ++e)  // member e's [B][K] host rows into its device rows [B][Kp]
+    HIP_TRY(hipMemcpy2DAsync(h->d_ens_eval + (size_t)e * row, Kp * 4, member_costs + (size_t)e * B * K, K * 4, K * 4, B,
+                             hipMemcpyHostToDevice, s));
+  const EnsembleArgs ea{n, mode, kappa, ensemble_rcp(n), (long)((size_t)B * Kp / 4), (long)row, h->d_ens_eval, d_costs, d_sd};
+  HIP_TRY(timed(h, kEnsemble, [&] { return launch_ensemble(ea, s); }));
+  if (costs) HIP_TRY(hipMemcpy2DAsync(costs, K * 4, d_costs, Kp * 4, K * 4, B, hipMemcpyDeviceToHost, s));
+  if (sd) HIP_TRY(hipMemcpy2DAsync(sd, K * 4, d_sd, Kp * 4, K * 4, B, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MPPI_OK;
 }
 
 // slot `slot` of the diagnostics' buffers -> host (the stream is idle)

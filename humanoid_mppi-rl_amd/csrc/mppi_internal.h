@@ -554,6 +554,20 @@ struct RateArgs {
 };
 hipError_t launch_rate_cost(const RateArgs& a, hipStream_t stream);  // the term and wcost (one of two forms)
 hipError_t launch_rate_store_prev(const float* u0, float* u_prev, int n, hipStream_t stream);  // u_prev <- u0 [n]
+// kernels_ensemble.hip: the members' costs of a dynamics-model ensemble combined per sample (mppi_set_ensemble; the rule:
+// ensemble.h), by value like SolveArgs, so the launch can sit in a captured graph.
+struct EnsembleArgs {
+  int n;                 // members, 2..MPPI_ENS_MAX
+  int mode;              // MPPI_ENS_*
+  float kappa;
+  float r;               // ensemble_rcp(n), computed on the host
+  long n4;               // B Kp / 4: the lanes' count (the rows of one member are dense)
+  long stride;           // floats between member e's and member e + 1's rows (a multiple of 4, >= B Kp)
+  const float* members;  // [n][stride]
+  float* costs;          // [B][Kp] out
+  float* sd;             // [B][Kp] out
+};
+hipError_t launch_ensemble(const EnsembleArgs& a, hipStream_t stream);
 hipError_t launch_record(const float* x, const float* u, float* rx, float* ru, int nxB, int nuB, hipStream_t stream);
 
 }  // namespace mppi

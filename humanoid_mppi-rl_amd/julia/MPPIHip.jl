@@ -968,6 +968,75 @@ function best(c::Controller)
     return (permutedims(v, (2, 1)), cost[], Int(k[]) + 1, Int(it[]) + 1)
 end
 
+const ENS_MODES = Dict(:mean => 0, :mean_std => 1, :worst => 2)  # MPPI_ENS_*
+
+"""
+    load_member!(c, e, kind, weights)
+
+Member `e` (1:7) of a dynamics-model ensemble (mppi_load_member): a weight blob file of the kind the controller was
+created with (`:mlp`, `:feature_attention`, `:cross_attention`), or for `:cartpole` a vector of its 10 parameters
+(`nothing`: the defaults).  Member 0 is the model the controller loaded; members are loaded densely.
+"""
+function load_member!(c::Controller, e::Integer, kind::Symbol, weights)
+    if kind == :cartpole
+        p = weights === nothing ? Float32[] : Vector{Float32}(weights)
+        GC.@preserve p check(ccall((:mppi_load_member, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Csize_t),
+                                   c.handle, e, DYN_CARTPOLE, isempty(p) ? C_NULL : pointer(p), sizeof(p)))
+        return c
+    end
+    blob = read(weights)
+    k = kind == :mlp ? DYN_MLP : kind == :feature_attention ? DYN_FEATURE_ATTN : DYN_CROSS_ATTN
+    check(ccall((:mppi_load_member, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{UInt8}, Csize_t), c.handle, e, k, blob,
+                length(blob)))
+    return c
+end
+
+"""
+    set_ensemble!(c, n; mode = :mean, kappa = 0, env_member = 0)
+
+Roll every sample under members `0:n-1` and combine their costs per sample on the device (mppi_set_ensemble; the PE of
+PETS): `:mean`, `:mean_std` (mean + kappa * population std; a negative kappa is an optimism bonus) or `:worst`.
+`n == 1` turns it off.  `env_member` (0-based, as the ABI) steps the environment.  Any change destroys captured graphs.
+"""
+function set_ensemble!(c::Controller, n::Integer; mode::Symbol = :mean, kappa::Real = 0, env_member::Integer = 0)
+    haskey(ENS_MODES, mode) || throw(ArgumentError("mode must be :mean, :mean_std or :worst"))
+    check(ccall((:mppi_set_ensemble, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Cfloat, Cint), c.handle, n, ENS_MODES[mode],
+                Float32(kappa), env_member))
+    return c
+end
+
+"""
+    ensemble(c) -> (n, mode::Symbol, kappa::Float32, env_member, n_loaded)
+
+The setting of `set_ensemble!` and the number of members loaded, member 0 included (mppi_get_ensemble).
+"""
+function ensemble(c::Controller)
+    n, mode, env, loaded, kappa = Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0), Ref{Cfloat}(0)
+    check(ccall((:mppi_get_ensemble, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Cfloat}, Ref{Cint}, Ref{Cint}),
+                c.handle, n, mode, kappa, env, loaded))
+    name = first(k for (k, v) in ENS_MODES if v == mode[])
+    return (Int(n[]), name, Float32(kappa[]), Int(env[]), Int(loaded[]))
+end
+
+"""
+    member_costs(c, e) -> Vector{Float32}        ensemble_spread(c) -> Vector{Float32}
+
+Member `e`'s (0-based) costs and the members' population std per sample, length K, of the last solve made with an
+ensemble on (mppi_get_member_costs, mppi_get_ensemble_spread; both wait for the stream).
+"""
+function member_costs(c::Controller, e::Integer)
+    out = zeros(Float32, c.cfg.K)
+    GC.@preserve out check(ccall((:mppi_get_member_costs, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float32}), c.handle,
+                                 1, e, pointer(out)))
+    return out
+end
+function ensemble_spread(c::Controller)
+    out = zeros(Float32, c.cfg.K)
+    GC.@preserve out check(ccall((:mppi_get_ensemble_spread, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}), c.handle, 1,
+                                 pointer(out)))
+    return out
+end
+
 """
     solve_stats(c) -> (stats::SolveStats, eps_m2::Vector{Float32}, eps_m11::Vector{Float32})
 

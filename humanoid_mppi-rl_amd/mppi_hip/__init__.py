@@ -13,7 +13,7 @@ from .controller import (MPPIModel, SimData, mppi_controller, mppi_step, mppi_up
                          rollout_learned_model_batched)
 from .engine import Config, Engine, SolveResult
 from .stats import (adapt_noise_model, adapt_noise_model_f32, control_term_ref, elite_select_ref, ess_lambda_ref,
-                    ess_ref, iter_best_ref, keep_inject_ref, keep_store_ref, project_noise_ref, rate_term_ref, solve_stats_ref)
+                    ensemble_combine_f32, ess_ref, iter_best_ref, keep_inject_ref, keep_store_ref, project_noise_ref, rate_term_ref, solve_stats_ref)
 from .nets import (cross_attention_blob, feature_attention_blob, load_npz, mlp_blob, pack_blob,
                    synthetic_feature_attention, synthetic_mlp)
 
@@ -22,4 +22,4 @@ __all__ = ["Config", "Engine", "SolveResult", "MPPIModel", "SimData", "rollout",
            "cross_attention_blob", "feature_attention_blob", "mlp_blob", "synthetic_mlp", "synthetic_feature_attention",
            "solve_stats_ref", "adapt_noise_model", "adapt_noise_model_f32", "ess_ref", "ess_lambda_ref",
            "control_term_ref", "project_noise_ref", "rate_term_ref", "elite_select_ref",
-           "keep_store_ref", "keep_inject_ref", "iter_best_ref"]
+           "keep_store_ref", "keep_inject_ref", "iter_best_ref", "ensemble_combine_f32"]

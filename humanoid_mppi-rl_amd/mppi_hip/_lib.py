@@ -43,7 +43,8 @@ EXPORTED = ["mppi_preset", "mppi_create", "mppi_destroy", "mppi_load_dynamics", 
             "mppi_get_noise_steps_adapt", "mppi_get_step_moments", "mppi_step_moments_eval", "mppi_set_iterations",
             "mppi_get_iterations", "mppi_get_best", "mppi_iter_best_eval", "mppi_gen_route",
             "mppi_noise_beside_eval", "mppi_set_population", "mppi_get_population", "mppi_population_icem",
-            "mppi_iter_rollout_kernel", "mppi_reduce_regen"]
+            "mppi_iter_rollout_kernel", "mppi_reduce_regen", "mppi_load_member", "mppi_set_ensemble",
+            "mppi_get_ensemble", "mppi_get_member_costs", "mppi_get_ensemble_spread", "mppi_ensemble_eval"]
 
 
 class MPPIError(RuntimeError):
@@ -189,6 +190,13 @@ def load(path: str | None = None) -> ctypes.CDLL:
         "mppi_get_population": (i32, [vp, vp, ctypes.POINTER(i32)]),
         "mppi_population_icem": (i32, [i32, i32, ctypes.c_double, i32, vp]),
         "mppi_iter_rollout_kernel": (ctypes.c_char_p, [vp, i32]),
+        "mppi_load_member": (i32, [vp, i32, i32, vp, sz]),
+        "mppi_set_ensemble": (i32, [vp, i32, i32, ctypes.c_float, i32]),
+        "mppi_get_ensemble": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_float),
+                                    ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "mppi_get_member_costs": (i32, [vp, i32, i32, vp]),
+        "mppi_get_ensemble_spread": (i32, [vp, i32, vp]),
+        "mppi_ensemble_eval": (i32, [vp, i32, i32, i32, ctypes.c_float, vp, vp, vp]),
         "mppi_kernel_clock_read": (i32, [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_double)]),
     }

@@ -23,7 +23,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib as L
-from .engine import Config, Engine
+from .engine import ENSEMBLE_MODES, Config, Engine
 from .nets import cross_attention_blob, feature_attention_blob, mlp_blob
 from .noise import ar1_filter, basis_filter, colored_basis, knot_filter, steps_filter
 from .stats import adapt_noise_model
@@ -48,7 +48,8 @@ class MPPIModel:
     """The reference script's module-level state for one controller, plus the engine handle.
 
     dynamics: "cartpole" (analytic mj_step restatement), ("cross_attention", state_dict[, dims dict]),
-              ("feature_attention", state_dict[, dims dict]) or ("mlp", state_dict[, dims dict]).
+              ("feature_attention", state_dict[, dims dict]) or ("mlp", state_dict[, dims dict]); or an ensemble of one
+              kind, ("mlp_ensemble", [state_dict, ...][, dims dict]) and so on (ensemble_mode below).
     noise:    "device" -> Philox on the GPU (seeded, advances per call);
               "numpy"  -> np.random.randn(nu,T,K)*sigma from numpy's global RNG, exactly the reference's draw
                           (src/cartpole_mppi.py:89), injected into the engine.
@@ -103,6 +104,11 @@ class MPPIModel:
               the step instead of the mean's, add_mean enters the nominal as a candidate in the last iteration.  Needs
               device noise when n_iter > 1 and excludes u0_before when n_iter > 1 or return_best.  (1, False, False)
               (default): one solve per step.
+    ensemble_mode, ensemble_kappa: with dynamics = ("mlp_ensemble", [sd0, sd1, ...][, dims]) -- likewise
+              "cross_attention_ensemble", "feature_attention_ensemble", and "cartpole_ensemble" with parameter sets of 10
+              floats -- every sample is rolled under each of the 2..8 members and the members' costs are combined per
+              sample on the device (Engine.load_member, Engine.set_ensemble; the PE of PETS): "mean" (default),
+              "mean_std" (mean + ensemble_kappa * population std; a negative kappa is an optimism bonus) or "worst".
     """
 
     def __init__(self, preset: str = "cartpole_py", dynamics="cartpole", cost: str | None = None, device: int = 0,
@@ -112,7 +118,7 @@ class MPPIModel:
                  lambda_limits=(1e-3, 1e3), control_cost: float = 0.0, u_min=None, u_max=None, rate_cost=None,
                  rate_anchor: bool = True, n_elite: int = 0, n_keep: int = 0, noise_knots=None, noise_basis=None,
                  noise_steps=None, adapt_steps: float = 0.0, n_iter: int = 1, return_best: bool = False,
-                 add_mean: bool = False, **overrides):
+                 add_mean: bool = False, ensemble_mode: str = "mean", ensemble_kappa: float = 0.0, **overrides):
         """body_ids: 0-based MuJoCo body ids of HUMANOID_BODIES (default: src/humanoid.xml's, HUMANOID_BODY_IDS)
         for the per-call humanoid context; u0_before: apply U[:,0] before the update
         (src/quadruped_datacollection.py:170, MPPI_FLAG_U0_BEFORE)."""
@@ -146,6 +152,11 @@ class MPPIModel:
         if u0_before and (n_iter > 1 or return_best):
             raise ValueError("MPPIModel: u0_before excludes n_iter > 1 and return_best")
         self.n_iter, self.return_best, self.add_mean = int(n_iter), bool(return_best), bool(add_mean)
+        if ensemble_mode not in ENSEMBLE_MODES:
+            raise ValueError(f"MPPIModel: ensemble_mode must be one of {sorted(ENSEMBLE_MODES)}")
+        self.ensemble_mode, self.ensemble_kappa = ensemble_mode, float(ensemble_kappa)
+        if not np.isfinite(self.ensemble_kappa):
+            raise ValueError("MPPIModel: ensemble_kappa must be finite")
         self.preset = preset
         self.body_ids = dict(HUMANOID_BODY_IDS if body_ids is None else body_ids)
         self.u0_before = bool(u0_before)
@@ -162,16 +173,32 @@ class MPPIModel:
         else:
             kind, sd = dynamics[0], dynamics[1]
             dims = dynamics[2] if len(dynamics) > 2 else {}
-            if kind == "cross_attention":
-                k, blob = cross_attention_blob(sd, **dims)
-            elif kind == "mlp":
-                k, blob = mlp_blob(sd, state_dim=self.config.nx, action_dim=self.config.nu, **dims)
-            elif kind == "feature_attention":
-                dims = {"hidden_dim": np.asarray(sd["feature_encoding.0.weight"]).shape[0], **dims}
-                k, blob = feature_attention_blob(sd, state_dim=self.config.nx, action_dim=self.config.nu, **dims)
-            else:
+
+            def blob_of(kind, sd):
+                if kind == "cross_attention":
+                    return cross_attention_blob(sd, **dims)
+                if kind == "mlp":
+                    return mlp_blob(sd, state_dim=self.config.nx, action_dim=self.config.nu, **dims)
+                if kind == "feature_attention":
+                    d = {"hidden_dim": np.asarray(sd["feature_encoding.0.weight"]).shape[0], **dims}
+                    return feature_attention_blob(sd, state_dim=self.config.nx, action_dim=self.config.nu, **d)
+                if kind == "cartpole":  # a parameter set: the 10 floats of mppi_load_dynamics, or None for the defaults
+                    return L.DYN_CARTPOLE, None if sd is None else np.asarray(sd, np.float32).reshape(10).tobytes()
                 raise ValueError(f"unknown dynamics {kind!r}")
-            self.engine.load_dynamics(k, blob)
+
+            if isinstance(kind, str) and kind.endswith("_ensemble"):
+                members = list(sd)
+                if not 2 <= len(members) <= 8:
+                    raise ValueError("MPPIModel: an ensemble takes 2..8 members")
+                for e, m in enumerate(members):
+                    k, blob = blob_of(kind[:-len("_ensemble")], m)
+                    if e == 0:
+                        self.engine.load_dynamics(k, blob)
+                    else:
+                        self.engine.load_member(e, k, blob)
+                self.engine.set_ensemble(len(members), self.ensemble_mode, self.ensemble_kappa)
+            else:
+                self.engine.load_dynamics(*blob_of(kind, sd))
         self.cost = cost or PRESET_COST[preset]
         self.engine.set_cost(self.cost, ctx)
         # the humanoid goal (ctx[0:3]) the per-call real-env context keeps: the caller's, when one was given

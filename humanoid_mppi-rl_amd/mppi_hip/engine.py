@@ -10,6 +10,8 @@ from . import _lib as L
 
 _KINDS_COST = {"cartpole": L.COST_CARTPOLE, "cartpole_est": L.COST_CARTPOLE_EST, "humanoid_v3": L.COST_HUMANOID_V3,
                "humanoid_v1": L.COST_HUMANOID_V1, "quad_jl": L.COST_QUAD_JL, "quad_est": L.COST_QUAD_EST}
+# MPPI_ENS_* (include/mppi.h): how an ensemble's member costs become one cost per sample
+ENSEMBLE_MODES = {"mean": 0, "mean_std": 1, "worst": 2}
 
 
 @dataclass
@@ -720,6 +722,71 @@ class Engine:
         """The kernel iteration `it` of the last control step's rollout was routed to (mppi_iter_rollout_kernel); ""
         outside [0, n_iter) or before any solve."""
         return (self.lib.mppi_iter_rollout_kernel(self._h, int(it)) or b"").decode()
+
+    # -- dynamics-model ensembles (mppi_set_ensemble; mppi_hip.stats.ensemble_combine_f32 restates the rule)
+    def load_member(self, e: int, kind: int, blob: bytes | None = None):
+        """Member e >= 1 of an ensemble (mppi_load_member): any blob load_dynamics accepts for this config, of member 0's
+        kind; members are loaded densely and a loaded e is replaced.  Member 0 is what load_dynamics loaded."""
+        if blob is None:
+            L.check(self.lib.mppi_load_member(self._h, int(e), kind, None, 0))
+        else:
+            buf = ctypes.create_string_buffer(blob, len(blob))
+            L.check(self.lib.mppi_load_member(self._h, int(e), kind, buf, len(blob)))
+        return self
+
+    def set_ensemble(self, n: int, mode="mean", kappa: float = 0.0, env_member: int = 0):
+        """Roll every sample under members 0..n-1 and combine their costs per sample on the device (mppi_set_ensemble):
+        mode "mean", "mean_std" (mean + kappa * population std; kappa < 0 is an optimism bonus) or "worst" (the max).
+        n == 1 turns it off (loaded members stay).  env_member steps the environment.  Any change destroys captured
+        graphs and drops a prefetched noise (key sequence unchanged)."""
+        m = ENSEMBLE_MODES.get(mode, mode)
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in ENSEMBLE_MODES.values():
+            raise ValueError(f"set_ensemble: mode must be one of {sorted(ENSEMBLE_MODES)}")
+        L.check(self.lib.mppi_set_ensemble(self._h, int(n), int(m), float(kappa), int(env_member)))
+        return self
+
+    def ensemble(self) -> dict:
+        """The setting in effect and the number of members loaded, member 0 included (mppi_get_ensemble)."""
+        n, mode, env, loaded = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        kappa = ctypes.c_float(0.0)
+        L.check(self.lib.mppi_get_ensemble(self._h, ctypes.byref(n), ctypes.byref(mode), ctypes.byref(kappa),
+                                           ctypes.byref(env), ctypes.byref(loaded)))
+        names = {v: k for k, v in ENSEMBLE_MODES.items()}
+        return {"n": n.value, "mode": names[mode.value], "kappa": float(kappa.value), "env_member": env.value,
+                "n_loaded": loaded.value}
+
+    def member_costs(self, e: int, B: int = 1) -> np.ndarray:
+        """Member e's costs [B, K] of the last solve with the ensemble on (mppi_get_member_costs): bit for bit the costs
+        of an engine that loaded that member alone."""
+        out = np.zeros((int(B), self.config.K), np.float32)
+        L.check(self.lib.mppi_get_member_costs(self._h, int(B), int(e), _ptr(out)))
+        return out
+
+    def ensemble_spread(self, B: int = 1) -> np.ndarray:
+        """The members' population std per sample [B, K] of the last solve with the ensemble on
+        (mppi_get_ensemble_spread)."""
+        out = np.zeros((int(B), self.config.K), np.float32)
+        L.check(self.lib.mppi_get_ensemble_spread(self._h, int(B), _ptr(out)))
+        return out
+
+    def ensemble_eval(self, member_costs, mode="mean", kappa: float = 0.0):
+        """The combining kernel on host arrays member_costs [n, B, K] (NaN and +-inf allowed) -> (costs, sd), [B, K] each
+        (mppi_ensemble_eval).  The handle's state is untouched; no dynamics or cost need be loaded."""
+        c = self.config
+        mc = _f32(member_costs)
+        if mc.ndim == 2:
+            mc = mc[:, None, :]
+        if mc.ndim != 3 or mc.shape[2] != c.K:
+            raise ValueError("ensemble_eval: member_costs must be [n, B, K]")
+        m = ENSEMBLE_MODES.get(mode, mode)
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in ENSEMBLE_MODES.values():
+            raise ValueError(f"ensemble_eval: mode must be one of {sorted(ENSEMBLE_MODES)}")
+        n, B = mc.shape[0], mc.shape[1]
+        mc = np.ascontiguousarray(mc)
+        costs = np.zeros((B, c.K), np.float32)
+        sd = np.zeros((B, c.K), np.float32)
+        L.check(self.lib.mppi_ensemble_eval(self._h, B, n, int(m), float(kappa), _ptr(mc), _ptr(costs), _ptr(sd)))
+        return costs, sd
 
     # -- host-memory solve
     def solve(self, x0, U, noise=None, seed: int = 0, ctx=None, shift: bool = False, u0_before: bool = False,

@@ -78,6 +78,10 @@ step_moments_ref is the float64 restatement, step_moments_f32 the device's own s
 the per-step sampling scales (mppi_set_noise_steps_adapt; csrc/step_law.h is the fp32 rule) moves every solve's table
 towards its own moments, about the weighted mean or about zero, and shifts it with the nominal: adapt_noise_steps is
 the float64 restatement, adapt_noise_steps_f32 the step as the device takes it, bit for bit.
+
+Dynamics-model ensembles (mppi_set_ensemble; csrc/ensemble.h is the fp32 rule): every sample is rolled under each of n
+members and the members' costs become one cost per sample -- their mean, mean + kappa * population std, or maximum --
+beside their spread.  ensemble_combine_f32 is the rule as the device takes it, bit for bit.
 """
 from __future__ import annotations
 
@@ -1029,3 +1033,56 @@ def icem_population(K: int, n_iter: int, gamma: float, k_min: int) -> np.ndarray
         out[i] = max(k_min, int(float(K) / d))
         d *= gamma
     return out
+
+
+ENSEMBLE_MODES = {"mean": 0, "mean_std": 1, "worst": 2}  # MPPI_ENS_* (include/mppi.h)
+
+
+def ensemble_combine_f32(member_costs, mode="mean", kappa: float = 0.0):
+    """The combining rule of a dynamics-model ensemble (mppi_set_ensemble; csrc/ensemble.h) as the device takes it, float32
+    operation by operation -> (costs, sd), each of member_costs' shape without its first axis, bit for bit the device's.
+
+    member_costs [n, ...] float32, 2 <= n <= 8, the members' costs of every sample; r = float32(1) / float32(n):
+
+        any member not finite:  cost = +inf, sd = +inf
+        s = c_0;  s = s + c_e  ascending;  m = s * r;  every member bit for bit c_0: m = c_0
+        q = +0;   q = fmaf(c_e - m, c_e - m, q)  ascending;  sd = sqrt(q * r)
+        "mean": cost = m;  "mean_std": cost = fmaf(kappa, sd, m);  "worst": cost = the max, +0 above -0
+        a non-finite cost becomes +inf, a non-finite sd becomes +inf"""
+    m_id = ENSEMBLE_MODES.get(mode, mode)
+    if isinstance(m_id, bool) or m_id not in ENSEMBLE_MODES.values():
+        raise ValueError(f"ensemble_combine_f32: mode must be one of {sorted(ENSEMBLE_MODES)}")
+    c = np.asarray(member_costs, np.float32)
+    if c.ndim < 1 or not 2 <= c.shape[0] <= 8:
+        raise ValueError("ensemble_combine_f32: member_costs must be [n, ...] with 2 <= n <= 8")
+    kappa = np.float32(kappa)
+    if not np.isfinite(kappa):
+        raise ValueError("ensemble_combine_f32: kappa must be finite")
+    n = c.shape[0]
+    r = np.float32(1.0) / np.float32(n)
+    inf = np.float32(np.inf)
+    with np.errstate(all="ignore"):
+        fin = np.isfinite(c).all(axis=0)
+        s = c[0].copy()
+        mx = c[0].copy()
+        for e in range(1, n):
+            s = (s + c[e]).astype(np.float32)
+            # the larger; of two zeros, +0
+            mx = np.where(mx < c[e], c[e], np.where(c[e] < mx, mx, np.where(np.signbit(mx), c[e], mx)))
+        u = np.ascontiguousarray(c).view(np.uint32)
+        same = (u == u[0]).all(axis=0)  # n equal numbers: their mean is that number
+        m = np.where(same, c[0], (s * r).astype(np.float32)).astype(np.float32)
+        q = np.zeros_like(m)
+        for e in range(n):
+            d = (c[e] - m).astype(np.float32)
+            q = _fma32_vec(d, d, q)
+        sd = np.sqrt((q * r).astype(np.float32)).astype(np.float32)
+        if m_id == 0:
+            cost = m
+        elif m_id == 1:
+            cost = _fma32_vec(np.broadcast_to(kappa, sd.shape).astype(np.float32), sd, m)
+        else:
+            cost = mx.astype(np.float32)
+        cost = np.where(fin & np.isfinite(cost), cost, inf).astype(np.float32)
+        sd = np.where(fin & np.isfinite(sd), sd, inf).astype(np.float32)
+    return cost, sd

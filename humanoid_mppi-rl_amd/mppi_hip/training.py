@@ -166,6 +166,29 @@ def train_mlp(X: np.ndarray, Y: np.ndarray, state_dim: int, action_dim: int, hid
                  eval_set, log)
 
 
+def train_mlp_ensemble(X: np.ndarray, Y: np.ndarray, n_members: int, state_dim: int, action_dim: int,
+                       hidden_dim: int = 128, hidden_layers: int = 2, epochs: int = 50, batch: int = 32, lr: float = 1e-4,
+                       device: str = "cuda", bootstrap: bool = True, seed: int = 0, eval_set=None, log=print) -> list:
+    """The probabilistic ensemble of PETS for Engine.load_dynamics / load_member / set_ensemble: member i is train_mlp
+    with seed seed + i (its own init and batch order) on a bootstrap resample of the rows -- len(X) draws with
+    replacement from np.random.default_rng(seed + i); bootstrap=False trains every member on all rows, apart by their
+    seeds alone.  Returns the members' state dicts (numpy), member 0 first."""
+    n_members = int(n_members)
+    if not 2 <= n_members <= 8:
+        raise ValueError("train_mlp_ensemble: n_members must be in 2..8 (MPPI_ENS_MAX)")
+    X, Y = np.asarray(X, np.float32), np.asarray(Y, np.float32)
+    out = []
+    for i in range(n_members):
+        Xi, Yi = X, Y
+        if bootstrap:
+            idx = np.random.default_rng(seed + i).integers(0, len(X), size=len(X))
+            Xi, Yi = X[idx], Y[idx]
+        model, _ = train_mlp(Xi, Yi, state_dim, action_dim, hidden_dim, hidden_layers, epochs, batch, lr, device,
+                             seed + i, eval_set, log)
+        out.append(state_dict_numpy(model))
+    return out
+
+
 def train_fa(X: np.ndarray, Y: np.ndarray, state_dim: int, action_dim: int, hidden_dim: int = 512, num_heads: int = 4,
              attn_layers: int = 2, epochs: int = 50, batch: int = 32, lr: float = 1e-4, device: str = "cuda",
              seed: int = 0, eval_set=None, log=print):

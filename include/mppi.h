@@ -149,7 +149,14 @@ extern "C" {
  *      solve; MPPI_FLAG_CHAIN below).  Every output, the seed counter included, is bit for bit what it was.
  *      Additive, version unchanged: mppi_reduce_regen.  BEHAVIOUR (timing only): a solve's read-only reduce may compute
  *      part of the noise it sums from the key the noise was drawn with instead of reading it (decided per solve;
- *      mppi_reduce_regen below).  Every output is bit for bit what it was. */
+ *      mppi_reduce_regen below).  Every output is bit for bit what it was.
+ *      Additive, version unchanged: mppi_load_member / mppi_set_ensemble / mppi_get_ensemble / mppi_get_member_costs /
+ *      mppi_get_ensemble_spread / mppi_ensemble_eval and MPPI_ENS_* (dynamics-model ensembles, the PE of PETS: every
+ *      sample rolled under each of up to 8 members and the members' costs combined per sample on the device, in every
+ *      stream form; for the analytic cartpole a parameter ensemble); kernel name "ensemble" in mppi_kernel_time.  A
+ *      handle that never enables an ensemble, or sets n_members == 1, launches exactly the kernels it launched before,
+ *      with the same grids and arguments.  BEHAVIOUR while an ensemble is on only: mppi_load_dynamics returns
+ *      MPPI_E_STATE; "rollout" counts n_members launches per solve and mppi_kernel_clock stamps each of them. */
 #define MPPI_ABI_VERSION 4
 
 /* ---- status codes ---- */
@@ -1014,6 +1021,67 @@ int mppi_set_population(mppi_handle* h, const int32_t* K_it /* [n] host, or NULL
 int mppi_get_population(mppi_handle* h, int32_t* K_it /* [16] or NULL */, int* n /* 0 while off */);
 int mppi_population_icem(int K, int n_iter, double gamma, int k_min, int32_t* K_it /* [n_iter] */);
 const char* mppi_iter_rollout_kernel(mppi_handle* h, int it);
+
+/* Dynamics-model ensembles (the probabilistic ensemble of PETS; for the analytic cartpole a parameter ensemble: domain
+ * randomisation, robust MPPI): every sample of a solve is rolled under each of n members and the members' costs are
+ * combined, per sample, ON THE DEVICE and in every stream form, into the one cost everything behind the rollout reads.
+ * THE DEFINITION is a loop, as for mppi_set_iterations.  With n members on, member e's costs are, bit for bit, the
+ * io.costs of a handle of the same config that loaded blob e alone and solved on the same inputs and noise key (the
+ * cartpole: in its unfused form); the combined costs are the rule below over them; everything behind -- the cost terms,
+ * the elites, the keep store, the best-sample tracking, the lambda search, the reduce, the statistics, the adapted
+ * laws -- is the existing solve on the combined costs, and io.costs returns them.  Every member reads the same x0, U,
+ * ctx and noise (injected, kept-elite-injected and bounds-projected as without an ensemble); the n rollouts are
+ * launched in member order on the handle's stream, each routed as the handle that loaded it alone would be, and one
+ * launch of ensemble_kernel follows (kernel name "ensemble", counted once per iteration; "rollout" counts n).  With
+ * n_iter > 1 every iteration runs the n rollouts and the combine, with a population table at that iteration's shape.
+ * Chained solves, MPPI_FLAG_ASYNC, captured graphs and trajectory logging give bit for bit what a loop of plain solves
+ * on the same handle gives.  The env step (MPPI_FLAG_ENV_STEP) runs member env_member, at MPPI_PREC_BF16X3 its fp32
+ * image.  mppi_rollout_kernel and mppi_iter_rollout_kernel report member 0's kernel; the noise overlap of chained
+ * solves is decided on, and runs beside, member 0's launch; mppi_kernel_clock stamps every member's launch.  The
+ * analytic cartpole takes its unfused rollout while an ensemble is on, exactly as for elites.
+ * THE RULE is csrc/ensemble.h (host + device); mppi_hip.stats.ensemble_combine_f32 is its numpy restatement, bitwise
+ * equal.  Per sample k, over all Kp lanes of a row (the pads are never counted downstream), fp32 with contraction off,
+ * with c_e the members' costs and r = 1.0f / (float)n computed once on the host:
+ *     any c_e not finite:  cost = +inf, sd = +inf
+ *     s = c_0;  s = s + c_e  for e ascending;  m = s * r;  every c_e bit for bit c_0: m = c_0
+ *     q = +0;   q = fmaf(c_e - m, c_e - m, q)  for e ascending;  sd = sqrtf(q * r)        (the population std)
+ *     MPPI_ENS_MEAN: cost = m;   MPPI_ENS_MEAN_STD: cost = fmaf(kappa, sd, m);
+ *     MPPI_ENS_WORST: cost = fmaxf chained from c_0 ascending (of two zeros, +0)
+ *     a non-finite cost becomes +inf; a non-finite sd becomes +inf
+ * The mean of n equal numbers is that number, which the sums alone give for n in {2, 4} only (3 c is not always a float,
+ * and n c overflows where c does not): with that line n identical members give the single model's cost bit for bit and
+ * sd = +0, for every n and in every mode.
+ * mppi_load_member(e, kind, blob): member 0 is what mppi_load_dynamics loads; 1 <= e < MPPI_ENS_MAX goes through the
+ * same build and upload path (at MPPI_PREC_BF16X3 the fp32 env image included) and accepts any blob the loader accepts
+ * for the handle's nx, nu and precision: members may differ in hidden size, each is routed on its own; the cartpole
+ * takes its 10 parameters (NULL: the defaults).  Needs member 0 loaded (MPPI_E_STATE) and the same kind (MPPI_E_ARG);
+ * members are loaded densely: e greater than the number loaded is MPPI_E_ARG, a loaded e is replaced (captured graphs
+ * that roll it are destroyed).  A refused blob changes nothing.  The CrossAttention net at MPPI_PREC_BF16X3 returns
+ * MPPI_E_UNSUPPORTED and names both setters in mppi_last_error: its split form is decided by a probe of member 0 alone.
+ * mppi_load_dynamics returns MPPI_E_STATE while an ensemble is on and, while off, frees members 1 and above.
+ * mppi_set_ensemble: 2 <= n_members <= the loaded count enables, n_members == 1 disables (loaded members stay); mode
+ * one of MPPI_ENS_*; kappa finite (negative: an optimism bonus); 0 <= env_member < n_members; anything else is
+ * MPPI_E_ARG and changes nothing.  The first enabling call allocates the members' costs [MPPI_ENS_MAX][max_batch][Kp]
+ * and the spread [max_batch][Kp], zero-filled; nothing is allocated inside a solve.  Any change drops a prefetched
+ * noise and destroys captured graphs exactly as mppi_set_noise_model does (the key sequence is unchanged) and forgets
+ * the last solve's read-outs; setting the value already in effect keeps all of them.
+ * mppi_get_ensemble: the setting and the number of members loaded (member 0 included); each pointer may be NULL.
+ * mppi_get_member_costs / mppi_get_ensemble_spread: member e's costs and the spread of the last solve enqueued (after a
+ * graph launch the chain's last solve; with n_iter > 1 the last iteration's, at its shape as io.costs); wait for the
+ * stream.  MPPI_E_STATE before any solve under the setting in effect, MPPI_E_ARG for B or e beyond it.
+ * mppi_ensemble_eval: the same kernel on host arrays, member_costs [n][B][K], through buffers of its own: the handle's
+ * state, its prefetched noise included, is left alone.  Needs only mppi_create; costs and sd may be NULL. */
+#define MPPI_ENS_MAX 8
+#define MPPI_ENS_MEAN 0      /* mean over the members                                  */
+#define MPPI_ENS_MEAN_STD 1  /* mean + kappa * population std over the members         */
+#define MPPI_ENS_WORST 2     /* max over the members                                   */
+int mppi_load_member(mppi_handle* h, int e, int kind, const void* blob, size_t nbytes);   /* 1 <= e < MPPI_ENS_MAX */
+int mppi_set_ensemble(mppi_handle* h, int n_members, int mode, float kappa, int env_member);
+int mppi_get_ensemble(mppi_handle* h, int* n_members, int* mode, float* kappa, int* env_member, int* n_loaded);
+int mppi_get_member_costs(mppi_handle* h, int B, int e, float* costs /* [B][K] */);
+int mppi_get_ensemble_spread(mppi_handle* h, int B, float* sd /* [B][K] */);
+int mppi_ensemble_eval(mppi_handle* h, int B, int n, int mode, float kappa,
+                       const float* member_costs /* [n][B][K] host */, float* costs, float* sd /* [B][K] */);
 
 /* Solve diagnostics (MPPI_FLAG_STATS).  Besides mppi_solve_stats, the per-actuator moments of the noise the solve
  * used, weighted with w and taken about zero, i.e. about the nominal U, as the update itself is:
